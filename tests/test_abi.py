@@ -33,7 +33,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert set(_lib.ENGINE_SYMBOLS) == set(_declared("distdiff_hip.h"))
 
 
-def test_struct_mirrors_match_c_layout():
+def test_struct_mirrors_match_c_layout(tmp_path):
     """ctypes mirrors must have the size the C compiler gives the POD parameter blocks."""
     src = r'''
     #include <stdio.h>
@@ -43,8 +43,8 @@ def test_struct_mirrors_match_c_layout():
                        sizeof(AttnParams), sizeof(dd_config), sizeof(dd_sampler_params), sizeof(dd_expand_args), sizeof(ConvF32Params));
                 return 0; }
     '''
-    exe = "/tmp/dd_sizes"
-    cpp = "/tmp/dd_sizes.cpp"
+    exe = str(tmp_path / "dd_sizes")
+    cpp = str(tmp_path / "dd_sizes.cpp")
     open(cpp, "w").write(src)
     r = subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-I", os.path.abspath(ROOT), "-o", exe, cpp], text=True,
                        capture_output=True, cwd=ROOT)

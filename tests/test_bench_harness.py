@@ -145,3 +145,51 @@ def test_resolve_world():
         bench.resolve_world(8, {"RANK": "0", "WORLD_SIZE": "1"})
     with pytest.raises(SystemExit):
         bench.resolve_world(0, {})
+
+
+def test_bench_steps_and_dump_outputs_on_the_stub(tmp_path):
+    """`--steps K` is the number of timed steps (the stand-in engine sleeps 10 ms per step, so ms_per_step cannot be under 10), a plain
+    run carries none of the --full extras, and --dump-outputs writes the last timed step's float32 arrays; the same arguments give
+    the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("dump%d" % run)
+        out = _run_bench(["--gpus", "1", "--harness_stub", "--config", "tiny", "--steps", "5", "--warmup", "2", "--batch", "4",
+                          "--dump-outputs", str(d)])
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, out.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 5 and r["warmup"] == 2 and r["ms_per_step"] >= 10.0
+        assert r["config"]["shards"] == [[0, 0, 4 * (5 + 2)]]
+        for k in ("roofline", "strength1", "output_stage", "cpu_baseline"):
+            assert k not in r, k
+        assert sorted(os.listdir(d)) == ["images.npy", "latents.npy", "score.npy"]
+        arrs = {k: np.load(d / (k + ".npy")) for k in ("images", "latents", "score")}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert arrs["latents"].shape == (4, 4, 16, 16) and arrs["score"].shape == (1,)
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_bench_dump_samples_large_arrays(tmp_path):
+    """An output above DUMP_MAX_ELEMS is written as a fixed, seeded sample of that many of its values."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_MAX_ELEMS + 12345
+    img = torch.arange(n, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.ones(2, 4), img, torch.tensor(3.0))
+    a, b = np.load(tmp_path / "a" / "images_sample.npy"), np.load(tmp_path / "b" / "images_sample.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b)
+    assert (np.diff(a) > 0).all() and a[-1] < n                    # distinct sorted positions of the original array
+    assert sorted(os.listdir(tmp_path / "a")) == ["images_sample.npy", "latents.npy", "score.npy"]
+    assert np.load(tmp_path / "a" / "score.npy").tolist() == [3.0]
+
+
+def test_bench_refuses_zero_steps():
+    out = _run_bench(["--gpus", "1", "--harness_stub", "--config", "tiny", "--steps", "0"])
+    assert out.returncode != 0 and "--steps" in out.stderr and out.stdout.strip() == ""

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out/effclk
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/run -o p -- python3 $ROOT/bench.py --steps 1 --warmup 1 --no_cpu_baseline --no_profile $EFFCLK_ARGS > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/run -o p -- python3 $ROOT/bench.py --steps 1 --warmup 1 --full --no_cpu_baseline --no_profile $EFFCLK_ARGS > $OUT/bench.json 2> $OUT/bench.err
 cd $ROOT
 ls $OUT/run/* | head
 python3 - <<'PY'
