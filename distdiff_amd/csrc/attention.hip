@@ -99,11 +99,6 @@ __device__ __forceinline__ void load_row_frags(bf16x8* f, const bf16_t* g, bool 
 }
 
 constexpr float LOG2E = 1.4426950408889634f;
-#ifndef DD_ATTN_ABL
-// timing ablations (results wrong): 1 no exp, 2 no barriers, 4 no row max, 8 / 16 no global prefetch / LDS staging after tile 0 (register-
-// staged kernel), 32 no LDS fragment reads after tile 0, 64 no P.V MFMAs, 128 no DMA after tile 0 (LDS-DMA kernel)
-#define DD_ATTN_ABL 0
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // forward.  grid (ceil(Nq / QB), H, B), 256 threads. DSPLIT=1: each wave owns QT 16-query tiles;
@@ -114,9 +109,6 @@ constexpr float LOG2E = 1.4426950408889634f;
 // (tools/bench_attn_occ.py, same device: d = 40 forward 1612 -> 1527 us at 4 waves / 128 VGPRs with 7 spilled registers; d = 80
 // 397 -> 327 us at 3 waves / 168 VGPRs, its 77-key cross-attention 91 -> 82 us; NOT for d = 64 at 4 waves (48 spills: 1190 -> 1910 us),
 // d = 40 at 5 waves (3x slower) or the backward kernels at 3 waves (d = 40: 1620 -> 1680 us)).
-#ifndef DD_ATTN_SAFE_ONLY
-#define DD_ATTN_SAFE_ONLY 0      // 1: the lazy forward always takes the per-tile row maximum (A/B builds; results identical up to rounding)
-#endif
 #ifndef DD_AW_FWD
 #define DD_AW_FWD(D) ((D) <= 40 ? 4 : (D) <= 80 ? 3 : 1)
 #endif
@@ -183,17 +175,16 @@ __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams 
   // mask's compares and index arithmetic (as a run-time test the compiler hoisted them in front of the branch)
   auto tile = [&](auto partial_c, int k0) {
     constexpr bool partial = decltype(partial_c)::value;
-    if (!(DD_ATTN_ABL & 2)) __syncthreads();
-    if ((DD_ATTN_ABL & 16) && k0 > 0) {
-    } else if (PREFETCH) {
+    __syncthreads();
+    if (PREFETCH) {
       tile_store<KT, PREFETCH ? DPK : 32>(kreg, Ks, S, tid);
       tile_store<KT, PREFETCH ? DPK : 32>(vreg, Vs, S, tid);
     } else {
       stage_tile<KT, DPK>(Ks, S, kg + (size_t)k0 * p.ldk, p.ldk, p.Nk - k0, D, tid);
       stage_tile<KT, DPK, ONES>(Vs, S, vg + (size_t)k0 * p.ldv, p.ldv, p.Nk - k0, D, tid);
     }
-    if (!(DD_ATTN_ABL & 2)) __syncthreads();
-    if (PREFETCH && k0 + KT < p.Nk && !((DD_ATTN_ABL & 8) && k0 > 0)) {
+    __syncthreads();
+    if (PREFETCH && k0 + KT < p.Nk) {
       tile_load<KT, PREFETCH ? DPK : 32>(kreg, kg + (size_t)(k0 + KT) * p.ldk, p.ldk, p.Nk - k0 - KT, D, tid);
       tile_load<KT, PREFETCH ? DPK : 32, ONES>(vreg, vg + (size_t)(k0 + KT) * p.ldv, p.ldv, p.Nk - k0 - KT, D, tid);
     }
@@ -221,14 +212,12 @@ __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams 
             if (k0 + kt * 16 + 4 * g + r >= klim[qt]) st[qt][kt][r] = -INFINITY;
       }
       float mx = st[qt][0][0];
-      if (!(DD_ATTN_ABL & 4)) {
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[qt][kt][r]);
       mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      }
       const float mnew = fmaxf(mrun[qt], mx * sl2);           // running max in the scaled log2 domain (sl2 > 0)
       const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
       float ps = 0.f;
@@ -236,7 +225,7 @@ __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams 
       for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float e = (DD_ATTN_ABL & 1) ? __builtin_fmaf(st[qt][kt][r], sl2, -mnew) : __builtin_amdgcn_exp2f(__builtin_fmaf(st[qt][kt][r], sl2, -mnew));
+          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(st[qt][kt][r], sl2, -mnew));
           st[qt][kt][r] = e;
           if (!ONES) ps += e;
         }
@@ -425,8 +414,8 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
   auto tile = [&](auto first_c, auto partial_c, auto safe_c, int k0, int buf) {
     constexpr bool FIRST = decltype(first_c)::value, PARTIAL = decltype(partial_c)::value, SAFE = decltype(safe_c)::value;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this wave's pieces of the tile have landed ...
-    if (!(DD_ATTN_ABL & 2) || FIRST) __syncthreads();        // ... everybody's have, and nobody still reads the other buffer
-    if (!PARTIAL && k0 + KT < p.Nk && !((DD_ATTN_ABL & 128) && !FIRST)) issue_tile(k0 + KT, buf ^ 1);
+    __syncthreads();                                         // ... everybody's have, and nobody still reads the other buffer
+    if (!PARTIAL && k0 + KT < p.Nk) issue_tile(k0 + KT, buf ^ 1);
     const unsigned char* Ks = smem + buf * 2 * TILE;
     const unsigned char* Vs = Ks + TILE;
     if constexpr (FP8) {
@@ -448,7 +437,7 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
       for (int qt = 0; qt < QT; ++qt) st[qt][kt] = LZ ? negm[qt] : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        const bf16x8 kf = ((DD_ATTN_ABL & 32) && !FIRST) ? qf[0][ks] : lds_row_frag(Ks, kt * 16 + i16, S, g + 4 * ks);
+        const bf16x8 kf = lds_row_frag(Ks, kt * 16 + i16, S, g + 4 * ks);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) st[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][ks], st[qt][kt], 0, 0, 0);
       }
@@ -465,7 +454,7 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
             if (k0 + kt * 16 + 4 * g + r >= p.Nk) st[qt][kt][r] = -INFINITY;
       }
       float mx = st[qt][0][0];
-      if (!(DD_ATTN_ABL & 4) && (!LZ || FIRST || SAFE)) {
+      if (!LZ || FIRST || SAFE) {
         mx = vmax3(mx, st[qt][0][1], st[qt][0][2]);
         mx = vmax2(mx, st[qt][0][3]);
 #pragma unroll
@@ -518,7 +507,7 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
       for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float e = (DD_ATTN_ABL & 1) ? __builtin_fmaf(st[qt][kt][r], sl2, -mnew) : __builtin_amdgcn_exp2f(__builtin_fmaf(st[qt][kt][r], sl2, -mnew));
+          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(st[qt][kt][r], sl2, -mnew));
           st[qt][kt][r] = e;
           if (!ONES) ps += e;
         }
@@ -557,8 +546,7 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
     for (int dt = 0; dt < DVT; ++dt)
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
-        const bf16x8 vf = ((DD_ATTN_ABL & 32) && !FIRST) ? qf[0][0] : lds_col_frag(Vs, 32 * c, S, dt, lane);
-        if (DD_ATTN_ABL & 64) { if (dt == 0 && c == 0) o[0][0][0] += pf[0][0][0] + pf[QT - 1][NC - 1][3]; continue; }
+        const bf16x8 vf = lds_col_frag(Vs, 32 * c, S, dt, lane);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qt][c], o[qt][dt], 0, 0, 0);
       }
@@ -581,9 +569,8 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
     // away from its first tile's maximum by more than any trained attention does; the workgroup then repeats the sweep with the
     // per-tile maximum and the rebase (the decision is workgroup-uniform: the waves share the K/V ring and its barriers).
     constexpr float LZ_LIMIT = 1.8446744e19f;                // 2^64
-    constexpr bool safe_only = DD_ATTN_SAFE_ONLY || FP8;     // FP8: always the per-tile maximum (the probabilities are bounded by 2^LZ_SLACK)
-    bool bad = safe_only;
-    if (!safe_only) {
+    bool bad = FP8;                                          // FP8: always the per-tile maximum (the probabilities are bounded by 2^LZ_SLACK)
+    if (!FP8) {
       sweep(F_{});
 #pragma unroll
       for (int qt = 0; qt < QT; ++qt) {
@@ -977,17 +964,15 @@ hipError_t run_fwd_dma2(const AttnParams& p, hipStream_t s) {
 }
 template <int D, int QT, int KT, int NW>
 hipError_t run_fwd_dma(const AttnParams& p, hipStream_t s) {
-  static const int lazy = getenv("DD_ATTN_LAZY") ? atoi(getenv("DD_ATTN_LAZY")) : 0;
-  return (lazy || p.q_prescaled) ? run_fwd_dma2<D, QT, KT, NW, true>(p, s) : run_fwd_dma2<D, QT, KT, NW, false>(p, s);
+  return p.q_prescaled ? run_fwd_dma2<D, QT, KT, NW, true>(p, s) : run_fwd_dma2<D, QT, KT, NW, false>(p, s);
 }
 // the causal mask (CLIP text encoder, forward only) is a template flag: the UNet / VAE loops carry no per-score mask code
 template <int D, int QT, int KT, int DSPLIT>
 hipError_t run_fwd(const AttnParams& p, hipStream_t s) {
-  static const int dma = getenv("DD_ATTN_DMA") ? atoi(getenv("DD_ATTN_DMA")) : 1;
   // LDS-DMA staging: head dims whose rows are whole 16-byte granules, key / value row pitches within the 32-bit offset of one batch image
   if constexpr (DSPLIT == 1 && D % 8 == 0 && D <= 80 && (KT * AttnDmaGeo<D>::RG) % 64 == 0) {   // d = 160: the two-deep ring would cost a workgroup per CU
-    if (dma && !p.causal && (size_t)p.Nk * (size_t)(p.ldk > p.ldv ? p.ldk : p.ldv) * 2 < 0xF0000000ull) {
-      if constexpr (D <= 40) { if (dma != 4 && p.Nq % (8 * QT * 16) == 0) return run_fwd_dma<D, QT, KT, 8>(p, s); }   // DD_ATTN_DMA=4: four-wave workgroups everywhere
+    if (!p.causal && (size_t)p.Nk * (size_t)(p.ldk > p.ldv ? p.ldk : p.ldv) * 2 < 0xF0000000ull) {
+      if constexpr (D <= 40) { if (p.Nq % (8 * QT * 16) == 0) return run_fwd_dma<D, QT, KT, 8>(p, s); }
       return run_fwd_dma<D, QT, KT, 4>(p, s);
     }
   }
@@ -1028,38 +1013,18 @@ static bool attn_check(const AttnParams& p) {
   return !(p.ldq & 7) && !(p.ldk & 7) && !(p.ldv & 7) && !(p.ldo & 3) && p.Nq > 0 && p.Nk > 0;
 }
 
-static bool attn_short(const AttnParams& p) {
-  static const int on = getenv("DD_ATTN_SHORT") ? atoi(getenv("DD_ATTN_SHORT")) : 0;   // measured: 383.5 vs 376.0 ms of attention per bench step -- off
-  return on && !p.causal && p.Nk > 64 && p.Nk <= 96;
-}
-
 hipError_t launch_attention_fwd(const AttnParams& p, hipStream_t s) {
   if (!attn_check(p)) return hipErrorInvalidValue;
   if (attention_shortk_supported(p)) return launch_attention_fwd_shortk(p, s);     // <= 80 keys: K / V resident, per-wave query tiles
   switch (p.D) {
     case 32: return run_fwd<32, 2, 64, 1>(p, s);
-#ifndef DD_A40_QT
-#define DD_A40_QT 2
-#endif
-#ifndef DD_A40_KT
-#define DD_A40_KT 64
-#endif
-    // short key sequences (the 77-token prompt of the cross-attention): ONE 96-key tile instead of a full and a mostly masked 64-key tile
-    // (no key loop, one barrier), 16 queries per wave so that the 6 score tiles fit the register budget.  Built and measured SLOWER on the bench
-    // workload (the 16-query waves read the K / V tile twice as often per query): kept behind DD_ATTN_SHORT=1
-    case 40: if (attn_short(p)) return run_fwd<40, 1, 96, 1>(p, s); return run_fwd<40, DD_A40_QT, DD_A40_KT, 1>(p, s);
+    case 40: return run_fwd<40, 2, 64, 1>(p, s);
     case 64:
       // fp8 P.V (configs[4]): opt-in per launch, non-causal, key / value rows within the LDS-DMA offset range
       if (p.pv_fp8 && !p.causal && (size_t)p.Nk * (size_t)(p.ldk > p.ldv ? p.ldk : p.ldv) * 2 < 0xF0000000ull)
         return run_fwd_dma2<64, 2, 128, 8, true, true>(p, s);
-      {
-        // control for the fp8 A/B: the same 8-wave / 128-key tiling with the bf16 P.V (DD_ATTN_D64_WIDE=1, prescaled queries only)
-        static const int wide = getenv("DD_ATTN_D64_WIDE") ? atoi(getenv("DD_ATTN_D64_WIDE")) : 0;
-        if (wide && p.q_prescaled && !p.causal && (size_t)p.Nk * (size_t)(p.ldk > p.ldv ? p.ldk : p.ldv) * 2 < 0xF0000000ull)
-          return run_fwd_dma2<64, 2, 128, 8, true, false>(p, s);
-      }
       return run_fwd<64, 2, 64, 1>(p, s);
-    case 80: if (attn_short(p)) return run_fwd<80, 1, 96, 1>(p, s); return run_fwd<80, 2, 64, 1>(p, s);
+    case 80: return run_fwd<80, 2, 64, 1>(p, s);
     case 160: return run_fwd<160, 2, 64, 1>(p, s);
     case 512: return run_fwd<512, 4, 32, 4>(p, s);   // 64 queries per workgroup: K/V stream traffic per query / 4 (+50 %)
     default: return hipErrorInvalidValue;

@@ -186,8 +186,8 @@ size_t attention_gemm_workspace(int Nq, int Nk, int D, int bwd) {
 // images per launch: single-head layers only (with H > 1 the heads of one image interleave along the columns of the same rows, so the
 // images of a group do not stack along M), whole 256-row tiles per image, as many as the scratch holds
 static int group_size(const AttnParams& p, size_t workspace_bytes, int bwd) {
-  static const int gmax = getenv("DD_ATTN_GEMM_GROUP") ? atoi(getenv("DD_ATTN_GEMM_GROUP")) : 8;
-  if (p.H != 1 || (p.Nq & 255) || (p.Nk & 255) || gmax <= 1) return 1;
+  constexpr int gmax = 8;
+  if (p.H != 1 || (p.Nq & 255) || (p.Nk & 255)) return 1;
   const size_t per = attention_gemm_workspace(p.Nq, p.Nk, p.D, bwd);
   size_t g = workspace_bytes / per;
   if (g > (size_t)gmax) g = gmax;

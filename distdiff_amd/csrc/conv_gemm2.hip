@@ -740,12 +740,8 @@ hipError_t run_big(const ConvGemmParams& p, hipStream_t stream) {
   // (register allocation), which made the generic form the better one beyond ~100 K-steps per item.  With the bias staged through
   // LDS the batched form wins at every depth (same-device tools/ab_ops.sh, 32-image batch: limit 60 -> 1975 ms of conv, 100 -> 1949,
   // none -> 1936), so only split-K items (fp32 partial stores, no epilogue work) take the generic instantiation.
-  const int steps_per_item = (p.K / 64 + p.ksplit - 1) / p.ksplit;
-#ifndef DD_FE_LIMIT
-#define DD_FE_LIMIT 1000000
-#endif
   // split-K items only store fp32 partials (same code in both instantiations): take the faster loop
-  return (steps_per_item <= DD_FE_LIMIT && p.ksplit == 1) ? run_big_fe<WM, WN, TM, TN, NS, true>(p, stream) : run_big_fe<WM, WN, TM, TN, NS, false>(p, stream);
+  return p.ksplit == 1 ? run_big_fe<WM, WN, TM, TN, NS, true>(p, stream) : run_big_fe<WM, WN, TM, TN, NS, false>(p, stream);
 }
 
 }  // namespace
@@ -767,11 +763,10 @@ int conv_gemm_big_config(int M, int N, int K, int flags) {
   // Items of up to ~100 K-steps run as two independent 4-wave workgroups per CU (NS = 2, half the tile): one workgroup's epilogue
   // and pipeline refill overlap the other's MFMAs, which a single 8-wave workgroup in lock step cannot do.  Same-device A/B on
   // the bench workload (tools/ab_ops.sh): conv 1078 -> 1029 ms per step; deeper items and the big VAE shapes prefer the larger
-  // tile (arithmetic intensity).  DD_CONV_2WG / DD_CONV_2WG128 override the K-step limits (0 disables) for A/B runs.
-  static const int two_wg = getenv("DD_CONV_2WG") ? atoi(getenv("DD_CONV_2WG")) : 100;
-  if (two_wg > 0 && K / 64 <= two_wg && !geglu && N % 160 == 0) return 4;              // 128 x 160, 4 waves, 2 per CU
-  static const int two_wg128 = getenv("DD_CONV_2WG128") ? atoi(getenv("DD_CONV_2WG128")) : 24;
-  if (two_wg128 > 0 && K / 64 <= two_wg128 && N % 128 == 0 && (geglu || N % 160 != 0)) return 5;   // 128 x 128, 4 waves, 2 per CU
+  // tile (arithmetic intensity).
+  constexpr int two_wg = 100, two_wg128 = 24;                                           // K-step limits of the two forms
+  if (K / 64 <= two_wg && !geglu && N % 160 == 0) return 4;              // 128 x 160, 4 waves, 2 per CU
+  if (K / 64 <= two_wg128 && N % 128 == 0 && (geglu || N % 160 != 0)) return 5;   // 128 x 128, 4 waves, 2 per CU
   if (N <= 128) return 3;                          // 256 x 128
   if (!geglu && N % 160 == 0 && (N % 256 != 0 || N == 1280)) return 2;   // 256 x 160
   if (N % 256 == 0 || N >= 1024) return 1;         // 128 x 256
@@ -789,7 +784,7 @@ void conv_gemm_big_tile(int cfg, int* bm, int* bn) {
 
 hipError_t launch_conv_gemm_big(const ConvGemmParams& p, int cfg, hipStream_t stream) {
   switch (cfg) {
-    // three LDS stages + counted vmcnt + partner-wave stagger: +0..7 % over two stages in same-device A/B (tools/ab_conv.sh)
+    // three LDS stages + counted vmcnt + partner waves one phase apart: +0..7 % over two stages in same-device A/B (tools/ab_conv.sh)
     case 1: return run_big<2, 4, 4, 4, 3>(p, stream);    // 128 x 256, 8 waves
     case 2: return run_big<4, 2, 4, 5, 3>(p, stream);    // 256 x 160, 8 waves
     case 3: return run_big<4, 2, 4, 4, 3>(p, stream);    // 256 x 128, 8 waves

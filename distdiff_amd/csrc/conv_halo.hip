@@ -160,7 +160,7 @@ __device__ __forceinline__ void pp_epilogue(const ConvGemmParams& p, f32x4 (&acc
 // Tile geometry (host: halo_geometry): a tile is th x tw OUTPUT pixels of one image (th * tw = 256, tw = min(Wo, 128) a power of two),
 // i.e. 256 / Wo whole image rows for Wo <= 128 and a 2 x 128 block for wider images; its halo is (th + 2) x (tw + 2) LOGICAL input
 // pixels (the fused nearest-2x upsample of the decoder's / UNet's upsamplers reads stored pixel (iy >> shift, ix >> shift)).
-struct HaloGeo { int ltw, th, halo_px, tiles_x, tiles_y, ipt, stagger, tab; };   // tab: the one-tile kernel uses the LDS halo address table   // stagger (persistent form): start delay per phase, in 10 ns ticks   // ipt: images per tile (4 at 8 x 8: a tile is 4 whole images, each with its own 10 x 10 halo block)
+struct HaloGeo { int ltw, th, halo_px, tiles_x, tiles_y, ipt, tab; };   // tab: the one-tile kernel uses the LDS halo address table   // ipt: images per tile (4 at 8 x 8: a tile is 4 whole images, each with its own 10 x 10 halo block)
 
 // WN = 4: 256 x (64 TN) tiles, waves 2 (M) x 4 (N); WN = 2: 512 x (32 TN) tiles, waves 4 (M) x 2 (N) -- the narrow outputs of the decoder's
 // last level (N = 128).  Either way a wave owns 128 rows x TN * 16 columns and waves w, w + 4 (one SIMD) sit in different row groups.
@@ -177,7 +177,6 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const halo = smem + 2 * WB;
   float* const bias_s = (float*)(halo + ((halo_px + 7) & ~7) * 128);
-  float* const coef_s = bias_s + BN;                     // CF_GNFOLD: (a, b) of the chunk's 64 channels for this tile's image
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -233,9 +232,9 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
   const bf16_t* ximg = p.x + (size_t)img * p.H * p.W * p.x_ld;     // per-image base: 32-bit byte offsets only span one image
   // Halo address table (geo.tab; see 3.8.8 of DESIGN.md and conv_halo_persist_kernel): a workgroup of this kernel has ONE tile, so the byte
   // offset of every (piece, lane) of its halo -- out-of-image pixels as the out-of-range offset that reads zeros -- is the same for every
-  // chunk.  All 8 waves compute their pieces once, in the prologue, store them behind the bias / coef block and request chunk c_begin with
+  // chunk.  All 8 waves compute their pieces once, in the prologue, store them behind the bias block and request chunk c_begin with
   // them; the refills at the chunk boundaries (row group 0) are a table read + a request per piece.
-  unsigned* const htab = (unsigned*)(coef_s + 128);
+  unsigned* const htab = (unsigned*)(bias_s + BN);
   const bool use_tab = geo.tab != 0;
   auto halo_voff = [&](int pc) {
     const int hp = pc * 8 + prow;
@@ -274,36 +273,6 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
     for (int pc = wave; pc < npc; pc += 4) hdma16(ximg, halo + pc * 1024, halo_voff(pc), soff);
   };
 
-  // CF_GNFOLD: GroupNorm(+SiLU) applied to the staged halo chunk in place -- y = silu(x * a[c] + b[c]) on every pixel that lies inside
-  // the image (the zero padding stays zero) -- once per tile and chunk instead of a pass over the tensor in front of this convolution.
-  // The two row groups take alternate 256-vector slices; 16 bytes = 8 channels of one pixel per thread and step.
-  const bool gnf = (p.flags & CF_GNFOLD) != 0;
-  auto load_coef = [&](int chunk) {        // wave 0: 64 channels x (a, b)
-    if (wave == 0) *(float2*)(coef_s + lane * 2) = *(const float2*)(p.gn_coef + ((size_t)img * p.cin + chunk * 64 + lane) * 2);
-  };
-  auto apply_gn = [&](int g) {
-    const int nv = halo_px * 8;
-    for (int v = g * 256 + (tid & 255); v < nv; v += 512) {
-      const int hp = v >> 3, ps = v & 7;
-      const int hy = (int)(((float)hp + 0.5f) * inv_w2), hx = hp - hy * W2;
-      const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
-      if (iy < 0 || iy >= p.Ho || ix < 0 || ix >= p.Wo) continue;
-      const int j = ps ^ (hx & 7);
-      uint4* px = (uint4*)(halo + v * 16);
-      float xv[8];
-      unpack8(*px, xv);
-      const float4 c0 = *(const float4*)(coef_s + j * 16), c1 = *(const float4*)(coef_s + j * 16 + 4);
-      const float4 c2 = *(const float4*)(coef_s + j * 16 + 8), c3 = *(const float4*)(coef_s + j * 16 + 12);
-      const float ca[8] = {c0.x, c0.z, c1.x, c1.z, c2.x, c2.z, c3.x, c3.z}, cb[8] = {c0.y, c0.w, c1.y, c1.w, c2.y, c2.w, c3.y, c3.w};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float y = xv[e] * ca[e] + cb[e];
-        xv[e] = p.gn_silu ? silu_f(y) : y;
-      }
-      *px = pack8(xv);
-    }
-  };
-
   f32x4 acc[8][TN];
 #pragma unroll
   for (int a = 0; a < 8; ++a)
@@ -311,14 +280,12 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
     for (int b = 0; b < TN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- prologue
-  if (gnf) load_coef(c_begin);
   if (use_tab) first_halo(c_begin);
   else if (grp == 0) issue_halo(c_begin);
 #pragma unroll
   for (int i = 0; i < NWP; ++i) issue_w(0, i);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();                                      // also publishes bias_s / coef_s
-  if (gnf) { apply_gn(grp); __syncthreads(); }
+  __syncthreads();                                      // also publishes bias_s
   if (grp == 1) __builtin_amdgcn_s_barrier();           // the second group runs one barrier behind
 
   // Two sections per K-step, one per 32-deep K half: 8 x TN MFMAs between two barriers (the barrier hand-off between the SIMD partners is
@@ -333,22 +300,10 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
     if (c > c_begin) {
       // every read of the previous chunk's halo has retired (both groups waited lgkmcnt(0) in front of their last X barrier)
       if (grp == 0) {
-        if (gnf) load_coef(c);
-#ifndef DD_HALO_ABL       // timing ablation (-DDD_HALO_ABL: results wrong): the halo of chunk 0 serves every chunk -- what the refill at a chunk boundary costs
         issue_halo(c);
-#endif
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      } else if (gnf) {
-        // group 1 arrives here one barrier late, i.e. behind the barrier in front of which group 0 waited for the new halo: it applies
-        // its slice now, group 0 applies its own behind that same barrier, and the extra barrier below closes both
-        apply_gn(1);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
       __builtin_amdgcn_s_barrier();
-      if (gnf) {
-        if (grp == 0) { apply_gn(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-        __builtin_amdgcn_s_barrier();
-      }
     }
     for (int t = 0; t < 9; ++t, ++kt) {
       const int e = __builtin_amdgcn_readlane(v_taps, t);
@@ -449,7 +404,7 @@ __device__ unsigned long long g_pp_trace[8192 * 6];
 // CU (LDS) nothing overlaps them.  One workgroup per CU walks its tiles: behind the last K-step of a tile the halo buffer and the idle
 // weight stage are free, so the NEXT tile's first halo chunk, first weight stage and bias row are requested BEFORE this tile's epilogue
 // and land while it stores.  Same tile -> XCD map as the one-tile kernel (an XCD's workgroups share a contiguous tile range, n-tiles
-// fastest), same K loop, same epilogue; no CF_GNFOLD, N % BN == 0.  Results are bitwise those of conv_halo_kernel (same order of
+// fastest), same K loop, same epilogue; N % BN == 0.  Results are bitwise those of conv_halo_kernel (same order of
 // operations per tile).
 template <int TN, int WN>
 __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParams p, HaloGeo geo) {
@@ -479,13 +434,6 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
   }
   int t = blockIdx.x >> 3;
   if (t >= xc) return;
-  if (geo.stagger > 0) {
-    // de-phase the workgroups: launched together and walking tiles of identical cost they would refill their halos in the same
-    // microsecond, chip-wide, at the HBM rate (~11 B/clk per CU) instead of a CU's own (MI355X guide, "prologue HBM burst").  16 phases
-    // over the workgroups of an XCD; every wave of the workgroup waits the same time
-    const unsigned long long until = __builtin_amdgcn_s_memrealtime() + (unsigned long long)((blockIdx.x >> 3) & 15) * (unsigned)geo.stagger;
-    while (__builtin_amdgcn_s_memrealtime() < until) __builtin_amdgcn_s_sleep(4);
-  }
   const int chunks = p.cin >> 6, KT = chunks * 9;
   const int v_taps = lane < 9 ? p.taptab[lane] : 0;
   const int prow = lane >> 3, jw = (lane & 7) ^ prow;
@@ -576,10 +524,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
     for (int c = 0; c < chunks; ++c) {
       if (c > 0) {
         if (grp == 0) {
-#ifndef DD_PERSIST_ABL
-#define DD_PERSIST_ABL 0      // timing ablations (results wrong): 1 no refill at the chunk boundary; 2 the refill re-reads chunk 0 (cache-hot lines, same issue work)
-#endif
-          if (DD_PERSIST_ABL != 1) issue_halo(g, DD_PERSIST_ABL == 2 ? 0 : c, 4);
+          issue_halo(g, c, 4);
           asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         }
         __builtin_amdgcn_s_barrier();
@@ -637,10 +582,8 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
     const int mimg = g.img * p.Ho * p.Wo, y0 = g.y0, x0 = g.x0;
     auto m_of = [&](int r) { return mimg + (y0 + (r >> lw)) * p.Wo + x0 + (r & (Wd - 1)); };
     const float* bias_s = bias_base + (it & 1) * BN;
-#ifndef DD_PERSIST_LA
-#define DD_PERSIST_LA 2      // 4 measured 2-3 % SLOWER on every decoder shape (256 VGPRs + 10 spills; profiles/r06_decoder_persist.txt)
-#endif
-    pp_epilogue<TN, DD_PERSIST_LA>(p, acc, m_of, wr, wc, g.n0, bias_s, bias_s, 0, fr, fq);
+    // look-ahead 2: 4 measured 2-3 % SLOWER on every decoder shape (256 VGPRs + 10 spills; profiles/r06_decoder_persist.txt)
+    pp_epilogue<TN, 2>(p, acc, m_of, wr, wc, g.n0, bias_s, bias_s, 0, fr, fq);
     HP_STAMP(xs + t, 4);
     if (!have_next) break;
     g = gn; t = tn_;
@@ -856,29 +799,27 @@ bool halo_geometry(const ConvGemmParams& p, int bm, HaloGeo* g) {
   g->ipt = 1;
   if (Wo == 8 && Ho == 8 && bm == 256 && p.B % 4 == 0 && !p.shift) {
     // 8 x 8 level: a 256-pixel tile is four whole images, each with its own 10 x 10 halo block
-    g->ltw = 3; g->th = 8; g->halo_px = 4 * 100; g->tiles_x = 1; g->tiles_y = 1; g->ipt = 4; g->stagger = 0; g->tab = 0;
+    g->ltw = 3; g->th = 8; g->halo_px = 4 * 100; g->tiles_x = 1; g->tiles_y = 1; g->ipt = 4; g->tab = 0;
     return true;
   }
   if (Wo < 16 || (Wo & (Wo - 1))) return false;
   // wide images: 512-pixel tiles are 8 rows x 64 pixels (halo 10 x 66 = 660 pixels) rather than 4 x 128 (6 x 130 = 780): the halo refill
   // at every 64-channel chunk boundary is the largest exposed cost of the decoder's short K loops (tools/halo_trace.py: ~5 us of a
   // 14.6 us chunk), and it scales with the halo's bytes.  tw >= 64 keeps a CF_STATS block (64 consecutive output pixels) inside one row.
-  static const int tw512 = getenv("DD_HALO_TW512") ? atoi(getenv("DD_HALO_TW512")) : 64;
-  const int tw = Wo < 128 ? Wo : (bm == 512 ? tw512 : 128), th = bm / tw;
+  const int tw = Wo < 128 ? Wo : (bm == 512 ? 64 : 128), th = bm / tw;
   if (Ho % th) return false;
   int l = 0;
   while ((1 << l) < tw) ++l;
   g->ltw = l; g->th = th; g->halo_px = (th + 2) * (tw + 2); g->tiles_x = Wo / tw; g->tiles_y = Ho / th;
-  static const int stagger = getenv("DD_HALO_STAGGER") ? atoi(getenv("DD_HALO_STAGGER")) : 0;
-  g->stagger = stagger; g->tab = 0;
+  g->tab = 0;
   return true;
 }
 
 template <int TN, int WN, bool MI = false>
 hipError_t run_halo(const ConvGemmParams& p, const HaloGeo& g, hipStream_t stream) {
   constexpr int BM = (8 / WN) * 128, BN = WN * TN * 16;
-  int lds = 2 * BN * 128 + ((g.halo_px + 7) & ~7) * 128 + BN * 4 + 512 + 64;
-  // halo address table behind the bias / coef block when it fits
+  int lds = 2 * BN * 128 + ((g.halo_px + 7) & ~7) * 128 + BN * 4 + 64;
+  // halo address table behind the bias block when it fits
   static const int tab_on = getenv("DD_HALO_TAB") ? atoi(getenv("DD_HALO_TAB")) : 1;
   HaloGeo gg = g;
   const int tab_bytes = ((g.halo_px + 7) >> 3) * 256;
@@ -931,9 +872,8 @@ int conv_halo_config(const ConvGemmParams& p) {
   // narrow outputs (conv_out of the decoder / the UNet, N <= 4): a 512 x 32 form whose weight stage is 4 KB -- the input tile is read once
   // from HBM (halo) instead of being gathered tap by tap through the 128-wide tiles of the general kernels (60 of 64 columns wasted)
   static const int narrow_on = getenv("DD_HALO_NARROW") ? atoi(getenv("DD_HALO_NARROW")) : 1;
-  const bool narrow = narrow_on && p.N <= 4 && !(p.flags & ~(CF_BIAS | CF_OUT_F32 | CF_GNFOLD)) && !p.bias_sel && !p.shift && p.ksplit <= 1;
-  if (!narrow && ((p.flags & ~(CF_BIAS | CF_RES | CF_RELU | CF_STATS | CF_GNFOLD)) || p.bias_sel)) return 0;
-  if ((p.flags & CF_GNFOLD) && (!p.gn_coef || p.shift)) return 0;
+  const bool narrow = narrow_on && p.N <= 4 && !(p.flags & ~(CF_BIAS | CF_OUT_F32)) && !p.bias_sel && !p.shift && p.ksplit <= 1;
+  if (!narrow && ((p.flags & ~(CF_BIAS | CF_RES | CF_RELU | CF_STATS)) || p.bias_sel)) return 0;
   // tile forms by preference: 512 x 160 / 512 x 128 (the halo-resident input is cheap, the streamed weights are not: 20 / 16 KB of
   // weights + ~10 KB of halo per K-step instead of 40 / 32 + 5.6) where the image geometry allows 512-pixel tiles, else 256 x 320 / 256 x 256
   static const int tall = getenv("DD_HALO_TALL") ? atoi(getenv("DD_HALO_TALL")) : 1;
@@ -944,7 +884,7 @@ int conv_halo_config(const ConvGemmParams& p) {
     HaloGeo g;
     if (p.N == 4 && (p.flags & CF_OUT_F32) && (p.y_ld & 3)) return 0;             // float4 stores
     if (!halo_geometry(p, 512, &g) || p.M / 512 < 192) return 0;
-    if (2 * 32 * 128 + ((g.halo_px + 7) & ~7) * 128 + 32 * 4 + 512 + 64 > 163840) return 0;
+    if (2 * 32 * 128 + ((g.halo_px + 7) & ~7) * 128 + 32 * 4 + 64 > 163840) return 0;
     return 1;
   }
   if (conv_halo_split(p) > 1) return 5;                  // 8 x 8 level: 256 x 320 multi-image tiles + chunk split (fp32 partials)
@@ -958,7 +898,7 @@ int conv_halo_config(const ConvGemmParams& p) {
     HaloGeo g;
     if (!halo_geometry(p, bm, &g) || g.ipt > 1) continue;   // multi-image tiles (8 x 8) exist in the chunk-split form only (above)
     if ((p.M / bm) * (p.N / bn) < 192) continue;        // needs (most of) the chip: small grids keep the split-K forms
-    if (2 * bn * 128 + ((g.halo_px + 7) & ~7) * 128 + bn * 4 + 512 + 64 > 163840) continue;
+    if (2 * bn * 128 + ((g.halo_px + 7) & ~7) * 128 + bn * 4 + 64 > 163840) continue;
     return tn;
   }
   return 0;
@@ -968,7 +908,7 @@ int conv_halo_config(const ConvGemmParams& p) {
 int gemm_pp_config(const ConvGemmParams& p) {
   static const int on = getenv("DD_GEMM_PP") ? atoi(getenv("DD_GEMM_PP")) : 1;
   static const int geglu_on = getenv("DD_GEMM_PP_GEGLU") ? atoi(getenv("DD_GEMM_PP_GEGLU")) : 1;
-  static const int nmax = getenv("DD_GEMM_PP_NMAX") ? atoi(getenv("DD_GEMM_PP_NMAX")) : 3840;
+  constexpr int nmax = 3840;
   if (!on || p.force_small) return 0;
   if (p.ntaps != 1 || p.stride != 1 || p.shift || p.parity || p.H != p.Ho || p.W != p.Wo || (p.cin & 63) || p.K != p.cin) return 0;
   if ((p.M & 255) || p.K < 256 || p.ksplit > 1 || p.bias_sel || (p.x_ld & 7) || (p.y_ld & 7)) return 0;
@@ -1015,7 +955,7 @@ hipError_t launch_conv_halo(const ConvGemmParams& p, int tn, hipStream_t stream)
   // 512 x 128 tiles with a short K loop (the decoder's levels): the persistent form, next tile's first stage requested under the epilogue
   static const int persist = getenv("DD_HALO_PERSIST") ? atoi(getenv("DD_HALO_PERSIST")) : 1;
   // (address table: halo row < 31, column < 256, byte offsets inside the halo's stored rows below 8 MB)
-  if (tn == 2 && persist && g.ipt == 1 && !(p.flags & CF_GNFOLD) && p.N % 128 == 0 && (p.cin >> 6) <= persist * 8 &&
+  if (tn == 2 && persist && g.ipt == 1 && p.N % 128 == 0 && (p.cin >> 6) <= persist * 8 &&
       g.th + 2 < 31 && (1 << g.ltw) + 2 < 256 && (size_t)(g.th + 3) * p.W * p.x_ld * 2 < (8u << 20) &&
       2 * 128 * 128 + ((g.halo_px + 7) & ~7) * 128 + 2 * 128 * 4 + ((g.halo_px + 7) >> 3) * 256 + 64 <= 163840)
     return run_halo_persist<4, 2>(p, g, stream);

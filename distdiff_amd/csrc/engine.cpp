@@ -16,7 +16,7 @@ struct Run {
   dd_engine* E; hipStream_t s; int B;
   Ctx ctx(const Program& P, char* act) {
     Ctx c; c.act = act; c.grad = E->grad_slab; c.tr = E->tr_slab; c.tr_stride = P.tr_max; c.scratch_partial = E->scratch_partial; c.partial_cap = E->partial_cap;
-    c.scratch_tmp = E->scratch_tmp; c.tmp_cap = E->tmp_cap; c.tap1x1 = E->tap1x1; c.gn_scratch = E->gn_scratch; c.rowpart = E->rowpart; c.gn_coef = E->gn_coef; c.s = s; c.B = B; c.cross_kv = &E->cross_kv; c.flops = &E->flops; c.prof = &E->prof;
+    c.scratch_tmp = E->scratch_tmp; c.tmp_cap = E->tmp_cap; c.tap1x1 = E->tap1x1; c.gn_scratch = E->gn_scratch; c.rowpart = E->rowpart; c.s = s; c.B = B; c.cross_kv = &E->cross_kv; c.flops = &E->flops; c.prof = &E->prof;
     return c;
   }
 };
@@ -183,10 +183,6 @@ int dd_create(const dd_config* cfg, dd_engine** out) {
 
 void dd_destroy(dd_engine* e) {
   if (!e) return;
-  for (auto& kv : e->step_graphs) if (kv.second.exec) hipGraphExecDestroy(kv.second.exec);
-  if (e->gstream) hipStreamDestroy(e->gstream);
-  if (e->ev_in) hipEventDestroy(e->ev_in);
-  if (e->ev_out) hipEventDestroy(e->ev_out);
   for (void* p : e->dev_allocs) hipFree(p);
   delete e;
 }
@@ -309,7 +305,7 @@ int dd_finalize_weights(dd_engine* E) {
                                E->text.scratch_partial, E->text2.scratch_partial, (size_t)1 << 20});
     E->scratch_partial = (char*)E->dmalloc(E->partial_cap, false);
     E->tmp_cap = std::max({E->unet.scratch_tmp, E->vae.scratch_tmp, E->guide.scratch_tmp, E->venc.scratch_tmp, E->text.scratch_tmp, E->text2.scratch_tmp, (size_t)256});
-    if (!getenv("DD_ATTN_FLASH_ONLY")) {   // A/B switch: keep the flash kernels for wide heads too
+    {
       const int tap = (32 << 6) | 32;
       E->tap1x1 = (int*)E->dmalloc(sizeof(int), false);
       HIPCHK(hipMemcpy(E->tap1x1, &tap, sizeof(int), hipMemcpyHostToDevice));
@@ -318,13 +314,6 @@ int dd_finalize_weights(dd_engine* E) {
     const int maxG = std::max(c.unet_groups, c.vae_groups);
     E->gn_scratch = (float*)E->dmalloc(groupnorm_scratch_bytes(2 * B, maxG), false);
     E->rowpart = (float*)E->dmalloc(std::max(E->unet.scratch_rowpart, (size_t)256), false);
-    {   // GroupNorm affine of the op that ran last (CF_GNFOLD): [images][channels][2] of the widest GroupNorm input
-      size_t n = 256;
-      for (const Program* P : {&E->unet, &E->vae, &E->venc})
-        for (const Op& o : P->ops)
-          if (o.kind == OP_GN) n = std::max(n, (size_t)P->t[o.x].B * P->t[o.x].C * 8);
-      E->gn_coef = (float*)E->dmalloc(n, false);
-    }
     for (auto& f : E->f32_tmp) f = (float*)E->dmalloc(zbytes);
     E->img_tmp = (float*)E->dmalloc((size_t)B * 3 * 64 * L * L * 4);
     E->score_tmp = (float*)E->dmalloc(256);
@@ -508,55 +497,7 @@ int dd_denoise_step(dd_engine* E, const float* z, int step_index, float* z_prev_
   DD_TRY(E, {
     check_batch(E, B);
     if (step_index < 0 || step_index >= (int)E->timesteps.size()) throw std::runtime_error("step_index out of range");
-    hipStream_t s = (hipStream_t)stream;
-    // Opt-in (DD_GRAPH=1): measured on MI355X the replay does not pay -- B = 16: 1485 vs 1481 ms per batch, B = 1: 313 vs 302 ms
-    // (DESIGN.md section 6): even at B = 1 the ~6300 launches of an image are GPU-bound small kernels, not launch-bound.
-    static const bool use_graph = getenv("DD_GRAPH") != nullptr && atoi(getenv("DD_GRAPH")) != 0;
-    if (!use_graph || !E->graphs_ok || E->prof.on) { denoise_step_enqueue(E, z, step_index, z_prev_out, x0_out, s); return DD_OK; }
-    // first sighting of a (step, buffers) key: plain launches (also runs every one-time hipFuncSetAttribute); second: capture on the
-    // engine's own stream (the caller's may be the legacy default stream, which cannot be captured) and instantiate; then replay
-    char key[96];
-    snprintf(key, sizeof key, "%d/%p/%p/%p", step_index, (const void*)z, (void*)z_prev_out, (void*)x0_out);
-    auto it = E->step_graphs.find(key);
-    if (it == E->step_graphs.end()) {
-      if (E->step_graphs.size() >= 256) { denoise_step_enqueue(E, z, step_index, z_prev_out, x0_out, s); return DD_OK; }
-      dd_engine::StepGraph g;
-      const double f0 = E->flops;
-      denoise_step_enqueue(E, z, step_index, z_prev_out, x0_out, s);
-      g.flops = E->flops - f0; g.seen = 1;
-      E->step_graphs[key] = g;
-      return DD_OK;
-    }
-    dd_engine::StepGraph& g = it->second;
-    if (!E->gstream) {
-      HIPCHK(hipStreamCreateWithFlags(&E->gstream, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&E->ev_in, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&E->ev_out, hipEventDisableTiming));
-    }
-    HIPCHK(hipEventRecord(E->ev_in, s));
-    HIPCHK(hipStreamWaitEvent(E->gstream, E->ev_in, 0));
-    if (!g.exec) {
-      hipGraph_t graph = nullptr;
-      const double f0 = E->flops;
-      bool ok = hipStreamBeginCapture(E->gstream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-      if (ok) {
-        try { denoise_step_enqueue(E, z, step_index, z_prev_out, x0_out, E->gstream); } catch (...) { ok = false; }
-        ok = (hipStreamEndCapture(E->gstream, &graph) == hipSuccess) && ok && graph;
-      }
-      E->flops = f0;
-      if (ok) ok = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) == hipSuccess;
-      if (graph) hipGraphDestroy(graph);
-      if (!ok) {   // capture is an optimisation only: fall back to plain launches for good
-        (void)hipGetLastError();
-        g.exec = nullptr; E->graphs_ok = false;
-        denoise_step_enqueue(E, z, step_index, z_prev_out, x0_out, s);
-        return DD_OK;
-      }
-    }
-    HIPCHK(hipGraphLaunch(g.exec, E->gstream));
-    E->flops += g.flops;
-    HIPCHK(hipEventRecord(E->ev_out, E->gstream));
-    HIPCHK(hipStreamWaitEvent(s, E->ev_out, 0));
+    denoise_step_enqueue(E, z, step_index, z_prev_out, x0_out, (hipStream_t)stream);
   });
 }
 

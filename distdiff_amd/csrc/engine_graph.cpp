@@ -363,25 +363,6 @@ void plan_gn_stats(Program& P) {
   check_transients(P);
   P.emitted.assign(P.ops.size(), 0);
   P.row_spans.assign(P.ops.size(), 0);
-  P.gn_folded.assign(P.ops.size(), 0);
-  // GroupNorm -> 3x3 convolution pairs (ResnetBlock2D: norm1 -> conv1, norm2 -> conv2; conv_norm_out -> conv_out): candidates for
-  // CF_GNFOLD.  The GroupNorm's output is a transient read by that convolution only (check_transients), so nothing else needs it.
-  // Built, bit-identical to the separate kernels (tests/test_kernels_gpu.py::test_groupnorm_applied_by_the_halo_convolution) and
-  // OFF by default: the apply runs once per tile, 64-channel chunk and n-tile while the matrix pipe waits (norm family 206 -> 155 ms,
-  // conv family 1615 -> 1673 ms per 32-image step, same device, tools/ab_gn.sh): DD_GN_APPLY_FUSION=1 switches it on.
-  // DD_GN_NARROW_FUSION=1: only conv_norm_out -> conv_out (N <= 4, conv_halo_kernel<1, 2>).  Measured on the bench step, same box:
-  // conv_out on the narrow halo form 2098 -> 2089 ms per step; with its GroupNorm folded in as well 2095 ms (norm -3.5 ms, conv +8 ms:
-  // that form is bound by its exposed halo refill and the apply in LDS lengthens exactly that) -- off as well.
-  const bool fold_all = getenv("DD_GN_APPLY_FUSION") && atoi(getenv("DD_GN_APPLY_FUSION"));
-  const bool fold_narrow = getenv("DD_GN_NARROW_FUSION") && atoi(getenv("DD_GN_NARROW_FUSION"));
-  if (!P.f32 && (fold_all || fold_narrow))
-    for (size_t gi = 0; gi + 1 < P.ops.size(); ++gi) {
-      Op& g = P.ops[gi]; Op& cv = P.ops[gi + 1];
-      if (g.kind != OP_GN || cv.kind != OP_CONV || cv.x != g.y || cv.x_fwd >= 0 || !P.t[g.y].transient) continue;
-      if (cv.cw->KH != 3 || cv.cw->KW != 3 || cv.stride != 1 || cv.up || cv.cw->f32 || cv.cw->geglu) continue;
-      if (!fold_all && cv.cw->Cout > 4) continue;
-      g.gn_into = (int)gi + 1; cv.gn_from = (int)gi;
-    }
   if (P.f32 || getenv("DD_NO_GN_FUSION")) return;
   std::unordered_map<int, size_t> root_part;
   for (size_t gi = 0; gi < P.ops.size(); ++gi) {
@@ -460,20 +441,19 @@ int build_transformer(Builder& b, const std::string& p, int x, int heads, int G,
     // the three LayerNorms of a block are folded into the linear each of them feeds (Builder::fold_ln; DD_NO_LN_FOLD=1 builds the plain graph)
     const bool fold = ln_fold_enabled();
     // the softmax scale 1/sqrt(d) * log2(e) lives in the to_q rows: the attention forward exponentiates the MFMA results as they are
-    const int qs = attn_prescale() ? 1 : 0;
-    const float qscale = qs ? 1.4426950408889634f / sqrtf((float)(C / heads)) : 1.f;
+    const float qscale = 1.4426950408889634f / sqrtf((float)(C / heads));
     int n = b.ln(h, make_norm(E, m, t + ".norm1"), 1e-5f);
     int qkv = b.conv(n, make_conv_cat(E, m, {t + ".attn1.to_q", t + ".attn1.to_k", t + ".attn1.to_v"}, false, fold ? t + ".norm1" : "",
-                                      qs ? C : 0, qscale));
+                                      C, qscale));
     if (fold) b.fold_ln();
     int q = P.view(qkv, 0, C), k = P.view(qkv, C, C), v = P.view(qkv, 2 * C, C);
     const int fp8 = E->cfg.unet_attn_fp8 && C / heads == 64;      // BASELINE configs[4]: fp8 P.V for the d = 64 heads (SDXL)
-    int a = b.attn(q, k, v, heads, HW, HW, -1, 0, qs);
+    int a = b.attn(q, k, v, heads, HW, HW, -1, 0, 1);
     P.ops.back().pv_fp8 = fp8;
     h = b.conv(a, make_conv(E, m, t + ".attn1.to_out.0", 0), 1, 0, h);
     // cross attention: K,V of the text embeddings are computed once per prompt (dd_set_prompt)
     n = b.ln(h, make_norm(E, m, t + ".norm2"), 1e-5f);
-    int q2 = b.conv(n, make_conv(E, m, t + ".attn2.to_q", 0, false, false, fold ? t + ".norm2" : "", qs ? C : 0, qscale));
+    int q2 = b.conv(n, make_conv(E, m, t + ".attn2.to_q", 0, false, false, fold ? t + ".norm2" : "", C, qscale));
     if (fold) b.fold_ln();
     if (P.t[q2].B == E->cfg.max_batch && b.full_batch == 2 * E->cfg.max_batch) {
       // Up to here the unconditional and the conditional half of the CFG batch were the SAME computation (same latents, same timestep;
@@ -487,7 +467,7 @@ int build_transformer(Builder& b, const std::string& p, int x, int heads, int G,
     slot.wv = make_conv(E, m, t + ".attn2.to_v", 0, false, false);
     slot.C = C;
     E->cross_slots.push_back(slot);
-    a = b.attn(q2, -1, -1, heads, HW, E->cfg.text_len, (int)E->cross_slots.size() - 1, 0, qs);
+    a = b.attn(q2, -1, -1, heads, HW, E->cfg.text_len, (int)E->cross_slots.size() - 1, 0, 1);
     P.ops.back().pv_fp8 = fp8;
     h = b.conv(a, make_conv(E, m, t + ".attn2.to_out.0", 0), 1, 0, h);
     // GEGLU feed-forward

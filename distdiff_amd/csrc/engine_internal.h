@@ -103,7 +103,7 @@ struct Op {
   int heads = 0, D = 0, Nq = 0, Nk = 0, cross_slot = -1;
   int causal = 0, act_kind = 0;
   int pv_fp8 = 0;              // OP_ATTN: P.V on the fp8 MFMA (dd_config.unet_attn_fp8; d = 64 heads of the UNet only)
-  int q_prescaled = 0;         // OP_ATTN: the to_q weights carry 1/sqrt(D) * log2(e) (attn_prescale(); the kernels then get scale = ln 2)
+  int q_prescaled = 0;         // OP_ATTN: the to_q weights carry 1/sqrt(D) * log2(e) (the UNet's transformer blocks; the kernels then get scale = ln 2)
   int patch = 0, sel_stride = 0;   // OP_PATCHIFY: patch size; OP_SELECT: row stride (tokens per image)
   size_t stats_off = 0;  // fp32 stats / lse in the activation slab
   bool fused = false;    // OP_CONCAT: both operands live inside the output buffer (column views): no copy, forward or backward
@@ -119,9 +119,6 @@ struct Op {
   // and the OP_CONV reads the LayerNorm's INPUT (x_fwd) with CF_LNFOLD; the backward plan is untouched (x stays the LayerNorm output)
   bool ln_fold = false; int x_fwd = -1; size_t ln_stats_off = 0;
   int rowstat_from = -1; bool rowstat_emit = false; int rowstat_ld = 0;
-  // GroupNorm(+SiLU) applied by the 3x3 convolution that follows (plan_gn_fold; decided per run, CF_GNFOLD): OP_GN.gn_into = that
-  // convolution's op index, OP_CONV.gn_from = the GroupNorm's
-  int gn_into = -1, gn_from = -1;
   double flops = 0;
 };
 
@@ -133,7 +130,6 @@ struct Program {
   bool want_grad = false;
   bool f32 = false;      // every activation AND gradient of this program is fp32 (the guide network, guide_f32.hip)
   mutable std::vector<char> emitted;   // per op, per forward run: this convolution did emit its GroupNorm partials
-  mutable std::vector<char> gn_folded; // per op, per forward run: this GroupNorm only produced its affine, the next convolution applies it
   mutable std::vector<int> row_spans;  // per op, per forward run: column spans of the LayerNorm row partials this GEMM emitted (0 = none)
   size_t scratch_rowpart = 0;          // bytes of the shared row-partial buffer (producer GEMM -> LayerNorm statistics, adjacent ops)
   size_t tr_max = 0;     // bytes of one transient ping-pong buffer
@@ -209,7 +205,6 @@ struct Ctx {  // per-call execution context
   char* scratch_tmp = nullptr;
   float* gn_scratch = nullptr;
   float* rowpart = nullptr;      // LayerNorm row partials of the GEMM that ran last (CF_ROWSTATS)
-  float* gn_coef = nullptr;      // GroupNorm affine [B][C][2] of the op that ran last (CF_GNFOLD)
   const int* tap1x1 = nullptr;   // device int: the 1x1 tap, for GEMMs issued outside a ConvW (wide-head attention)
   size_t tmp_cap = 0;
   int step_index = 0;
@@ -289,7 +284,6 @@ struct dd_engine {
   char* scratch_tmp = nullptr; size_t tmp_cap = 0;
   float* gn_scratch = nullptr;
   float* rowpart = nullptr;
-  float* gn_coef = nullptr;
   int* tap1x1 = nullptr;
   float* f32_tmp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [B,4,L,L] fp32 temporaries
   float* img_tmp = nullptr;    // [B,3,8L,8L] fp32
@@ -300,12 +294,6 @@ struct dd_engine {
   size_t total_bytes = 0;
   double flops = 0;
   Profiler prof;
-  // hipGraph replay of the plain denoise step (~700 launches): one captured graph per (timestep index, latent buffers); the bias
-  // tables / DDIM coefficients of a step and every workspace pointer are static, so a step is the same launch sequence every time
-  struct StepGraph { hipGraphExec_t exec = nullptr; double flops = 0; int seen = 0; };
-  std::unordered_map<std::string, StepGraph> step_graphs;
-  hipStream_t gstream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
-  bool graphs_ok = true;
 
   void dfree(void* p) {
     if (!p) return;
@@ -359,7 +347,7 @@ namespace ddi {
 // engine_weights.cpp
 ConvW* make_conv_f32(dd_engine* E, const float* w, const float* bias, int Cout, int Cin, int KH, int KW, int pad, int groups, bool need_bwd);
 // qrows / qscale: output rows [0, qrows) (weights and bias, forward and input-gradient packings) are multiplied by qscale before the bf16
-// rounding -- the attention query projection carrying 1/sqrt(D) * log2(e) (attn_prescale)
+// rounding -- the attention query projection carrying 1/sqrt(D) * log2(e) (the UNet's transformer blocks)
 ConvW* make_conv_raw(dd_engine* E, const float* w, const float* bias, bool has_bias, int Cout, int Cin, int KH, int KW, int pad, bool geglu,
                      bool need_bwd, bool fold = false, const float* ln_gamma = nullptr, const float* ln_beta = nullptr, int qrows = 0,
                      float qscale = 1.f);
@@ -367,7 +355,6 @@ ConvW* make_conv(dd_engine* E, const std::string& model, const std::string& pref
                  const std::string& ln = "", int qrows = 0, float qscale = 1.f);
 ConvW* make_conv_cat(dd_engine* E, const std::string& model, const std::vector<std::string>& prefixes, bool with_bias, const std::string& ln = "",
                      int qrows = 0, float qscale = 1.f);
-bool attn_prescale();       // fold the softmax scale into the to_q weights of the UNet's transformer blocks (DD_ATTN_PRESCALE=0: off)
 ConvW* make_conv_bn(dd_engine* E, const std::string& model, const std::string& conv, const std::string& bn, int pad, float eps, int cin_total);
 NormW* make_norm(dd_engine* E, const std::string& model, const std::string& prefix);
 bool ln_fold_enabled();

@@ -103,7 +103,6 @@ ConvW* make_conv_raw(dd_engine* E, const float* w_in, const float* bias_in, bool
 }
 
 bool ln_fold_enabled() { static const bool on = !getenv("DD_NO_LN_FOLD"); return on; }
-bool attn_prescale() { static const bool on = !(getenv("DD_ATTN_PRESCALE") && atoi(getenv("DD_ATTN_PRESCALE")) == 0); return on; }
 
 // ln: prefix of the LayerNorm to fold into this linear ("" = none)
 ConvW* make_conv(dd_engine* E, const std::string& model, const std::string& prefix, int pad, bool geglu, bool has_bias, const std::string& ln,

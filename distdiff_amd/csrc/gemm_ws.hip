@@ -22,7 +22,7 @@
 // drain the LDS-DMA queue.  The way in is an LDS destination (LDS-DMA of the residual tile, 30 KB), not built.
 // History: commit 7d952d8 is the first form (K split over the two waves of a SIMD, fp32 partial hand-off through LDS, a barrier per
 // 16-row step): parity green, slower than the ping-pong GEMM -- the finishing wave's epilogue serialised behind its own MFMAs.
-// tools/ws_trace.py (-DWS_TRACE stamps) and the WS_ABL ablations are what the current form was derived from (profiles/r05_ws_*.txt).
+// tools/ws_trace.py (-DWS_TRACE stamps) and timing ablations are what the current form was derived from (profiles/r05_ws_*.txt).
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
@@ -59,13 +59,6 @@ __device__ unsigned long long g_ws_trace[8 * 16 * 10];
 #endif
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#ifndef WS_VAR
-#define WS_VAR 1      // A/B switches of this file: 1 hand-built fragment addresses (374 -> 341 vector instructions per GEGLU tile and wave, 235 -> 182 VGPRs;
-                      // isolated 581 -> 577 us: kept for the registers), 2 / 4 s_setprio 1 for waves 4 .. 7 / 0 .. 3 (no gain: profiles/r06_ws_variants.txt)
-#endif
-#ifndef WS_ABL
-#define WS_ABL 0      // timing ablations (results wrong): 1 no DMA behind the first two tiles, 2 no epilogue arithmetic, 4 no MFMAs, 8 no fragment reads, 16 no stores, 32 no barrier
-#endif
 constexpr int WS_RT = 64;                 // rows per tile
 constexpr int WS_KC = 10;                 // 32-deep K chunks (K = 320)
 constexpr int WS_TILE_B = WS_RT * 640;    // bytes of one activation tile in LDS: 5 blocks of [64 rows][128 B]
@@ -139,38 +132,24 @@ __device__ __forceinline__ void ws_wave(const ConvGemmParams& p, unsigned char* 
   // The sched_barrier lets VALU / SALU / MFMA cross (so the previous epilogue still interleaves with the next MFMAs) but no LDS or
   // memory instruction: left to itself the scheduler sinks each ds_read to just in front of its MFMA and every K chunk pays the LDS latency.
   bf16x8 xf[WS_KC];
-#if WS_VAR & 1
   // the swizzle term depends on the lane only (row & 7 == fr & 7 for every 16-row step): two lane bases (even / odd K chunk), everything
   // else -- step, 64-channel block -- is an immediate offset of the ds_read (the compiler otherwise keeps ~12 address registers and
-  // spends two integer instructions per fragment read on them)
+  // spends two integer instructions per fragment read on them: 374 -> 341 vector instructions per GEGLU tile and wave, 235 -> 182 VGPRs)
   const unsigned xfe = (unsigned)(fr * 128 + ((fq ^ (fr & 7)) << 4)), xfo = (unsigned)(fr * 128 + (((4 + fq) ^ (fr & 7)) << 4));
-#endif
   auto load_xf = [&](int slot, int a) {
-    const int row = a * 16 + fr;
-#if WS_VAR & 1
     typedef const __attribute__((address_space(3))) unsigned char* lds_cp;
     unsigned be = lds0 + (unsigned)slot * WS_TILE_B + xfe, bo = lds0 + (unsigned)slot * WS_TILE_B + xfo;
     asm volatile("" : "+v"(be), "+v"(bo));              // opaque: no strength reduction into a register per (step, parity)
     const lds_cp Ae = (lds_cp)(unsigned long long)be, Ao = (lds_cp)(unsigned long long)bo;
 #pragma unroll
     for (int kc = 0; kc < WS_KC; ++kc) xf[kc] = *(const __attribute__((address_space(3))) bf16x8*)(((kc & 1) ? Ao : Ae) + a * 2048 + (kc >> 1) * 8192);
-#else
-    const unsigned char* At = smem + slot * WS_TILE_B + row * 128;
-#pragma unroll
-    for (int kc = 0; kc < WS_KC; ++kc) {
-      if (WS_ABL & 8) { if (slot == 0 && a == 0) xf[kc] = *(const bf16x8*)(At + kc * 16); continue; }
-      xf[kc] = *(const bf16x8*)(At + (kc >> 1) * 8192 + ((((kc & 1) * 4 + fq) ^ (row & 7)) << 4));
-    }
-#endif
     __builtin_amdgcn_sched_barrier(0x000F);
   };
   load_xf(0, 0);
-  if ((WS_VAR & 2) && HS) __builtin_amdgcn_s_setprio(1);      // the younger half loses every arbitration otherwise (MI355X guide, "Two waves per SIMD" item 4)
-  if ((WS_VAR & 4) && !HS) __builtin_amdgcn_s_setprio(1);
   for (int it = 0; it < count; ++it, tile += tstep) {
     const int slot = it % WS_SLOTS;
     const int m0 = tile * WS_RT;
-    const bool dma = it + 2 < count && !(WS_ABL & 1);
+    const bool dma = it + 2 < count;
     WS_STAMP(it, 0);
     // the slot of tile it + 2 held tile it - 1: every wave passed the barrier behind that tile's last MFMAs
     if (dma) issue_tile(tile + 2 * tstep, (it + 2) % WS_SLOTS);
@@ -192,7 +171,7 @@ __device__ __forceinline__ void ws_wave(const ConvGemmParams& p, unsigned char* 
           if (dma) wait_vm<NY + ND>(); else wait_vm<NY>();
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (!(WS_ABL & 32)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
       }
       const float2 lc = lcs[a];
       f32x4 acc[NTW];
@@ -202,7 +181,6 @@ __device__ __forceinline__ void ws_wave(const ConvGemmParams& p, unsigned char* 
       for (int kc = 0; kc < WS_KC; ++kc)
 #pragma unroll
         for (int jn = 0; jn < NTW; ++jn) {
-          if (WS_ABL & 4) { if (kc == 0) { acc[jn][0] = (float)xf[jn][0]; acc[jn][1] = (float)wreg[jn][a][0]; } continue; }
           acc[jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[jn][kc], xf[kc], acc[jn], 0, 0, 0);
         }
       if (a < 3) {
@@ -220,7 +198,7 @@ __device__ __forceinline__ void ws_wave(const ConvGemmParams& p, unsigned char* 
             if (dma) wait_vm<NY + ND>(); else wait_vm<NY>();
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          if (!(WS_ABL & 32)) __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_s_barrier();
         }
         load_xf((it + 1) % WS_SLOTS, 0);
       }
@@ -243,7 +221,7 @@ __device__ __forceinline__ void ws_wave(const ConvGemmParams& p, unsigned char* 
         }
         float o[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (WS_ABL & 2) ? h[e] + g[e] : h[e] * gelu_f(g[e]);
+        for (int e = 0; e < 4; ++e) o[e] = h[e] * gelu_f(g[e]);
         *(uint2*)((bf16_t*)p.y + (size_t)m * p.y_ld + ((n0 + colw) >> 1) + fq * 4) = make_uint2(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]));
       } else {
         bf16_t* yp = (bf16_t*)p.y + (size_t)m * p.y_ld + n0 + colw;
@@ -329,7 +307,7 @@ hipError_t run_ws(const ConvGemmParams& p, hipStream_t stream) {
 // weight-stationary GEMM for K = 320 pointwise layers: 0 = not eligible, 5: 320-column blocks, 4: 256-column blocks (GEGLU)
 int gemm_ws_config(const ConvGemmParams& p) {
   static const int on = getenv("DD_GEMM_WS") ? atoi(getenv("DD_GEMM_WS")) : 1;
-  static const int mmin = getenv("DD_GEMM_WS_MMIN") ? atoi(getenv("DD_GEMM_WS_MMIN")) : 32768;
+  constexpr int mmin = 32768;
   static const int mask = getenv("DD_GEMM_WS_MASK") ? atoi(getenv("DD_GEMM_WS_MASK")) : 15;   // diagnostics: 1 GEGLU, 2 row statistics, 4 LayerNorm-folded, 8 the rest
   if (!on || p.force_small) return 0;
   if (!(mask & ((p.flags & CF_GEGLU) ? 1 : (p.flags & CF_ROWSTATS) ? 2 : (p.flags & CF_LNFOLD) ? 4 : 8))) return 0;

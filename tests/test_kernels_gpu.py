@@ -211,43 +211,6 @@ def test_conv_general_staging_path_beyond_4gb(ops):
         assert_close(got, ref, what="general path, image %d" % b)
 
 
-@pytest.mark.parametrize("case", [("gnfold_320_32x32", 48, 320, 320, 32, 32, 32, True), ("gnfold_256_64x64_res", 12, 128, 256, 64, 64, 32, True),
-                                  ("gnfold_n128_nosilu", 1, 64, 128, 256, 512, 32, False),
-                                  ("gnfold_conv_out_128to3_512px", 1, 128, 3, 512, 512, 32, True), ("gnfold_conv_out_320to4_64px", 32, 320, 4, 64, 64, 32, True)],
-                         ids=lambda c: c[0])
-def test_groupnorm_applied_by_the_halo_convolution(ops, case):
-    """CF_GNFOLD: GroupNorm(+SiLU) -> 3x3 convolution (ResnetBlock2D norm1 -> conv1, norm2 -> conv2) with the normalisation applied to
-    the convolution's staged input tile instead of a pass over the tensor: same result as GroupNorm -> conv through the separate
-    kernels (the affine, SiLU and bf16 rounding are the same arithmetic) and as torch on the same bf16 inputs."""
-    name, B, Cin, Cout, H, W, G, silu = case
-    g = torch.Generator().manual_seed(len(name))
-    x = bf(torch.randn(B, Cin, H, W, generator=g) * 1.5 + 0.4)
-    gamma, beta = 1.0 + 0.2 * torch.randn(Cin, generator=g), 0.3 * torch.randn(Cin, generator=g)
-    w = bf(torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(Cin * 9))
-    bias = torch.randn(Cout, generator=g)
-    hn = F.group_norm(x, G, gamma, beta, 1e-5)
-    ref = F.conv2d(bf(F.silu(hn) if silu else hn), w, bias, padding=1)
-    xd = ops.to_nhwc_bf16(x, Cin).cuda()
-    pk = ops.PackedConv(w, 1, mode=0, bias=bias)
-    coef, stats = ops.groupnorm_coef(xd, gamma.cuda(), beta.cuda(), B, H * W, G, 1e-5)
-    yn, _ = ops.groupnorm(xd, gamma.cuda(), beta.cuda(), B, H * W, G, 1e-5, silu)
-    if Cout <= 4:      # conv_norm_out -> conv_out as the engine runs it: fp32 output into 8-wide rows, the narrow form of the halo kernel
-        y = torch.zeros((B * H * W, 8), dtype=torch.float32, device="cuda")
-        ops.conv_gemm(xd, pk, B, H, W, H, W, y=y[:, :Cout], out_f32=True, gn_coef=coef, gn_silu=silu, ksplit=1)
-        y2 = torch.zeros((B * H * W, 8), dtype=torch.float32, device="cuda")
-        ops.conv_gemm(yn, pk, B, H, W, H, W, y=y2[:, :Cout], out_f32=True, ksplit=1)
-        torch.cuda.synchronize()
-        assert_close(ops.from_nhwc(y[:, :Cout], B, H, W), ref, rtol=5e-3, atol=2e-3, what=name + " vs torch")
-        assert torch.equal(y.cpu(), y2.cpu()), "folded and separate GroupNorm -> conv differ bitwise"
-        return
-    y = ops.conv_gemm(xd, pk, B, H, W, H, W, gn_coef=coef, gn_silu=silu)
-    torch.cuda.synchronize()
-    assert_close(ops.from_nhwc(y, B, H, W), ref, what=name + " vs torch")
-    y2 = ops.conv_gemm(yn, pk, B, H, W, H, W)
-    torch.cuda.synchronize()
-    assert torch.equal(y.cpu(), y2.cpu()), "folded and separate GroupNorm -> conv differ bitwise"
-
-
 def test_linear_epilogues(ops):
     g = torch.Generator().manual_seed(3)
     M, K, N = 300, 320, 640
@@ -990,11 +953,10 @@ def test_conv_emits_groupnorm_partials(ops, case):
 def test_halo_switch_fallbacks_stay_correct():
     """The A/B switches of the halo kernels select code that the default configuration never runs (they are read once per process):
     no address table (`DD_HALO_TAB=0`: per-piece address arithmetic, also what a geometry whose table does not fit in LDS gets), decoder
-    levels on the one-tile form (`DD_HALO_PERSIST=0`), 4 x 128-pixel tiles (`DD_HALO_TW512=128`, whose 780-pixel halo leaves no room for
-    the table in the 512 x 160 form).  The halo cases of this file again, in a child process with all three set."""
+    levels on the one-tile form (`DD_HALO_PERSIST=0`).  The halo cases of this file again, in a child process with both set."""
     import subprocess
     import sys
-    env = dict(os.environ, DD_HALO_TAB="0", DD_HALO_PERSIST="0", DD_HALO_TW512="128")
+    env = dict(os.environ, DD_HALO_TAB="0", DD_HALO_PERSIST="0")
     out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-k",
                           "test_conv_forward_and_dgrad and halo"], capture_output=True, text=True, timeout=900, env=env,
                          cwd=os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
