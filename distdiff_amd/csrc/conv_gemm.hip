@@ -382,7 +382,14 @@ bool conv_gemm_can_emit_rowstats(ConvGemmParams p, size_t partial_cap_bytes, int
   return true;
 }
 
-hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStream_t stream) {
+int conv_halo_kernel_kind(const ConvGemmParams& p, int tn);   // conv_halo.hip: 1 conv_halo_kernel, 2 conv_halo_persist_kernel, 0 launch_conv_halo refuses
+
+// The launcher's decision, in one place: launch_conv_gemm acts on it, conv_gemm_kind reports it.  On return p is the problem as the chosen
+// kernel gets it (ksplit set; partial dropped when the 8 x 8 chunk split does not fit the scratch).
+enum { PLAN_GENERAL = 0, PLAN_HALO = 1, PLAN_WS = 3, PLAN_PPS = 4, PLAN_EMPTY = 5, PLAN_GROUPED = 6 };
+struct ConvPlan { int path, tn, cfg, split; };
+static hipError_t conv_gemm_plan(ConvGemmParams& p, size_t partial_cap_bytes, ConvPlan* pl) {
+  pl->path = PLAN_EMPTY; pl->tn = 0; pl->cfg = 0; pl->split = 1;
   if (p.K & 63) return hipErrorInvalidValue;
   if ((p.flags & CF_LNFOLD) && (!p.ln_stats || !p.ln_c1 || p.ntaps != 1)) return hipErrorInvalidValue;
   if (p.flags & CF_ROWSTATS) {
@@ -401,7 +408,8 @@ hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStrea
     if (cfg) conv_gemm_big_tile(cfg, &bm, &bn);
     if (!cfg || split != 1 || p.wgroup_rows % bm || p.ntaps != 1 || (p.flags & ~(CF_OUT_F32 | CF_BIAS))) return hipErrorInvalidValue;
     p.ksplit = 1;
-    return launch_conv_gemm_big(p, cfg, stream);
+    pl->path = PLAN_GROUPED; pl->cfg = cfg;
+    return hipSuccess;
   }
   {
     // deep 3x3 / stride 1: halo-resident input tile; at the 8 x 8 level with a chunk split into the split-K scratch + the reduce kernel
@@ -410,22 +418,48 @@ hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStrea
     if (hs > 1 && (size_t)hs * p.M * p.N * sizeof(float) > partial_cap_bytes) q.partial = nullptr;     // scratch too small: no split form
     if (const int tn = conv_halo_config(q)) {
       q.ksplit = conv_halo_split(q) > 1 ? hs : q.ksplit;
-      hipError_t e = launch_conv_halo(q, tn, stream);
-      if (e == hipSuccess && q.ksplit > 1) {
-        const size_t total = (size_t)q.M * ((q.N + 3) / 4);
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, q);
-        e = hipGetLastError();
-      }
-      return e;
+      p = q;
+      pl->path = PLAN_HALO; pl->tn = tn;
+      return hipSuccess;
     }
   }
-  if (const int tn = gemm_ws_config(p)) return launch_gemm_ws(p, tn, stream);           // K = 320 pointwise layers: weight-stationary GEMM
-  if (const int tn = gemm_pp_config(p)) return launch_gemm_pp(p, tn, stream);           // narrow pointwise layers: ping-pong GEMM
-  int cfg, split;
-  select_config(p, partial_cap_bytes, &cfg, &split);
-  p.ksplit = split;
+  if (const int tn = gemm_ws_config(p)) { pl->path = PLAN_WS; pl->tn = tn; return hipSuccess; }     // K = 320 pointwise layers: weight-stationary GEMM
+  if (const int tn = gemm_pp_config(p)) { pl->path = PLAN_PPS; pl->tn = tn; return hipSuccess; }    // narrow pointwise layers: ping-pong GEMM
+  select_config(p, partial_cap_bytes, &pl->cfg, &pl->split);
+  p.ksplit = pl->split;
+  pl->path = PLAN_GENERAL;
+  return hipSuccess;
+}
+
+// The kernel launch_conv_gemm(p, partial_cap_bytes) would run, without launching: 0 conv_gemm_kernel / conv_gemm_big_kernel, 1 conv_halo_kernel,
+// 2 conv_halo_persist_kernel, 3 gemm_ws_kernel, 4 gemm_pps_kernel; -1 when the launcher would refuse the problem
+int conv_gemm_kind(ConvGemmParams p, size_t partial_cap_bytes) {
+  ConvPlan pl;
+  if (conv_gemm_plan(p, partial_cap_bytes, &pl) != hipSuccess) return -1;
+  if (pl.path == PLAN_HALO) { const int k = conv_halo_kernel_kind(p, pl.tn); return k ? k : -1; }
+  return pl.path == PLAN_WS || pl.path == PLAN_PPS ? pl.path : 0;
+}
+
+hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStream_t stream) {
+  ConvPlan pl;
+  const hipError_t pe = conv_gemm_plan(p, partial_cap_bytes, &pl);
+  if (pe != hipSuccess) return pe;
+  if (pl.path == PLAN_EMPTY) return hipSuccess;
+  if (pl.path == PLAN_GROUPED) return launch_conv_gemm_big(p, pl.cfg, stream);
+  if (pl.path == PLAN_HALO) {
+    hipError_t e = launch_conv_halo(p, pl.tn, stream);
+    if (e == hipSuccess && p.ksplit > 1) {
+      const size_t total = (size_t)p.M * ((p.N + 3) / 4);
+      int blocks = (int)((total + 255) / 256);
+      if (blocks > 4096) blocks = 4096;
+      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
+      e = hipGetLastError();
+    }
+    return e;
+  }
+  if (pl.path == PLAN_WS) return launch_gemm_ws(p, pl.tn, stream);
+  if (pl.path == PLAN_PPS) return launch_gemm_pp(p, pl.tn, stream);
+  const int cfg = pl.cfg, split = pl.split;
   if (cfg) {
     hipError_t e = launch_conv_gemm_big(p, cfg, stream);
     if (e != hipSuccess) return e;

@@ -44,8 +44,9 @@ __device__ __forceinline__ float hrow16_sum(float v) {
 // stats_s: the (mean, rstd) rows of the tile in LDS (persistent GEMM: they arrive with the bias through the LDS-DMA ring), or null (global loads).
 // LA: 16-row tiles whose residual rows / statistics are requested together (2: one exposed memory latency per 32 rows; 4: per 64 rows --
 // 16 more registers, which only the TN = 4 forms have: with TN = 5 it spilled)
-template <int TN, int LA = 2, class MOf>
-__device__ __forceinline__ void pp_epilogue(const ConvGemmParams& p, f32x4 (&acc)[8][TN], MOf m_of, int wr, int wc, int n0,
+// sblk_of(r): CF_STATS block slot ([M / 64] of p.stats) of the 64 tile rows r .. r + 63 (r a multiple of 64)
+template <int TN, int LA = 2, class MOf, class SOf>
+__device__ __forceinline__ void pp_epilogue(const ConvGemmParams& p, f32x4 (&acc)[8][TN], MOf m_of, SOf sblk_of, int wr, int wc, int n0,
                                             const float* bias_s, const float* c1_s, int span, int fr, int fq, const float* stats_s = nullptr) {
   constexpr int TNP = TN & ~1;
   const int fl = p.flags;
@@ -135,8 +136,7 @@ __device__ __forceinline__ void pp_epilogue(const ConvGemmParams& p, f32x4 (&acc
     }
     if (fl & CF_STATS) {
       // per-(64-row block, channel) (mean, M2) of the stored values for the GroupNorm that consumes this tensor (conv_gemm2.hip emit_stats)
-      const int m0w = m_of(wr * 128 + blk * 64);           // 64 consecutive output rows (tw >= 64, or whole image rows)
-      float* dst0 = p.stats + ((size_t)(m0w >> 6) * p.stats_ld) * 2;
+      float* dst0 = p.stats + ((size_t)sblk_of(wr * 128 + blk * 64) * p.stats_ld) * 2;
 #pragma unroll
       for (int jn = 0; jn < TN; ++jn) {
         float o[8];
@@ -157,10 +157,22 @@ __device__ __forceinline__ void pp_epilogue(const ConvGemmParams& p, f32x4 (&acc
   }
 }
 
-// Tile geometry (host: halo_geometry): a tile is th x tw OUTPUT pixels of one image (th * tw = 256, tw = min(Wo, 128) a power of two),
-// i.e. 256 / Wo whole image rows for Wo <= 128 and a 2 x 128 block for wider images; its halo is (th + 2) x (tw + 2) LOGICAL input
+// Tile geometry (host: halo_geometry): a tile is th x tw OUTPUT pixels of one image (th * tw = 256 or 512, tw a power of two >= 16 that
+// divides Wo: Wo itself, or 64 / 128 of a wider power-of-two row, or the largest power-of-two factor of a width such as 48 / 96 / 192 / 768),
+// tiles_x = Wo / tw of them side by side; its halo is (th + 2) x (tw + 2) LOGICAL input
 // pixels (the fused nearest-2x upsample of the decoder's / UNet's upsamplers reads stored pixel (iy >> shift, ix >> shift)).
 struct HaloGeo { int ltw, th, halo_px, tiles_x, tiles_y, ipt, tab; };   // tab: the one-tile kernel uses the LDS halo address table   // ipt: images per tile (4 at 8 x 8: a tile is 4 whole images, each with its own 10 x 10 halo block)
+
+// CF_STATS block slot of the 64 tile pixels r .. r + 63 (r % 64 == 0) of the tile at (y0, x0) of the image whose first output row is mimg.
+// tw >= 64: they are 64 consecutive output rows m inside one image row, slot m >> 6 as in every other kernel.  tw = 16 / 32: they are
+// 64 / tw image rows x tw pixels, which with several tiles per image row are NOT consecutive in m; the consumer (norm.hip,
+// gn_finalize_chan_kernel) merges the Ho * Wo / 64 slots of an image as an unordered set of equal-count (64) partials, so any one-to-one
+// map of the image's 64-pixel groups onto its slots is correct: slot = (row group) * tiles_x + (tile column).  Row groups are whole
+// (th is a multiple of 64 / tw), so the map is one-to-one; with one tile per image row it is m >> 6 again.
+__device__ __forceinline__ int halo_stats_block(int mimg, int y0, int x0, int r, int lw, int Wo, int tiles_x) {
+  if (lw >= 6) return (mimg + (y0 + (r >> lw)) * Wo + x0 + (r & ((1 << lw) - 1))) >> 6;
+  return (mimg >> 6) + ((y0 + (r >> lw)) >> (6 - lw)) * tiles_x + (x0 >> lw);
+}
 
 // WN = 4: 256 x (64 TN) tiles, waves 2 (M) x 4 (N); WN = 2: 512 x (32 TN) tiles, waves 4 (M) x 2 (N) -- the narrow outputs of the decoder's
 // last level (N = 128).  Either way a wave owns 128 rows x TN * 16 columns and waves w, w + 4 (one SIMD) sit in different row groups.
@@ -201,6 +213,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
   const int kz = MI ? blockIdx.y : 0;                     // chunk split (8 x 8 level: too few tiles to fill the chip): fp32 partial sums
   const int mimg = img * p.Ho * p.Wo;
   auto m_of = [&](int r) { return mimg + (y0 + (r >> lw)) * p.Wo + x0 + (r & (Wd - 1)); };   // output row of tile pixel r
+  auto sblk_of = [&](int r) { return halo_stats_block(mimg, y0, x0, r, lw, p.Wo, geo.tiles_x); };
   const int chunks_all = p.cin >> 6;
   const int cper = MI ? (chunks_all + p.ksplit - 1) / (p.ksplit > 0 ? p.ksplit : 1) : chunks_all;
   const int c_begin = MI ? kz * cper : 0, c_end = MI ? min(chunks_all, c_begin + cper) : chunks_all;
@@ -387,7 +400,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
       }
     }
   } else {
-    pp_epilogue<TN>(p, acc, m_of, wr, wc, n0, bias_s, bias_s, 0, fr, fq);
+    pp_epilogue<TN>(p, acc, m_of, sblk_of, wr, wc, n0, bias_s, bias_s, 0, fr, fq);
   }
 }
 
@@ -583,7 +596,8 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
     auto m_of = [&](int r) { return mimg + (y0 + (r >> lw)) * p.Wo + x0 + (r & (Wd - 1)); };
     const float* bias_s = bias_base + (it & 1) * BN;
     // look-ahead 2: 4 measured 2-3 % SLOWER on every decoder shape (256 VGPRs + 10 spills; profiles/r06_decoder_persist.txt)
-    pp_epilogue<TN, 2>(p, acc, m_of, wr, wc, g.n0, bias_s, bias_s, 0, fr, fq);
+    auto sblk_of = [&](int r) { return halo_stats_block(mimg, y0, x0, r, lw, p.Wo, geo.tiles_x); };
+    pp_epilogue<TN, 2>(p, acc, m_of, sblk_of, wr, wc, g.n0, bias_s, bias_s, 0, fr, fq);
     HP_STAMP(xs + t, 4);
     if (!have_next) break;
     g = gn; t = tn_;
@@ -787,8 +801,9 @@ __global__ __launch_bounds__(512, 1) void gemm_pps_kernel(ConvGemmParams p) {
     const float* bias_s = (const float*)(smem + AUX + (it & 1) * SLOT);
     const int m0c = m0;
     auto m_of = [&](int r) { return m0c + r; };
+    auto sblk_of = [&](int r) { return (m0c + r) >> 6; };
     if constexpr (GEGLU) pp_epilogue_geglu(p, acc, m_of, wr, wc, n0, bias_s, bias_s + 512, fr, fq, bias_s + 1024);
-    else pp_epilogue<TN>(p, acc, m_of, wr, wc, n0, bias_s, bias_s + 512, (n0 / BN) * 4 + wc, fr, fq, bias_s + 1024);
+    else pp_epilogue<TN>(p, acc, m_of, sblk_of, wr, wc, n0, bias_s, bias_s + 512, (n0 / BN) * 4 + wc, fr, fq, bias_s + 1024);
     PPS_STAMP(tile, 3);
     tile = tile_n; m0 = m0n; n0 = n0n; xt = xtn; wsoff = wsoffn;
   }
@@ -802,12 +817,21 @@ bool halo_geometry(const ConvGemmParams& p, int bm, HaloGeo* g) {
     g->ltw = 3; g->th = 8; g->halo_px = 4 * 100; g->tiles_x = 1; g->tiles_y = 1; g->ipt = 4; g->tab = 0;
     return true;
   }
-  if (Wo < 16 || (Wo & (Wo - 1))) return false;
-  // wide images: 512-pixel tiles are 8 rows x 64 pixels (halo 10 x 66 = 660 pixels) rather than 4 x 128 (6 x 130 = 780): the halo refill
-  // at every 64-channel chunk boundary is the largest exposed cost of the decoder's short K loops (tools/halo_trace.py: ~5 us of a
-  // 14.6 us chunk), and it scales with the halo's bytes.  tw >= 64 keeps a CF_STATS block (64 consecutive output pixels) inside one row.
-  const int tw = Wo < 128 ? Wo : (bm == 512 ? 64 : 128), th = bm / tw;
-  if (Ho % th) return false;
+  // Tile width tw: the largest power-of-two factor of Wo, capped -- 512-pixel tiles are 8 rows x 64 pixels (halo 10 x 66 = 660 pixels) rather
+  // than 4 x 128 (6 x 130 = 780): the halo refill at every 64-channel chunk boundary is the largest exposed cost of the decoder's short
+  // K loops (tools/halo_trace.py: ~5 us of a 14.6 us chunk), and it scales with the halo's bytes; 256-pixel tiles are at most 128 wide.
+  // A power-of-two Wo gives what it always gave (Wo itself below 128, else 64 / 128); 96 -> 32 (3 tiles per row), 48 / 80 -> 16,
+  // 160 -> 32, 192 / 320 -> 64, 384 / 640 / 768 -> 64 or 128.  tw >= 16 is what the kernels' LDS swizzle needs (16-pixel MFMA row tiles
+  // start at multiples of 16 inside a tile row): widths whose power-of-two factor is 8 or less (24, 12, 40, 20, 10) stay on the general
+  // kernels, and the 8 x 8 multi-image form above is the only narrower one.  th = bm / tw is a power of two >= 2, so every tile origin
+  // (y0, x0) is even: the fused-upsample forms (p.shift = 1) rely on it for (y0 - 1 + hy) >> 1 == (y0 >> 1) - 1 + ((hy + 1) >> 1).
+  // CF_STATS with tw < 64 and several tiles per row: halo_stats_block.
+  const int cap = bm == 512 ? 64 : 128;
+  int tw = Wo & -Wo;
+  if (tw > cap) tw = cap;
+  if (tw < 16) return false;
+  const int th = bm / tw;
+  if (th < 2 || (th & 1) || th > Ho || Ho % th) return false;
   int l = 0;
   while ((1 << l) < tw) ++l;
   g->ltw = l; g->th = th; g->halo_px = (th + 2) * (tw + 2); g->tiles_x = Wo / tw; g->tiles_y = Ho / th;
@@ -948,17 +972,31 @@ extern "C" int dd_debug_read_pp_trace(unsigned long long* host, int n) {
 }
 #endif
 
-hipError_t launch_conv_halo(const ConvGemmParams& p, int tn, hipStream_t stream) {
-  HaloGeo g;
-  if (!halo_geometry(p, tn == 2 || tn == 6 || tn == 1 ? 512 : 256, &g)) return hipErrorInvalidValue;
-  if (tn == 1) return run_halo<1, 2>(p, g, stream);
-  // 512 x 128 tiles with a short K loop (the decoder's levels): the persistent form, next tile's first stage requested under the epilogue
+// true iff launch_conv_halo runs form tn of this problem on conv_halo_persist_kernel: 512 x 128 tiles with a short K loop (the decoder's
+// levels, any width halo_geometry accepts: 128 ... 1024 as 192 / 384 / 768), next tile's first stage requested under the epilogue
+static bool halo_persist_ok(const ConvGemmParams& p, const HaloGeo& g, int tn) {
   static const int persist = getenv("DD_HALO_PERSIST") ? atoi(getenv("DD_HALO_PERSIST")) : 1;
   // (address table: halo row < 31, column < 256, byte offsets inside the halo's stored rows below 8 MB)
-  if (tn == 2 && persist && g.ipt == 1 && p.N % 128 == 0 && (p.cin >> 6) <= persist * 8 &&
-      g.th + 2 < 31 && (1 << g.ltw) + 2 < 256 && (size_t)(g.th + 3) * p.W * p.x_ld * 2 < (8u << 20) &&
-      2 * 128 * 128 + ((g.halo_px + 7) & ~7) * 128 + 2 * 128 * 4 + ((g.halo_px + 7) >> 3) * 256 + 64 <= 163840)
-    return run_halo_persist<4, 2>(p, g, stream);
+  return tn == 2 && persist && g.ipt == 1 && p.N % 128 == 0 && (p.cin >> 6) <= persist * 8 &&
+         g.th + 2 < 31 && (1 << g.ltw) + 2 < 256 && (size_t)(g.th + 3) * p.W * p.x_ld * 2 < (8u << 20) &&
+         2 * 128 * 128 + ((g.halo_px + 7) & ~7) * 128 + 2 * 128 * 4 + ((g.halo_px + 7) >> 3) * 256 + 64 <= 163840;
+}
+static int halo_bm(int tn) { return tn == 2 || tn == 6 || tn == 1 ? 512 : 256; }
+
+// which kernel launch_conv_halo(p, tn) runs: 1 conv_halo_kernel, 2 conv_halo_persist_kernel, 0 neither (the launch would fail)
+int conv_halo_kernel_kind(const ConvGemmParams& p, int tn) {
+  HaloGeo g;
+  if (!halo_geometry(p, halo_bm(tn), &g)) return 0;
+  if (tn != 1 && halo_persist_ok(p, g, tn)) return 2;
+  if (g.ipt > 1 && !(tn == 5 && p.ksplit > 1 && (p.cin >> 6) % p.ksplit == 0)) return 0;
+  return 1;
+}
+
+hipError_t launch_conv_halo(const ConvGemmParams& p, int tn, hipStream_t stream) {
+  HaloGeo g;
+  if (!halo_geometry(p, halo_bm(tn), &g)) return hipErrorInvalidValue;
+  if (tn == 1) return run_halo<1, 2>(p, g, stream);
+  if (halo_persist_ok(p, g, tn)) return run_halo_persist<4, 2>(p, g, stream);
   if (g.ipt > 1) return (tn == 5 && p.ksplit > 1 && (p.cin >> 6) % p.ksplit == 0) ? run_halo<5, 4, true>(p, g, stream) : hipErrorInvalidValue;
   return tn == 5 ? run_halo<5, 4>(p, g, stream) : tn == 4 ? run_halo<4, 4>(p, g, stream) : tn == 6 ? run_halo<5, 2>(p, g, stream) : run_halo<4, 2>(p, g, stream);
 }

@@ -68,6 +68,10 @@ struct ConvGemmParams {
 
 // Chooses tile configuration / split-K from the shape. `partial_cap_bytes` bounds split-K workspace.
 hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStream_t stream);
+// The kernel launch_conv_gemm(p, partial_cap_bytes) would run (the launcher's own decision code, nothing is launched): 0 the general
+// kernels (conv_gemm_kernel / conv_gemm_big_kernel), 1 conv_halo_kernel, 2 conv_halo_persist_kernel, 3 gemm_ws_kernel, 4 gemm_pps_kernel;
+// -1 when the launcher would refuse the problem
+int conv_gemm_kind(ConvGemmParams p, size_t partial_cap_bytes);
 // Preferred split for a shape (used by the engine to size the workspace).
 int conv_gemm_pick_split(int M, int N, int K);
 // true iff launch_conv_gemm(p, partial_cap_bytes) will honour CF_STATS for this problem (persistent big-tile kernel, no split-K,

@@ -11,6 +11,10 @@ int dd_op_conv_gemm(const ConvGemmParams* p, size_t cap, void* st) {
   // validates it when the weights are packed (distdiff_amd/ops.py: PackedConv.taptab_host), not here per launch.
   return (int)launch_conv_gemm(*p, cap, S(st));
 }
+int dd_op_conv_gemm_kind(const ConvGemmParams* p, size_t cap) {
+  if (!p) return -1;                                    // DD_ERR_ARG
+  return conv_gemm_kind(*p, cap);
+}
 int dd_op_conv_gemm_check(const ConvGemmParams* p, void* st) {
   // The synchronous companion for ABI users who want the contract checked against the DEVICE table: waits for the stream, reads the
   // tap table back and validates it (entries in range; a one-tap stride-1 same-size launch carries the centre tap).  0 = fine.

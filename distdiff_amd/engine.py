@@ -165,13 +165,26 @@ HBM_BYTES_PER_IMAGE_PLAIN = 3.0e9
 HBM_BYTES_FIXED = 12e9
 
 
-def batch_for_free_hbm(free_bytes, guided=True):
-    """Largest static engine batch of 32 / 16 / 8 whose workspace fits `free_bytes` of HBM."""
+def predicted_workspace_bytes(batch, guided=True, latent_size=64):
+    """HBM the engine is expected to need for `batch` images: the per-image part scales with the pixel count (every activation, stash and
+    gradient buffer is per pixel), the fixed part (weights, guide / VAE scratch, allocator slack) does not.  Measured vs predicted at
+    latents 48 and 96: DESIGN.md 5.2."""
     per = HBM_BYTES_PER_IMAGE_GUIDED if guided else HBM_BYTES_PER_IMAGE_PLAIN
-    for B in (32, 16):
-        if free_bytes >= B * per + HBM_BYTES_FIXED:
+    return batch * per * (latent_size / 64.0) ** 2 + HBM_BYTES_FIXED
+
+
+def batch_for_free_hbm(free_bytes, guided=True, latent_size=64):
+    """Largest static engine batch whose predicted workspace fits `free_bytes` of HBM: of 32 / 16 / 8 at 512 x 512 (latent 64; never below
+    8), of 32 / 16 / 8 / 4 / 2 / 1 at any other resolution (1 when none fits)."""
+    if latent_size == 64:
+        for B in (32, 16):
+            if free_bytes >= predicted_workspace_bytes(B, guided):
+                return B
+        return 8
+    for B in (32, 16, 8, 4, 2):
+        if free_bytes >= predicted_workspace_bytes(B, guided, latent_size):
             return B
-    return 8
+    return 1
 
 
 class Engine:

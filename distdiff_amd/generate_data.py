@@ -97,7 +97,8 @@ def parse_args(argv=None):
                    "configs[4]).  A real model directory is recognised by its text_encoder_2/ sub-folder")
     p.add_argument("--engine_batch", type=int, default=0, help="images per engine launch (0 = the largest of 32 / 16 / 8 whose workspace fits the free HBM -- engine.batch_for_free_hbm: "
                    "about 5.85 GB per image with transform guidance at 512x512 + 12 GB, i.e. 199 / 106 / 59 GB; 32 is 4 %% faster than 16 and 16 12 %% "
-                   "faster than 8; SDXL at 1024x1024: 4 or 2 --, the minimum over the ranks of a run); units (image, expand index) are independent")
+                   "faster than 8; at another --resolution the per-image part scales with the pixel count and the choice is of 32 / 16 / 8 / 4 / 2 / 1, "
+                   "e.g. 13.2 GB per image at 768x768; SDXL at 1024x1024: 4 or 2 --, the minimum over the ranks of a run); units (image, expand index) are independent")
     p.add_argument("--attn_fp8", action="store_true", help="BASELINE configs[4]: P.V of the UNet's d = 64 attention heads (SDXL) on the fp8 MFMA "
                    "(dd_config.unet_attn_fp8).  Off by default: the bf16 form is faster on MI355X and closer to fp32 (DESIGN.md Appendix A row 28)")
     p.add_argument("--data_root", type=str, default="data")
@@ -451,18 +452,20 @@ def load_config_and_weights(args, B):
 
 
 def auto_engine_batch(args, dev, distributed=False):
-    """Static engine batch when --engine_batch is not given: 8 for --tiny; at 512x512 the largest of 32 / 16 / 8 whose workspace fits the
-    free HBM (engine.batch_for_free_hbm: the two activation stashes of the chained guided steps + the liveness-packed gradient slab,
-    186.7 GB measured at 32 images; 32 images per launch are 4 % faster than 16 on an MI355X); 16 otherwise.  Ranks of one run agree on the minimum."""
+    """Static engine batch when --engine_batch is not given: 8 for --tiny; on a GPU the largest batch whose workspace fits the free HBM
+    (engine.batch_for_free_hbm: the two activation stashes of the chained guided steps + the liveness-packed gradient slab, 186.7 GB
+    measured at 32 images of 512 x 512, scaled by the pixel count of --resolution: 32 / 16 / 8 at 512 x 512, where 32 images per launch
+    are 4 % faster than 16 on an MI355X, 32 / 16 / 8 / 4 / 2 / 1 at any other resolution); 16 without a GPU.  Ranks of one run agree on
+    the minimum."""
     if args.tiny:
         return 8
     on_gpu = torch.device(dev).type == "cuda" and torch.cuda.is_available()
     if args.synthetic_arch == "sdxl" or os.path.isdir(os.path.join(args.pretrained_model_name_or_path, "text_encoder_2")):
         # SDXL-base at 1024 x 1024: 161 GB at 4 images, 115 GB at 2 (bench.py --config sdxl)
         B = (4 if torch.cuda.mem_get_info(torch.device(dev))[0] >= 175e9 else 2) if on_gpu else 2
-    elif args.resolution == 512 and on_gpu:
+    elif on_gpu:
         from .engine import batch_for_free_hbm
-        B = batch_for_free_hbm(torch.cuda.mem_get_info(torch.device(dev))[0], guided=bool(args.guidance_type))
+        B = batch_for_free_hbm(torch.cuda.mem_get_info(torch.device(dev))[0], guided=bool(args.guidance_type), latent_size=args.resolution // 8)
     else:
         return 16
     if distributed and on_gpu:

@@ -102,12 +102,22 @@ def conv_f32(x, pk, B, H, W, Ho, Wo, stride=1, shift=0, parity=0, res=None, mask
     return y[:, :pk.N]
 
 
-def conv_gemm(x, pk, B, H, W, Ho, Wo, stride=1, shift=0, parity=0, res=None, mask=None, relu=False, out_f32=False,
-              ksplit=0, alpha=1.0, raw=None, y=None, x_ld=None, partial=None, force_small=False, stats=None, ln_stats=None, ln_c1=None,
-              rowpart=None, check_device_taps=False):
-    """x: bf16 [B*H*W, x_ld]; returns y [B*Ho*Wo, N(or N/2 for GEGLU)].  stats: fp32 [M/64, C, 2] buffer (or a column view of one) to
-    receive the per-(64-row block, channel) partial (mean, M2) of the stored values (CF_STATS; the launch fails if the kernel the
-    launcher picks for this shape cannot emit them)."""
+_NOT_READ = 1 << 12     # stands for a buffer in conv_gemm_kind: the decision tests pointers for null and never follows them
+
+
+def _dry_ptr(t):
+    return C.c_void_p(_NOT_READ) if t is True else _ptr(t)
+
+
+def _dry_ld(t, ncols):
+    return ncols if t is True else t.stride(0)
+
+
+def _conv_gemm_params(x, pk, B, H, W, Ho, Wo, stride=1, shift=0, parity=0, res=None, mask=None, relu=False, out_f32=False,
+                      ksplit=0, alpha=1.0, raw=None, y=None, x_ld=None, partial=None, force_small=False, stats=None, ln_stats=None, ln_c1=None,
+                      rowpart=None, dry=False):
+    """The ConvGemmParams block of one launch: (p, partial_cap_bytes, y, buffers to keep alive).  dry (conv_gemm_kind): nothing is
+    allocated; x / y may be None (contiguous rows assumed) and res / stats / ln_stats / rowpart may be True for "present"."""
     p = ConvGemmParams()
     M = B * Ho * Wo
     ncols = pk.N // 2 if pk.geglu else pk.N
@@ -115,20 +125,20 @@ def conv_gemm(x, pk, B, H, W, Ho, Wo, stride=1, shift=0, parity=0, res=None, mas
     # checked here on the host copy kept at pack time, so the launch itself stays stream-asynchronous
     if pk.ntaps == 1 and stride == 1 and (H, W) == (Ho, Wo) and shift == 0 and int(pk.taptab_host[0]) != ((32 << 6) | 32):
         raise RuntimeError("conv_gemm: a one-tap stride-1 launch must be the centre tap (got %#x)" % int(pk.taptab_host[0]))
-    if y is None:
+    if y is None and not dry:
         y = torch.empty((M, ncols), device=x.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
     p.x, p.w, p.taptab, p.y = _ptr(x), _ptr(pk.w), _ptr(pk.taptab), _ptr(y)
-    p.x_ld = x_ld if x_ld is not None else x.stride(0)
-    p.y_ld = y.stride(0)
+    p.x_ld = x_ld if x_ld is not None else (x.stride(0) if x is not None else pk.cin)
+    p.y_ld = y.stride(0) if y is not None else ncols
     flags = 0
     if pk.bias is not None:
         flags |= CF_BIAS
         p.bias = _ptr(pk.bias)
     if res is not None:
         flags |= CF_RES
-        if res.dtype == torch.float32:
+        if res is not True and res.dtype == torch.float32:
             flags |= CF_RES_F32
-        p.res, p.res_ld = _ptr(res), res.stride(0)
+        p.res, p.res_ld = _dry_ptr(res), _dry_ld(res, ncols)
     if mask is not None:
         flags |= CF_MASK
         p.mask, p.mask_ld = _ptr(mask), mask.stride(0)
@@ -143,27 +153,49 @@ def conv_gemm(x, pk, B, H, W, Ho, Wo, stride=1, shift=0, parity=0, res=None, mas
             p.raw, p.raw_ld = _ptr(raw), raw.stride(0)
     cap = 0
     if ksplit != 1:
-        if partial is None:
+        if partial is None and not dry:
             partial = torch.empty((max(ksplit, 16) * M * pk.N,), device=x.device, dtype=torch.float32)
-        p.partial = _ptr(partial)
-        cap = partial.numel() * 4
+        p.partial = _dry_ptr(True if partial is None else partial)
+        cap = (max(ksplit, 16) * M * pk.N if partial is None else partial.numel()) * 4
     p.B, p.H, p.W, p.Ho, p.Wo, p.stride, p.shift, p.parity = B, H, W, Ho, Wo, stride, shift, parity
     p.cin, p.ntaps, p.M, p.N, p.K = pk.cin, pk.ntaps, M, pk.N, pk.K
     if stats is not None:
         flags |= CF_STATS
-        p.stats, p.stats_ld = _ptr(stats), stats.stride(0) // 2
+        p.stats, p.stats_ld = _dry_ptr(stats), _dry_ld(stats, 2 * ncols) // 2
     if ln_stats is not None:      # CF_LNFOLD: x is the raw LayerNorm input, pk holds gamma o W, ln_c1 its column sums (packed order)
         flags |= CF_LNFOLD
-        p.ln_stats, p.ln_c1 = _ptr(ln_stats), _ptr(ln_c1)
+        p.ln_stats, p.ln_c1 = _dry_ptr(ln_stats), _dry_ptr(True if ln_stats is True else ln_c1)
     if rowpart is not None:       # CF_ROWSTATS: fp32 [M, spans, 2] (sum, sum of squares) per row and column span
         flags |= CF_ROWSTATS
-        p.rowpart, p.rowpart_ld = _ptr(rowpart), rowpart.stride(0) // 2
+        p.rowpart, p.rowpart_ld = _dry_ptr(rowpart), _dry_ld(rowpart, 2 * ((ncols + 39) // 40)) // 2
     p.ksplit, p.flags, p.alpha = ksplit, flags, alpha
     p.force_small = int(force_small)
+    return p, cap, y, (partial,)
+
+
+def conv_gemm(x, pk, B, H, W, Ho, Wo, *args, check_device_taps=False, **kw):
+    """x: bf16 [B*H*W, x_ld]; returns y [B*Ho*Wo, N(or N/2 for GEGLU)].  stats: fp32 [M/64, C, 2] buffer (or a column view of one) to
+    receive the per-(64-row block, channel) partial (mean, M2) of the stored values (CF_STATS; the launch fails if the kernel the
+    launcher picks for this shape cannot emit them).  Keywords: _conv_gemm_params."""
+    p, cap, y, _keep = _conv_gemm_params(x, pk, B, H, W, Ho, Wo, *args, **kw)
     if check_device_taps:      # synchronous: the tap contract against the DEVICE table (dd_op_conv_gemm_check)
         check(_lib.lib().dd_op_conv_gemm_check(C.byref(p), _stream()), "conv_gemm tap table check")
     check(_lib.lib().dd_op_conv_gemm(C.byref(p), cap, _stream()), "conv_gemm")
     return y
+
+
+CONV_GEMM_KINDS = ("general", "conv_halo", "conv_halo_persist", "gemm_ws", "gemm_pps")
+
+
+def conv_gemm_kind(x, pk, B, H, W, Ho, Wo, *args, **kw):
+    """Which kernel conv_gemm would run for the same arguments, as an index into CONV_GEMM_KINDS (dd_op_conv_gemm_kind: the launcher's
+    own decision, nothing is launched or allocated).  Buffers may be left out: x / y = None mean contiguous rows, res / stats /
+    ln_stats / rowpart = True mean "present".  Raises for a problem the launcher refuses."""
+    p, cap, _y, _keep = _conv_gemm_params(x, pk, B, H, W, Ho, Wo, *args, dry=True, **kw)
+    kind = _lib.lib().dd_op_conv_gemm_kind(C.byref(p), cap)
+    if kind < 0:
+        raise RuntimeError("conv_gemm_kind: the launcher refuses this problem (status %d)" % kind)
+    return kind
 
 
 def groupnorm(x, gamma, beta, B, HW, G, eps, silu, dy=None, stats=None, chan_part=None):

@@ -38,6 +38,10 @@ struct ConvF32Params;
  * entry point is stream-asynchronous and does not read device memory: the owner of the table checks it on the host when the weights
  * are packed (distdiff_amd/ops.py raises on any other single tap). */
 int dd_op_conv_gemm(const struct ConvGemmParams* p, size_t partial_cap_bytes, void* stream);
+/* Which kernel dd_op_conv_gemm(p, partial_cap_bytes, .) would run, decided by the launcher's own code without launching anything (no
+ * device access; the pointers are only tested for null): 0 the general implicit-GEMM kernels (conv_gemm_kernel / conv_gemm_big_kernel),
+ * 1 conv_halo_kernel, 2 conv_halo_persist_kernel, 3 gemm_ws_kernel, 4 gemm_pps_kernel; DD_ERR_ARG (-1) for a problem the launcher refuses. */
+int dd_op_conv_gemm_kind(const struct ConvGemmParams* p, size_t partial_cap_bytes);
 /* Synchronous check of that contract against the DEVICE table (waits for the stream, copies the table back): 0 when every entry is in
  * range and a pointwise launch carries the centre tap.  For ABI users without a host copy of their tables; never called by the engine. */
 int dd_op_conv_gemm_check(const struct ConvGemmParams* p, void* stream);
