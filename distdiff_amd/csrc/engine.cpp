@@ -319,6 +319,7 @@ int dd_finalize_weights(dd_engine* E) {
     E->score_tmp = (float*)E->dmalloc(256);
     E->sample_w = (float*)E->dmalloc((size_t)B * 4);
     E->image_scores = (float*)E->dmalloc((size_t)B * 4);
+    E->rng_eb = (float*)E->dmalloc((size_t)B * 8 * 4);
     // cross-attention K/V buffers
     E->ctx_bf16 = (bf16_t*)E->dmalloc((size_t)2 * B * c.text_len * rup(c.unet_cross_dim, 8) * 2);
     for (auto& sl : E->cross_slots) {
@@ -651,19 +652,78 @@ int dd_direct_guidance(dd_engine* E, const float* z, const int* targets, int ste
   });
 }
 
+// out [B, n_per_unit] of one stream of the counter-based generator; the unit ids travel in the kernel arguments, DD_RNG_UNITS per launch
+static void philox_units_enqueue(uint64_t seed, int rng_stream, const uint64_t* unit_ids, int B, int64_t n_per_unit, float* out, hipStream_t s) {
+  for (int u0 = 0; u0 < B; u0 += DD_RNG_UNITS) {
+    RngUnits ids{};
+    const int cnt = std::min(DD_RNG_UNITS, B - u0);
+    for (int k = 0; k < cnt; ++k) { ids.lo[k] = (unsigned)unit_ids[u0 + k]; ids.hi[k] = (unsigned)(unit_ids[u0 + k] >> 32); }
+    HIPCHK(launch_philox_units(ids, cnt, seed, rng_stream, n_per_unit, out + (size_t)u0 * n_per_unit, s));
+  }
+}
+
+int dd_randn_units(dd_engine* E, uint64_t seed, int rng_stream, const uint64_t* unit_ids, int B, int64_t n_per_unit, float* out, void* stream) {
+  if (!E || !unit_ids || !out || B < 1 || n_per_unit < 1 || rng_stream < 0 || rng_stream > 3) return DD_ERR_ARG;
+  DD_TRY(E, { philox_units_enqueue(seed, rng_stream, unit_ids, B, n_per_unit, out, (hipStream_t)stream); });
+}
+
+// noise_mode 1 of dd_expand: the loop's first latent written straight from the generated values into `z0`, e and b into E->rng_eb
+static int expand_generated_inputs(dd_engine* E, const dd_expand_args* a, float* z0, hipStream_t s) {
+  DD_TRY(E, {
+    check_batch(E, a->B);
+    const dd_config& c = E->cfg;
+    const int HW = c.latent_size * c.latent_size;
+    if (a->text_to_img) {
+      philox_units_enqueue(a->seed, 0, a->unit_ids, a->B, (int64_t)c.unet_in_channels * HW, z0, s);      // z = n * init_noise_sigma (= 1 for DDIM)
+    } else {
+      for (int u0 = 0; u0 < a->B; u0 += DD_RNG_UNITS) {
+        RngUnits ids{};
+        const int cnt = std::min(DD_RNG_UNITS, a->B - u0);
+        for (int k = 0; k < cnt; ++k) { ids.lo[k] = (unsigned)a->unit_ids[u0 + k]; ids.hi[k] = (unsigned)(a->unit_ids[u0 + k] >> 32); }
+        const size_t off = (size_t)u0 * c.unet_in_channels * HW;
+        HIPCHK(launch_philox_add_noise(ids, cnt, a->seed, a->image_latents + off, z0 + off, c.unet_in_channels, HW, a->offset_noise,
+                                       E->coef_table + (size_t)a->start_index * 8 + 1, s));
+      }
+    }
+    if (a->guidance_type == 1) {
+      philox_units_enqueue(a->seed, 2, a->unit_ids, a->B, 4, E->rng_eb, s);
+      philox_units_enqueue(a->seed, 3, a->unit_ids, a->B, 4, E->rng_eb + (size_t)a->B * 4, s);
+    }
+  });
+}
+
 int dd_expand(dd_engine* E, const dd_expand_args* a, void* stream) {
-  if (!E || !a || !a->image_latents || !a->noise || !a->z_out) return DD_ERR_ARG;
+  if (!E || !a || !a->z_out || a->noise_mode < 0 || a->noise_mode > 1) return DD_ERR_ARG;
+  if ((!a->image_latents && !a->text_to_img) || (a->noise_mode == 0 && !a->noise) || (a->noise_mode == 1 && !a->unit_ids)) return DD_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int n = (int)E->timesteps.size();
   if (a->start_index < 0 || a->start_index >= n) { E->err = "start_index out of range"; return DD_ERR_ARG; }
-  int rc = dd_add_noise(E, a->image_latents, a->noise, E->f32_tmp[3], a->B, a->start_index, stream);
+  if (a->text_to_img && a->start_index != 0) { E->err = "text_to_img runs the whole schedule: start_index must be 0"; return DD_ERR_ARG; }
+  const float* ch_e = a->e;
+  const float* ch_b = a->b;
+  int rc;
+  if (a->noise_mode == 1) {
+    rc = expand_generated_inputs(E, a, E->f32_tmp[3], s);
+    ch_e = E->rng_eb;
+    ch_b = E->rng_eb + (size_t)a->B * 4;
+  } else if (a->text_to_img) {
+    // the caller's noise is the first latent (init_noise_sigma = 1): add_noise is skipped
+    rc = DD_OK;
+    try {
+      check_batch(E, a->B);
+      const dd_config& c = E->cfg;
+      HIPCHK(hipMemcpyAsync(E->f32_tmp[3], a->noise, (size_t)a->B * c.unet_in_channels * c.latent_size * c.latent_size * 4, hipMemcpyDeviceToDevice, s));
+    } catch (const std::exception& ex) { E->err = ex.what(); return DD_ERR_HIP; }
+  } else {
+    rc = dd_add_noise(E, a->image_latents, a->noise, E->f32_tmp[3], a->B, a->start_index, stream);
+  }
   if (rc) return rc;
   float* cur = E->f32_tmp[3];
   float* nxt = E->f32_tmp[4];
   for (int i = a->start_index; i < n; ++i) {
     if (a->guidance_type == 1 && a->guide_count > 0 && i == a->guide_first) {
       // transform guidance at t == guide_timesteps[0], then the step is executed again from the corrected latent (:1203-1207)
-      rc = dd_transform_guidance(E, cur, a->targets, a->e, a->b, a->guide_first, a->guide_count, nxt, a->score_out, nullptr, a->B, stream);
+      rc = dd_transform_guidance(E, cur, a->targets, ch_e, ch_b, a->guide_first, a->guide_count, nxt, a->score_out, nullptr, a->B, stream);
       if (rc) return rc;
       std::swap(cur, nxt);
       rc = dd_denoise_step(E, cur, i, nxt, nullptr, a->B, stream);

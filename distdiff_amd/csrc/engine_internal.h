@@ -290,6 +290,7 @@ struct dd_engine {
   float* score_tmp = nullptr;
   float* sample_w = nullptr; bool sample_w_set = false;   // per-image energy weights (dd_set_sample_weights); default 1/B
   float* image_scores = nullptr;                         // per-image energies of the last guidance call
+  float* rng_eb = nullptr;                               // e [B,4] | b [B,4] generated by dd_expand's noise_mode 1
   const float* image_override = nullptr; int image_override_count = 0;   // dd_debug_set_images: parity tests evaluate the guide at given images
   size_t total_bytes = 0;
   double flops = 0;

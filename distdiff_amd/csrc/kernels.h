@@ -182,6 +182,17 @@ hipError_t launch_mask_bf16(const bf16_t* dy, int ldd, const bf16_t* mask, int l
                             hipStream_t s);
 // add_noise: out = sa * x + sb * n   (fp32, n elements), coefficients from device memory {sa, sb}
 hipError_t launch_axpby(const float* x, const float* n, float* out, size_t count, const float* coef_dev, hipStream_t s);
+// Counter-based noise (rng.hip): Philox4x32-10, key = seed, counter = (j / 4, rng_stream, unit id lo, unit id hi) for element j of a
+// unit; up to DD_RNG_UNITS unit ids travel in the kernel arguments (nothing of the caller's is referenced after the launch).
+//   launch_philox_units    : out [count, n_per_unit] = the values of `rng_stream` (0, 1, 3: N(0,1) by Box-Muller; 2: U[0,1))
+//   launch_philox_add_noise: out [count, C, HW] = sa * x + sb * (n + 0.1 * o_c) with n from stream 0 and, when offset_noise, o_c from
+//                            stream 1 at channel c; coef_dev = {sa, sb} as launch_axpby -- bit for bit what launch_axpby gives on the
+//                            tensors of launch_philox_units
+#define DD_RNG_UNITS 16
+struct RngUnits { unsigned lo[DD_RNG_UNITS], hi[DD_RNG_UNITS]; };
+hipError_t launch_philox_units(const RngUnits& ids, int count, uint64_t seed, int rng_stream, int64_t n_per_unit, float* out, hipStream_t s);
+hipError_t launch_philox_add_noise(const RngUnits& ids, int count, uint64_t seed, const float* x, float* out, int C, int HW, int offset_noise,
+                                   const float* coef_dev, hipStream_t s);
 // 2x2 sum pooling of NHWC bf16 (backward of the fused nearest-2x upsample): [B,2H,2W,C] -> [B,H,W,C]
 hipError_t launch_sumpool2x2(const bf16_t* src, int src_ld, bf16_t* dst, int dst_ld, int B, int H, int W, int C,
                              int accumulate, hipStream_t s);

@@ -47,7 +47,8 @@ class DDSamplerParams(C.Structure):
 class DDExpandArgs(C.Structure):
     _fields_ = [("image_latents", vp), ("noise", vp), ("e", vp), ("b", vp), ("targets", vp), ("B", C.c_int),
                 ("start_index", C.c_int), ("guidance_type", C.c_int), ("guide_first", C.c_int), ("guide_count", C.c_int),
-                ("z_out", vp), ("image_out", vp), ("score_out", vp)]
+                ("z_out", vp), ("image_out", vp), ("score_out", vp),
+                ("seed", C.c_uint64), ("unit_ids", vp), ("noise_mode", C.c_int), ("offset_noise", C.c_int), ("text_to_img", C.c_int)]
 
 
 def _declare(l):
@@ -75,6 +76,7 @@ def _declare(l):
     l.dd_direct_guidance.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, i, vp]
     l.dd_decode.argtypes = [vp, vp, vp, i, i, vp]
     l.dd_expand.argtypes = [vp, C.POINTER(DDExpandArgs), vp]
+    l.dd_randn_units.argtypes = [vp, C.c_uint64, i, vp, i, C.c_int64, vp, vp]
     l.dd_guide_encode.argtypes = [vp, vp, vp, i, vp]
     l.dd_guide_encode_pooled.argtypes = [vp, vp, vp, i, i, vp]
     l.dd_vae_encode.argtypes = [vp, vp, vp, vp, vp, i, vp]
@@ -405,15 +407,33 @@ class Engine:
         self._chk(self.L.dd_guide_encode_pooled(self._h, _p(x), _p(f), x.shape[0], int(pooling == "max"), _stream()), "dd_guide_encode")
         return f
 
-    def expand(self, image_latents, noise, e, b, targets, start_index, guidance_type, guide_first, guide_count, want_image=True):
-        """guidance_type: None | 'transform_guidance' | 'direct_guidance' (generate_data.py:1203-1218)."""
-        lat, nz = self._f(image_latents), self._f(noise)
-        B = lat.shape[0]
+    def randn_units(self, seed, stream, unit_ids, n):
+        """The counter-based generator of `expand(seed=...)` on its own (dd_randn_units): device fp32 [len(unit_ids), n], row k a function
+        of (seed, stream, unit_ids[k]) alone.  stream 0 initial noise, 1 offset noise (unscaled), 3 b: N(0,1); 2 e: U[0,1)."""
+        ids = np.ascontiguousarray(np.asarray(unit_ids, dtype=np.uint64).reshape(-1))
+        out = torch.empty((len(ids), int(n)), device=self.device, dtype=torch.float32)
+        self._chk(self.L.dd_randn_units(self._h, int(seed) & (2 ** 64 - 1), int(stream), ids.ctypes.data_as(vp), len(ids), int(n), _p(out),
+                                        _stream()), "dd_randn_units")
+        return out
+
+    def expand(self, image_latents, noise, e, b, targets, start_index, guidance_type, guide_first, guide_count, want_image=True,
+               seed=None, unit_ids=None, offset_noise=False, text_to_img=False):
+        """guidance_type: None | 'transform_guidance' | 'direct_guidance' (generate_data.py:1203-1218).
+        seed + unit_ids [B]: the initial noise, the offset noise (offset_noise=True), e and b of row k are generated on the device from
+        (seed, unit_ids[k]) alone (`randn_units`); `noise`, `e`, `b` are then not read and may be None.
+        text_to_img: the loop starts from the noise itself and runs the whole schedule (start_index must be 0); image_latents may be None."""
+        generated = seed is not None or unit_ids is not None
+        if generated and (seed is None or unit_ids is None):
+            raise ValueError("expand: seed and unit_ids go together")
+        B = self.B if image_latents is None else image_latents.shape[0]
+        L = self.cfg.latent_size
+        lat = self._f(image_latents) if image_latents is not None else None
+        nz = self._f(noise) if noise is not None else None
         e = self._f(e).reshape(-1) if e is not None else torch.zeros(B * 4, device=self.device)
         b = self._f(b).reshape(-1) if b is not None else torch.zeros(B * 4, device=self.device)
         tg = targets.to(self.device, torch.int32).contiguous()
         a = DDExpandArgs()
-        z_out = torch.empty_like(lat)
+        z_out = torch.empty((B, self.cfg.unet.in_channels, L, L), device=self.device, dtype=torch.float32)
         L8 = self.cfg.latent_size * 8
         img = torch.empty((B, 3, L8, L8), device=self.device) if want_image else None
         score = torch.zeros(1, device=self.device)
@@ -422,6 +442,13 @@ class Engine:
         a.guidance_type = {None: 0, "": 0, "transform_guidance": 1, "direct_guidance": 2}[guidance_type]
         a.guide_first, a.guide_count = guide_first, guide_count
         a.z_out, a.image_out, a.score_out = _p(z_out), _p(img), _p(score)
+        if generated:
+            ids = np.ascontiguousarray(np.asarray(unit_ids, dtype=np.uint64).reshape(-1))
+            if len(ids) != B:
+                raise ValueError("expand: %d unit ids for a batch of %d" % (len(ids), B))
+            a.seed, a.unit_ids, a.noise_mode = int(seed) & (2 ** 64 - 1), ids.ctypes.data_as(vp), 1     # host array, read during the call
+            a.offset_noise = int(bool(offset_noise))
+        a.text_to_img = int(bool(text_to_img))
         self._chk(self.L.dd_expand(self._h, C.byref(a), _stream()), "dd_expand")
         return z_out, img, score
 

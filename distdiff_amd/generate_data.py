@@ -18,6 +18,14 @@ rank 0 loads and packs the weights once and broadcasts the packed device buffers
 Random streams: `e`/`b` of transform_guidance come from the CPU global generator in the reference's order (one draw of each per
 reference batch, :692-694); the initial noise comes from a dedicated generator seeded with --seed (the reference draws it from the
 CUDA global generator, whose stream no other device reproduces) -- see INTEGRATION.md.
+`--noise_rng philox` (default `stream`, the paragraph above) makes the image of a given (--seed, train image, expand index) independent
+of how the run is packed: the initial noise, the offset noise and `e`/`b` are generated on the device by a counter-based generator
+(Philox4x32-10) keyed by --seed and counted by `unit_id(index in the full train listing, expand index)`, so --engine_batch, a resumed
+run, --first_image_index and --gpus / --split no longer change them.  In this mode `e`/`b` do NOT follow the reference's CPU stream
+draw for draw: one draw per reference batch, in loop order, is exactly the order dependence this mode removes.
+`--text_to_img` runs what the reference's branch intends (:1150-1158; there it fails on `generator` used before assignment, :1155 vs
+:1194, and on `start_index` never being set): the loop starts from randn * init_noise_sigma (1 for DDIM) at the first timestep whatever
+--strength says, guidance as usual; image latents are not needed, so the latent cache / VAE encoder stage is skipped.
 The stage before the loop runs on the engine too: image latents come from the reference's cache
 `save/vae_embedding/<dataset>/<model>/image_latents.pt` when it exists and are otherwise produced by the HIP VAE encoder and
 written to that path in the same format (dataloader.py:788-811); class prompts go through the Hugging Face tokenizer of the
@@ -105,13 +113,14 @@ def parse_args(argv=None):
     p.add_argument("--gpus", type=int, default=1, help="spawn this many ranks (one per GPU) that shard the images like --total_split; "
                    "weights are loaded once on rank 0 and broadcast over RCCL")
     p.add_argument("--device", type=str, default=None)
+    p.add_argument("--noise_rng", default="stream", choices=["stream", "philox"],
+                   help="stream: initial noise / e / b drawn sequentially on the host, one draw per batch (the reference's scheme: the noise of an image "
+                   "depends on --engine_batch, resumes, --first_image_index and the shard).  philox: generated on the device from (--seed, index in the "
+                   "train listing, expand index) alone, so the same unit gets the same noise however the run is packed")
     args = p.parse_args(argv)
     env_local_rank = int(os.environ.get("LOCAL_RANK", -1))
     if env_local_rank != -1:
         args.local_rank = env_local_rank
-    if args.text_to_img:
-        raise SystemExit("--text_to_img is broken in the reference (generate_data.py:1155 uses `generator` before assignment) and is "
-                         "out of scope")
     if not args.do_classifier_free_guidance:
         raise SystemExit("the engine always runs classifier-free guidance (the reference's type=bool flag cannot be switched off either)")
     return args
@@ -130,7 +139,7 @@ class ExpansionDataset:
         self.class_pooled, self.uncond_pooled = class_pooled, uncond_pooled
 
     def __len__(self):
-        return self.latents.shape[0]
+        return len(self.targets)             # latents is None for --text_to_img on a real dataset (no image is encoded)
 
     @staticmethod
     def synthetic(cfg, n, n_classes, seed):
@@ -157,9 +166,11 @@ class ExpansionDataset:
         paths, targets, names = load_train_listing(args.dataset, args.data_root)
         # image latents: the reference's cache file if present (validated against this listing), else the HIP VAE encoder fills it
         # (dataloader.py:788-796).  center_crop=False: the reference hard-codes it for SDDataset (generate_data.py:1001).
-        lat = load_or_encode_latents(eng, args.dataset, args.pretrained_model_name_or_path, paths, args.resolution,
-                                     center_crop=False, seed=args.seed or 0)
-        lat = torch.cat([x.float().cpu() for x in lat], dim=0)
+        lat = None                           # --text_to_img starts from noise: no latent cache, no VAE encoder pass
+        if not args.text_to_img:
+            lat = load_or_encode_latents(eng, args.dataset, args.pretrained_model_name_or_path, paths, args.resolution,
+                                         center_crop=False, seed=args.seed or 0)
+            lat = torch.cat([x.float().cpu() for x in lat], dim=0)
         # class prompts + the empty prompt through the HIP CLIP text encoder (dataloader.py:766-786)
         tokenizer = load_tokenizer(args.pretrained_model_name_or_path, args.revision)
         if cfg.text2 is not None:
@@ -203,6 +214,15 @@ def output_path(output_dir, class_name, image_path, image_i):
     """generate_data.py:1134-1135 / 1231-1232."""
     stem = os.path.basename(image_path).split(".")[0]
     return "%s/%s/%s_expand_%d.png" % (output_dir, class_name, stem, image_i)
+
+
+def unit_id(i, image_i):
+    """Counter of one unit of work for --noise_rng philox: (index of the train image in the FULL listing, before sharding) << 32 |
+    expand index.  Injective for both below 2^32; nothing about the batch, the shard or the resume state enters it."""
+    i, image_i = int(i), int(image_i)
+    if not (0 <= i < 1 << 32 and 0 <= image_i < 1 << 32):
+        raise ValueError("unit_id: index %d / expand index %d out of range" % (i, image_i))
+    return (i << 32) | image_i
 
 
 def save_png(img, path):
@@ -314,6 +334,11 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
     ts = sched.timesteps
     n = len(ts)
     si = start_index(args.strength, n)
+    philox, t2i = getattr(args, "noise_rng", "stream") == "philox", bool(getattr(args, "text_to_img", False))
+    if t2i:
+        log.info("--text_to_img: the loop starts from noise at t=%d (start index 0; --strength %s does not apply%s)", ts[0], args.strength,
+                 ", nor does --offset_noise" if args.offset_noise else "")
+        si = 0
     gfirst, gcount = (0, 0)
     if args.guidance_type:
         gfirst, gcount = guide_window(n, args.guidance_step, args.guidance_period)
@@ -331,16 +356,24 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
     EB = engine.B
     transform = args.guidance_type == "transform_guidance"
     noise_gen = torch.Generator(device=rng_device)
+    seed = args.seed
     if args.seed is None:
         # no seed (programmatic callers; the CLI's default is the reference's 42, generate_data.py:370): fresh noise per run, like the
         # reference's unseeded global generator, and logged so that the run can be repeated
-        log.info("initial-noise generator seed: %d", noise_gen.seed())
+        seed = noise_gen.seed()
+        log.info("initial-noise generator seed: %d", seed)
     else:
         # the reference seeds its global generators once per process with --seed (set_seed, :859-861), so every invocation -- a resumed
         # run, a later --first_image_index -- replays the same noise stream from its first unit; kept as is
         noise_gen.manual_seed(int(args.seed))
-    Cl = ds.latents.shape[1]
-    units = []      # (dataset index, path, group id, group size, e[4], b[4], prompt embedding, noise offset[C] or None)
+    if ds.latents is not None:
+        lat_shape = tuple(ds.latents.shape[1:])
+    else:
+        lat_shape = (engine.cfg.unet.in_channels, engine.cfg.latent_size, engine.cfg.latent_size)
+    Cl = lat_shape[0]
+    offset_noise = args.offset_noise and not t2i                          # the reference's text-to-image branch has no offset noise
+    # --noise_rng philox: nothing is drawn on the host; every unit carries its counter and the engine generates noise, offset, e and b
+    units = []      # (dataset index, path, group id, group size, e[4], b[4], prompt embedding, noise offset[C] or None, unit id)
     n_groups = 0
     for s0 in range(0, len(idx), B):
         bidx = idx[s0:s0 + B]
@@ -353,14 +386,14 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
                 continue
             nb = len(bidx)
             # :1164-1168: noise += 0.1 * randn(b, c, 1, 1)
-            off = 0.1 * torch.randn(nb, Cl, 1, 1, generator=noise_gen, device=rng_device).cpu() if args.offset_noise else None
-            if transform:
+            off = 0.1 * torch.randn(nb, Cl, 1, 1, generator=noise_gen, device=rng_device).cpu() if offset_noise and not philox else None
+            if transform and not philox:
                 e = torch.rand([nb, 4, 1, 1])                                 # :692 CPU global RNG, one draw per reference batch
                 b = torch.zeros([nb, 4, 1, 1]).normal_(0, 1)                  # :694
             else:
                 e = b = torch.zeros([nb, 4, 1, 1])
             for k, (i, p) in enumerate(zip(bidx, paths)):
-                units.append((i, p, n_groups, nb, e[k], b[k], prompts[k], off[k] if off is not None else None))
+                units.append((i, p, n_groups, nb, e[k], b[k], prompts[k], off[k] if off is not None else None, unit_id(i, image_i)))
             n_groups += 1
     group_scores = {}
     for u0 in range(0, len(units), EB):
@@ -369,11 +402,13 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
         chunk_p = chunk + [chunk[-1]] * (EB - nb)                           # ragged last batch: pad to the static batch
         pad = [u[0] for u in chunk_p]
         paths = [u[1] for u in chunk]
-        lat = ds.latents[pad]
+        lat = ds.latents[pad] if not t2i else None
         tg = ds.targets[pad]
-        noise = torch.randn(lat.shape, generator=noise_gen, device=rng_device).to(lat.dtype).cpu()      # :1170
-        if args.offset_noise:
-            noise = noise + torch.stack([u[7] for u in chunk_p])
+        noise = None
+        if not philox:
+            noise = torch.randn((EB,) + lat_shape, generator=noise_gen, device=rng_device).to(ds.uncond.dtype if lat is None else lat.dtype).cpu()      # :1170
+            if offset_noise:
+                noise = noise + torch.stack([u[7] for u in chunk_p])
         e = torch.stack([u[4] for u in chunk_p])
         b = torch.stack([u[5] for u in chunk_p])
         emb = torch.cat([ds.uncond.expand(EB, -1, -1), torch.stack([u[6] for u in chunk_p])])   # cat[negative, prompt], :1184
@@ -381,12 +416,18 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
         if ds.class_pooled is not None:
             # SDXL added_cond_kwargs (StableDiffusionXLPipeline.__call__): pooled text embeddings cat[negative, prompt] and
             # add_time_ids = (original size, crop top-left, target size), the same for both halves
-            S = float(8 * ds.latents.shape[-1])
+            S = float(8 * lat_shape[-1])
             pooled = torch.cat([ds.uncond_pooled.expand(EB, -1), ds.class_pooled[tg]])
             engine.set_added_cond(pooled.to(dev), torch.tensor([[S, S, 0.0, 0.0, S, S]]).expand(2 * EB, -1).to(dev))
         if args.guidance_type and hasattr(engine, "set_sample_weights"):
             engine.set_sample_weights([1.0 / u[3] for u in chunk] + [0.0] * (EB - nb))
-        z, img, score = engine.expand(lat, noise, e, b, tg, si, args.guidance_type or None, gfirst, gcount, want_image=True)
+        if not (philox or t2i):
+            z, img, score = engine.expand(lat, noise, e, b, tg, si, args.guidance_type or None, gfirst, gcount, want_image=True)
+        else:
+            kw = dict(seed=int(seed), unit_ids=[u[8] for u in chunk_p], offset_noise=offset_noise) if philox else {}
+            if t2i:
+                kw["text_to_img"] = True
+            z, img, score = engine.expand(lat, noise, e, b, tg, si, args.guidance_type or None, gfirst, gcount, want_image=True, **kw)
 
         def log_scores(per_image, chunk=chunk):
             for u, sc in zip(chunk, per_image):

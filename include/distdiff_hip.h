@@ -46,9 +46,10 @@ enum dd_status { DD_OK = 0, DD_ERR_ARG = -1, DD_ERR_HIP = -2, DD_ERR_STATE = -3,
 /* Layout version of the structs and argument lists of this header and distdiff_hip_ops.h.  A caller sets dd_config.abi_version =
  * DD_ABI_VERSION (after zero-initialising the struct: every struct of this ABI must be zero-initialised, new fields are appended and
  * mean "off" at 0); dd_create refuses another value with DD_ERR_ARG, and dd_abi_version() tells what the loaded library was built
- * as.  6: dd_config gained unet_attn_fp8 + abi_version, AttnParams gained no_shortk; 5 (unversioned): workspace_bytes in the dd_op_attention_gemm_* lists,
+ * as.  7: dd_expand_args gained seed / unit_ids / noise_mode / offset_noise / text_to_img (all 0 = the call of version 6), dd_randn_units
+ * is new; 6: dd_config gained unet_attn_fp8 + abi_version, AttnParams gained no_shortk; 5 (unversioned): workspace_bytes in the dd_op_attention_gemm_* lists,
  * ConvGemmParams.wgroup_rows / wgroup_elems, AttnParams.pv_fp8. */
-#define DD_ABI_VERSION 6
+#define DD_ABI_VERSION 7
 
 typedef struct dd_config {
   /* UNet2DConditionModel (unet/config.json) */
@@ -127,6 +128,15 @@ typedef struct dd_expand_args {
   float* z_out;               /* [B,4,L,L] final latents */
   float* image_out;           /* [B,3,8L,8L] in [0,1] (may be NULL) */
   float* score_out;           /* [1] device scalar: last guidance score (may be NULL) */
+  /* version 7, all 0 = the call as above.  With noise_mode 1 the initial noise, the offset noise, e and b of image i are generated on
+   * the device from (seed, unit_ids[i]) alone (counter layout: dd_randn_units), so they do not depend on the row, the batch or the
+   * call; `noise`, `e` and `b` are not read and may be NULL. */
+  uint64_t seed;              /* Philox key */
+  const uint64_t* unit_ids;   /* HOST [B], read before the call returns (noise_mode 1) */
+  int noise_mode;             /* 0: noise / e / b are read; 1: generated from (seed, unit id) */
+  int offset_noise;           /* noise_mode 1: noise += 0.1 * N(0,1) per (image, channel), generate_data.py:1164-1168 */
+  int text_to_img;            /* 1: the loop starts from the noise itself (init_noise_sigma = 1, :1150-1158): image_latents may be NULL,
+                                 start_index must be 0 (else DD_ERR_ARG), offset_noise is not applied */
 } dd_expand_args;
 
 int dd_abi_version(void);                     /* DD_ABI_VERSION the library was built with */
@@ -170,6 +180,13 @@ int dd_direct_guidance(dd_engine* e, const float* z, const int* targets, int ste
                        float* score_out, float* grad_z_out, int B, void* stream);
 int dd_decode(dd_engine* e, const float* z, float* image_out, int denormalize, int B, void* stream);
 int dd_expand(dd_engine* e, const dd_expand_args* a, void* stream);
+/* The counter-based generator of dd_expand's noise_mode 1 on its own: out DEVICE fp32 [B, n_per_unit].  Philox4x32-10 (Salmon et al.,
+ * Random123), key = (seed lo, seed hi), counter = (j / 4, rng_stream, unit id lo, unit id hi) for element j of a unit: one 128-bit
+ * block (words w0..w3) per 4 outputs.  Normals by Box-Muller from the word pairs (w0, w1) and (w2, w3): u1 = (wa + 0.5) 2^-32,
+ * u2 = (wb + 0.5) 2^-32, r = sqrt(-2 ln u1) -> r cos(2 pi u2), r sin(2 pi u2).  rng_stream: 0 initial noise [C,L,L], 1 offset noise
+ * [C] (unscaled), 3 b [4] -- N(0,1); 2 e [4] -- uniform (w >> 8) 2^-24 in [0,1).  unit_ids: HOST [B], read before the call returns. */
+int dd_randn_units(dd_engine* e, uint64_t seed, int rng_stream, const uint64_t* unit_ids, int B, int64_t n_per_unit, float* out,
+                   void* stream);
 /* The reference's energy is a `.mean()` over ITS batch (train_batch_size images: generate_data.py:709, :716, :751, :758), so each
  * image's gradient carries 1/train_batch_size.  A caller that packs several reference batches into one engine batch passes
  * w[i] = 1 / |reference batch of image i| (0 for padding rows): HOST float[B], or NULL to return to the default 1/B.  Applies to
