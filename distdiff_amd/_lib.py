@@ -93,12 +93,16 @@ CF_LNFOLD, CF_ROWSTATS = 1024, 2048
 
 # every symbol declared in include/distdiff_hip_ops.h and include/distdiff_hip.h (checked by tests/test_abi.py)
 OPS_SYMBOLS = [
-    "dd_op_conv_gemm", "dd_op_conv_gemm_kind", "dd_op_conv_gemm_check", "dd_op_groupnorm_fwd", "dd_op_groupnorm_bwd", "dd_op_groupnorm_scratch_bytes",
+    "dd_op_conv_gemm", "dd_op_conv_gemm_kind", "dd_op_conv_gemm_plan", "dd_op_conv_gemm_check", "dd_op_groupnorm_fwd", "dd_op_groupnorm_bwd", "dd_op_groupnorm_scratch_bytes",
     "dd_op_layernorm_fwd", "dd_op_layernorm_bwd", "dd_op_attention_fwd", "dd_op_attention_bwd",
     "dd_op_attention_gemm_workspace", "dd_op_attention_gemm_fwd", "dd_op_attention_gemm_bwd",
     "dd_pack_conv_weight", "dd_op_conv_f32", "dd_pack_conv_weight_f32", "dd_op_nchw_f32_to_nhwc_bf16", "dd_op_nhwc_to_nchw_f32", "dd_op_cfg_ddim",
     "dd_op_cfg_ddim_bwd", "dd_op_sumpool2x2", "dd_op_geglu_bwd", "dd_op_maxpool3x3s2", "dd_op_maxpool3x3s2_bwd",
     "dd_op_bicubic", "dd_op_bicubic_bwd", "dd_op_gap", "dd_op_energy", "dd_op_transform_update", "dd_op_affine",
+    "dd_op_mask_bf16", "dd_op_add_bf16", "dd_op_copy_bf16", "dd_op_dup_bwd", "dd_op_gap_bwd", "dd_op_act_bf16", "dd_op_act_bwd_bf16",
+    "dd_op_patchify", "dd_op_patchify_bwd", "dd_op_vit_embed", "dd_op_vit_embed_bwd", "dd_op_select_rows", "dd_op_select_rows_bwd",
+    "dd_op_sub_scaled", "dd_op_energy_weighted", "dd_op_mask_f32", "dd_op_add_f32", "dd_op_copy_f32", "dd_op_maxpool3x3s2_f32",
+    "dd_op_maxpool3x3s2_bwd_f32", "dd_op_bicubic_f32", "dd_op_bicubic_bwd_f32", "dd_op_gap_f32", "dd_op_gap_bwd_f32", "dd_op_nchw_to_nhwc_f32",
     "dd_debug_tensor", "dd_debug_num_tensors", "dd_debug_set_image", "dd_debug_set_images",
 ]
 ENGINE_SYMBOLS = [
@@ -113,6 +117,7 @@ def _declare(l):
     i, f, sz = C.c_int, C.c_float, C.c_size_t
     l.dd_op_conv_gemm.argtypes = [C.POINTER(ConvGemmParams), sz, vp]
     l.dd_op_conv_gemm_kind.argtypes = [C.POINTER(ConvGemmParams), sz]
+    l.dd_op_conv_gemm_plan.argtypes = [C.POINTER(ConvGemmParams), sz, vp]
     l.dd_op_conv_gemm_check.argtypes = [C.POINTER(ConvGemmParams), vp]
     l.dd_op_groupnorm_fwd.argtypes = [C.POINTER(GroupNormParams), vp]
     l.dd_op_groupnorm_bwd.argtypes = [C.POINTER(GroupNormParams), vp]
@@ -139,6 +144,31 @@ def _declare(l):
     l.dd_op_energy.argtypes = [vp, vp, vp, vp, i, i, i, f, f, i, i, i, f, vp, vp, vp]
     l.dd_op_transform_update.argtypes = [vp, vp, vp, vp, vp, i, i, f, f, vp]
     l.dd_op_affine.argtypes = [vp, vp, vp, vp, i, i, vp]
+    l.dd_op_mask_bf16.argtypes = [vp, i, vp, i, vp, i, i, i, vp]
+    l.dd_op_add_bf16.argtypes = [vp, i, vp, i, vp, i, i, i, vp]
+    l.dd_op_copy_bf16.argtypes = [vp, i, vp, i, i, i, vp]
+    l.dd_op_dup_bwd.argtypes = [vp, i, vp, i, i, i, i, i, vp]
+    l.dd_op_gap_bwd.argtypes = [vp, vp, i, i, i, i, vp, i, vp]
+    l.dd_op_act_bf16.argtypes = [vp, i, vp, i, i, i, i, vp]
+    l.dd_op_act_bwd_bf16.argtypes = [vp, i, vp, i, vp, i, i, i, i, i, vp]
+    l.dd_op_patchify.argtypes = [vp, i, vp, i, i, i, i, vp]
+    l.dd_op_patchify_bwd.argtypes = [vp, vp, i, i, i, i, i, vp]
+    l.dd_op_vit_embed.argtypes = [vp, i, vp, vp, vp, i, i, i, i, vp]
+    l.dd_op_vit_embed_bwd.argtypes = [vp, i, vp, i, i, i, i, vp]
+    l.dd_op_select_rows.argtypes = [vp, i, vp, i, i, i, i, vp]
+    l.dd_op_select_rows_bwd.argtypes = [vp, i, vp, i, i, i, i, i, vp]
+    l.dd_op_sub_scaled.argtypes = [vp, vp, vp, sz, f, vp]
+    l.dd_op_energy_weighted.argtypes = [vp, vp, vp, vp, i, i, i, f, f, i, i, i, f, vp, vp, vp, vp, vp]
+    l.dd_op_mask_f32.argtypes = [vp, i, vp, i, vp, i, i, i, f, vp]
+    l.dd_op_add_f32.argtypes = [vp, i, vp, i, vp, i, i, i, vp]
+    l.dd_op_copy_f32.argtypes = [vp, i, vp, i, i, i, vp]
+    l.dd_op_maxpool3x3s2_f32.argtypes = [vp, vp, i, i, i, i, vp]
+    l.dd_op_maxpool3x3s2_bwd_f32.argtypes = [vp, vp, vp, i, i, i, i, vp]
+    l.dd_op_bicubic_f32.argtypes = [vp, i, vp, i, i, i, i, i, i, i, i, vp]
+    l.dd_op_bicubic_bwd_f32.argtypes = [vp, i, vp, i, i, i, i, i, i, i, i, vp]
+    l.dd_op_gap_f32.argtypes = [vp, i, vp, vp, i, i, i, i, vp]
+    l.dd_op_gap_bwd_f32.argtypes = [vp, vp, i, i, i, i, vp, vp]
+    l.dd_op_nchw_to_nhwc_f32.argtypes = [vp, vp, i, i, i, i, i, i, vp]
     if hasattr(l, "dd_create"):
         from . import engine as _engine  # noqa: F401  (declares the engine prototypes)
         _engine._declare(l)

@@ -387,9 +387,9 @@ int conv_halo_kernel_kind(const ConvGemmParams& p, int tn);   // conv_halo.hip: 
 // The launcher's decision, in one place: launch_conv_gemm acts on it, conv_gemm_kind reports it.  On return p is the problem as the chosen
 // kernel gets it (ksplit set; partial dropped when the 8 x 8 chunk split does not fit the scratch).
 enum { PLAN_GENERAL = 0, PLAN_HALO = 1, PLAN_WS = 3, PLAN_PPS = 4, PLAN_EMPTY = 5, PLAN_GROUPED = 6 };
-struct ConvPlan { int path, tn, cfg, split; };
+struct ConvPlan { int path, tn, cfg, split, narrow; };   // narrow: the small kernel's 256 x 64 tiles instead of 128 x 128
 static hipError_t conv_gemm_plan(ConvGemmParams& p, size_t partial_cap_bytes, ConvPlan* pl) {
-  pl->path = PLAN_EMPTY; pl->tn = 0; pl->cfg = 0; pl->split = 1;
+  pl->path = PLAN_EMPTY; pl->tn = 0; pl->cfg = 0; pl->split = 1; pl->narrow = 0;
   if (p.K & 63) return hipErrorInvalidValue;
   if ((p.flags & CF_LNFOLD) && (!p.ln_stats || !p.ln_c1 || p.ntaps != 1)) return hipErrorInvalidValue;
   if (p.flags & CF_ROWSTATS) {
@@ -427,6 +427,7 @@ static hipError_t conv_gemm_plan(ConvGemmParams& p, size_t partial_cap_bytes, Co
   if (const int tn = gemm_pp_config(p)) { pl->path = PLAN_PPS; pl->tn = tn; return hipSuccess; }    // narrow pointwise layers: ping-pong GEMM
   select_config(p, partial_cap_bytes, &pl->cfg, &pl->split);
   p.ksplit = pl->split;
+  pl->narrow = (!pl->cfg && (p.N % 128) != 0 && (p.N % 128) <= 64 && p.M >= 256) ? 1 : 0;
   pl->path = PLAN_GENERAL;
   return hipSuccess;
 }
@@ -438,6 +439,18 @@ int conv_gemm_kind(ConvGemmParams p, size_t partial_cap_bytes) {
   if (conv_gemm_plan(p, partial_cap_bytes, &pl) != hipSuccess) return -1;
   if (pl.path == PLAN_HALO) { const int k = conv_halo_kernel_kind(p, pl.tn); return k ? k : -1; }
   return pl.path == PLAN_WS || pl.path == PLAN_PPS ? pl.path : 0;
+}
+
+// conv_gemm_kind plus the form inside the kind: out4 = {kind, configuration of conv_gemm_big_kernel (0: conv_gemm_kernel; 1 128 x 256,
+// 2 256 x 160, 3 256 x 128 on 8 waves; 4 128 x 160, 5 128 x 128 as two 4-wave workgroups), split-K / chunk split the launch uses,
+// 1 when conv_gemm_kernel runs its 256 x 64 tiles instead of 128 x 128}
+int conv_gemm_plan_query(ConvGemmParams p, size_t partial_cap_bytes, int* out4) {
+  ConvPlan pl;
+  if (conv_gemm_plan(p, partial_cap_bytes, &pl) != hipSuccess) return -1;
+  int kind = pl.path == PLAN_WS || pl.path == PLAN_PPS ? pl.path : 0;
+  if (pl.path == PLAN_HALO) { kind = conv_halo_kernel_kind(p, pl.tn); if (!kind) return -1; }
+  if (out4) { out4[0] = kind; out4[1] = pl.cfg; out4[2] = pl.path == PLAN_HALO ? (p.ksplit > 1 ? p.ksplit : 1) : pl.split; out4[3] = pl.narrow; }
+  return kind;
 }
 
 hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStream_t stream) {
@@ -479,8 +492,7 @@ hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStrea
     hipFuncSetAttribute((const void*)conv_gemm_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 128) * 128);
     attr_done = true;
   }
-  const bool narrow = ((p.N % 128) != 0 && (p.N % 128) <= 64) && p.M >= 256;
-  if (narrow) {
+  if (pl.narrow) {
     const int ntm = (p.M + 255) / 256, ntn = (p.N + 63) / 64;
     dim3 grid(ntm * ntn, split);
     hipLaunchKernelGGL((conv_gemm_kernel<4, 1>), grid, dim3(256), 2 * (256 + 64) * 128, stream, p);

@@ -649,6 +649,9 @@ __global__ void rows_bf16_to_f32_kernel(const bf16_t* x, int ld, float* y, int M
 }  // namespace
 
 #define LAUNCH(kern, n, ...) hipLaunchKernelGGL(kern, dim3(nblocks(n)), dim3(256), 0, s, __VA_ARGS__); return hipGetLastError()
+// The 8-wide bf16 row kernels move whole uint4 vectors: a channel count that is not a multiple of 8 would lose its tail, a row stride
+// that is not would misalign the 16-byte accesses.  Refused on the host, in front of any launch.
+#define VEC8(...) do { const int _v[] = {__VA_ARGS__}; for (int _x : _v) if (_x & 7) return hipErrorInvalidValue; } while (0)
 
 hipError_t launch_nchw_f32_to_nhwc_bf16(const float* src, bf16_t* dst, int B, int C, int H, int W, int Cpad, int ld, int dup,
                                         float scale, hipStream_t s) {
@@ -674,26 +677,35 @@ hipError_t launch_axpby(const float* x, const float* n, float* out, size_t count
 }
 hipError_t launch_sumpool2x2(const bf16_t* src, int src_ld, bf16_t* dst, int dst_ld, int B, int H, int W, int C, int accumulate,
                              hipStream_t s) {
+  VEC8(C, src_ld, dst_ld);
   LAUNCH(sumpool_kernel, (size_t)B * H * W * (C / 8), src, src_ld, dst, dst_ld, B, H, W, C, accumulate);
 }
 hipError_t launch_add_bf16(const bf16_t* a, int lda, const bf16_t* b, int ldb, bf16_t* y, int ldy, int M, int C, hipStream_t s) {
+  VEC8(C, lda, b ? ldb : 0, ldy);
   LAUNCH(add_kernel, (size_t)M * (C / 8), a, lda, b, ldb, y, ldy, M, C);
 }
 hipError_t launch_copy_bf16(const bf16_t* a, int lda, bf16_t* y, int ldy, int M, int C, hipStream_t s) {
+  VEC8(C, lda, ldy);
   LAUNCH(add_kernel, (size_t)M * (C / 8), a, lda, (const bf16_t*)nullptr, 0, y, ldy, M, C);
 }
 hipError_t launch_mask_bf16(const bf16_t* dy, int ldd, const bf16_t* mask, int ldm, bf16_t* y, int ldy, int M, int C,
                             hipStream_t s) {
+  VEC8(C, ldd, ldm, ldy);
   LAUNCH(mask_kernel, (size_t)M * (C / 8), dy, ldd, mask, ldm, y, ldy, M, C);
 }
 hipError_t launch_geglu_bwd(const bf16_t* raw, int ld_raw, const bf16_t* dout, int ld_dout, bf16_t* draw, int ld_draw, int M,
                             int F, hipStream_t s) {
+  VEC8(F, ld_raw, ld_dout, ld_draw);
   LAUNCH(geglu_bwd_kernel, (size_t)M * (F / 8), raw, ld_raw, dout, ld_dout, draw, ld_draw, M, F);
 }
 hipError_t launch_maxpool3x3s2(const bf16_t* x, bf16_t* y, int B, int H, int W, int C, hipStream_t s) {
+  VEC8(C);
+  if ((H | W) & 1) return hipErrorInvalidValue;      // the kernels pool to H / 2 x W / 2: torch's (H - 1) / 2 + 1 for even sizes only
   LAUNCH(maxpool_kernel, (size_t)B * (H / 2) * (W / 2) * (C / 8), x, y, B, H, W, C);
 }
 hipError_t launch_maxpool3x3s2_bwd(const bf16_t* x, const bf16_t* dy, bf16_t* dx, int B, int H, int W, int C, hipStream_t s) {
+  VEC8(C);
+  if ((H | W) & 1) return hipErrorInvalidValue;
   LAUNCH(maxpool_bwd_kernel, (size_t)B * H * W * (C / 8), x, dy, dx, B, H, W, C);
 }
 hipError_t launch_bicubic(const bf16_t* src, int ld_s, bf16_t* dst, int ld_d, int B, int Hs, int Ws, int Hd, int Wd, int C,

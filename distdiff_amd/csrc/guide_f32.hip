@@ -425,6 +425,8 @@ __global__ void nchw_to_nhwc_f32_kernel(const float* src, float* dst, int B, int
 }  // namespace
 
 #define LAUNCH(kern, n, ...) hipLaunchKernelGGL(kern, dim3(nblocks(n)), dim3(256), 0, s, __VA_ARGS__); return hipGetLastError()
+// the 4-wide fp32 row kernels move whole float4 vectors: channel counts and row strides must be multiples of 4 (refused on the host)
+#define VEC4(...) do { const int _v[] = {__VA_ARGS__}; for (int _x : _v) if (_x & 3) return hipErrorInvalidValue; } while (0)
 
 hipError_t launch_conv_f32(const ConvF32Params& p, hipStream_t s) {
   if ((p.K & 15) || (p.cin & 3) || (p.x_ld & 3)) return hipErrorInvalidValue;
@@ -441,18 +443,25 @@ hipError_t launch_conv_f32(const ConvF32Params& p, hipStream_t s) {
   return hipGetLastError();
 }
 hipError_t launch_add_f32(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int M, int C, hipStream_t s) {
+  VEC4(C, lda, b ? ldb : 0, ldy);
   LAUNCH(add_f32_kernel, (size_t)M * (C / 4), a, lda, b, ldb, y, ldy, M, C);
 }
 hipError_t launch_copy_f32(const float* a, int lda, float* y, int ldy, int M, int C, hipStream_t s) {
+  VEC4(C, lda, ldy);
   LAUNCH(add_f32_kernel, (size_t)M * (C / 4), a, lda, (const float*)nullptr, 0, y, ldy, M, C);
 }
 hipError_t launch_mask_f32(const float* dy, int ldd, const float* mask, int ldm, float* y, int ldy, int M, int C, float hi, hipStream_t s) {
+  VEC4(C, ldd, ldm, ldy);
   LAUNCH(mask_f32_kernel, (size_t)M * (C / 4), dy, ldd, mask, ldm, y, ldy, M, C, hi > 0.f ? hi : INFINITY);
 }
 hipError_t launch_maxpool3x3s2_f32(const float* x, float* y, int B, int H, int W, int C, hipStream_t s) {
+  VEC4(C);
+  if ((H | W) & 1) return hipErrorInvalidValue;      // pools to H / 2 x W / 2: torch's (H - 1) / 2 + 1 for even sizes only
   LAUNCH(maxpool_f32_kernel, (size_t)B * (H / 2) * (W / 2) * (C / 4), x, y, B, H, W, C);
 }
 hipError_t launch_maxpool3x3s2_bwd_f32(const float* x, const float* dy, float* dx, int B, int H, int W, int C, hipStream_t s) {
+  VEC4(C);
+  if ((H | W) & 1) return hipErrorInvalidValue;
   LAUNCH(maxpool_bwd_f32_kernel, (size_t)B * H * W * (C / 4), x, dy, dx, B, H, W, C);
 }
 hipError_t launch_bicubic_f32(const float* src, int ld_s, float* dst, int ld_d, int B, int Hs, int Ws, int Hd, int Wd, int C, int Cpad,

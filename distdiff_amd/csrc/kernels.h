@@ -72,6 +72,10 @@ hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStrea
 // kernels (conv_gemm_kernel / conv_gemm_big_kernel), 1 conv_halo_kernel, 2 conv_halo_persist_kernel, 3 gemm_ws_kernel, 4 gemm_pps_kernel;
 // -1 when the launcher would refuse the problem
 int conv_gemm_kind(ConvGemmParams p, size_t partial_cap_bytes);
+// The same decision with the form inside the kind: returns the kind and fills out4 = {kind, conv_gemm_big_kernel configuration (0: the
+// small conv_gemm_kernel; 1 128 x 256, 2 256 x 160, 3 256 x 128 on 8 waves; 4 128 x 160, 5 128 x 128 as two 4-wave workgroups per CU),
+// the split-K (8 x 8 halo level: chunk split) the launch uses, 1 when the small kernel runs 256 x 64 tiles instead of 128 x 128}
+int conv_gemm_plan_query(ConvGemmParams p, size_t partial_cap_bytes, int* out4);
 // Preferred split for a shape (used by the engine to size the workspace).
 int conv_gemm_pick_split(int M, int N, int K);
 // true iff launch_conv_gemm(p, partial_cap_bytes) will honour CF_STATS for this problem (persistent big-tile kernel, no split-K,
@@ -159,6 +163,10 @@ hipError_t launch_attention_gemm_bwd(const AttnParams& p, void* workspace, size_
 // ----------------------------------------------------------------------------------------------
 // K6/K7/K9/K10/K12: small HBM-bound kernels.
 // ----------------------------------------------------------------------------------------------
+// The vectorised bf16 row kernels (launch_add_bf16 / copy_bf16 / mask_bf16 / sumpool2x2 / geglu_bwd / maxpool3x3s2*) move uint4 vectors:
+// C (F) and every row stride must be multiples of 8, the max pools also need even H and W (they pool to H / 2 x W / 2); anything else is
+// hipErrorInvalidValue and nothing is launched.  Row base pointers must be 16-byte aligned (not checked: a column view has to start at
+// a multiple of 8 channels).
 // NCHW fp32 [B,C,H,W] -> NHWC bf16 [B*H*W, ld] (channels >= C zero-filled up to Cpad); dup copies
 // the batch twice (CFG: cat[z, z]).  scale multiplies.
 hipError_t launch_nchw_f32_to_nhwc_bf16(const float* src, bf16_t* dst, int B, int C, int H, int W, int Cpad, int ld,
@@ -291,6 +299,8 @@ struct ConvF32Params {
   int flags;            // CF_BIAS | CF_RES | CF_RELU | CF_MASK
 };
 hipError_t launch_conv_f32(const ConvF32Params& p, hipStream_t s);
+// add / copy / mask / maxpool3x3s2* move float4 vectors: C and every row stride multiples of 4, even H and W for the max pools, 16-byte
+// aligned row base pointers (hipErrorInvalidValue otherwise, pointers unchecked)
 hipError_t launch_add_f32(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int M, int C, hipStream_t s);
 hipError_t launch_copy_f32(const float* a, int lda, float* y, int ldy, int M, int C, hipStream_t s);
 // y = dy * (mask > 0 [&& mask < hi when hi > 0])   (ReLU / ReLU6 backward from the stored forward output)

@@ -15,6 +15,10 @@ int dd_op_conv_gemm_kind(const ConvGemmParams* p, size_t cap) {
   if (!p) return -1;                                    // DD_ERR_ARG
   return conv_gemm_kind(*p, cap);
 }
+int dd_op_conv_gemm_plan(const ConvGemmParams* p, size_t cap, int* out4) {
+  if (!p) return -1;                                    // DD_ERR_ARG
+  return conv_gemm_plan_query(*p, cap, out4);
+}
 int dd_op_conv_gemm_check(const ConvGemmParams* p, void* st) {
   // The synchronous companion for ABI users who want the contract checked against the DEVICE table: waits for the stream, reads the
   // tap table back and validates it (entries in range; a one-tap stride-1 same-size launch carries the centre tap).  0 = fine.
@@ -108,5 +112,76 @@ int dd_op_transform_update(const float* z, const float* g, const float* e, const
 }
 int dd_op_affine(const float* z, const float* e, const float* b, float* out, int BC, int HW, void* st) {
   return (int)launch_affine(z, e, b, out, BC, HW, S(st));
+}
+
+// the side kernels of the reverse programs
+int dd_op_mask_bf16(const uint16_t* dy, int ldd, const uint16_t* mask, int ldm, uint16_t* y, int ldy, int M, int C, void* st) {
+  return (int)launch_mask_bf16(dy, ldd, mask, ldm, y, ldy, M, C, S(st));
+}
+int dd_op_add_bf16(const uint16_t* a, int lda, const uint16_t* b, int ldb, uint16_t* y, int ldy, int M, int C, void* st) {
+  return (int)launch_add_bf16(a, lda, b, ldb, y, ldy, M, C, S(st));
+}
+int dd_op_copy_bf16(const uint16_t* a, int lda, uint16_t* y, int ldy, int M, int C, void* st) { return (int)launch_copy_bf16(a, lda, y, ldy, M, C, S(st)); }
+int dd_op_dup_bwd(const uint16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, void* st) {
+  return (int)launch_dup_bwd(gin, ld, g_z, B, C, HW, accumulate, halves, S(st));
+}
+int dd_op_gap_bwd(const float* gf, uint16_t* dx, int ld, int B, int HW, int C, const uint16_t* mask, int mask_ld, void* st) {
+  return (int)launch_gap_bwd(gf, dx, ld, B, HW, C, mask, mask_ld, S(st));
+}
+int dd_op_act_bf16(const uint16_t* x, int ldx, uint16_t* y, int ldy, int M, int C, int kind, void* st) {
+  return (int)launch_act_bf16(x, ldx, y, ldy, M, C, kind, S(st));
+}
+int dd_op_act_bwd_bf16(const uint16_t* x, int ldx, const uint16_t* dy, int ldd, uint16_t* dx, int ldo, int M, int C, int kind, int accumulate,
+                       void* st) {
+  return (int)launch_act_bwd_bf16(x, ldx, dy, ldd, dx, ldo, M, C, kind, accumulate, S(st));
+}
+int dd_op_patchify(const float* img, int ld, uint16_t* out, int B, int Sz, int p, int C, void* st) { return (int)launch_patchify(img, ld, out, B, Sz, p, C, S(st)); }
+int dd_op_patchify_bwd(const uint16_t* gout, float* gimg, int ld, int B, int Sz, int p, int C, void* st) {
+  return (int)launch_patchify_bwd(gout, gimg, ld, B, Sz, p, C, S(st));
+}
+int dd_op_vit_embed(const uint16_t* patches, int ldp, const float* cls, const float* pos, uint16_t* out, int ldo, int B, int np, int W, void* st) {
+  return (int)launch_vit_embed(patches, ldp, cls, pos, out, ldo, B, np, W, S(st));
+}
+int dd_op_vit_embed_bwd(const uint16_t* gout, int ldo, uint16_t* gp, int ldp, int B, int np, int W, void* st) {
+  return (int)launch_vit_embed_bwd(gout, ldo, gp, ldp, B, np, W, S(st));
+}
+int dd_op_select_rows(const uint16_t* x, int ldx, uint16_t* y, int ldy, int B, int stride, int C, void* st) {
+  return (int)launch_select_rows(x, ldx, y, ldy, B, stride, C, S(st));
+}
+int dd_op_select_rows_bwd(const uint16_t* dy, int ldy, uint16_t* dx, int ldx, int B, int stride, int C, int accumulate, void* st) {
+  return (int)launch_select_rows_bwd(dy, ldy, dx, ldx, B, stride, C, accumulate, S(st));
+}
+int dd_op_sub_scaled(const float* a, const float* g, float* out, size_t n, float rho, void* st) { return (int)launch_sub_scaled(a, g, out, n, rho, S(st)); }
+int dd_op_energy_weighted(const float* f, const float* Pc, const float* Pg, const int* targets, int B, int D, int K, float gs, float ls,
+                          int use_c, int use_g, int normalize, float weight, const float* sample_w, float* score_out, float* image_scores,
+                          float* gf, void* st) {
+  return (int)launch_energy(f, Pc, Pg, targets, B, D, K, gs, ls, use_c, use_g, normalize, weight, sample_w, score_out, image_scores, gf, S(st));
+}
+int dd_op_mask_f32(const float* dy, int ldd, const float* mask, int ldm, float* y, int ldy, int M, int C, float hi, void* st) {
+  return (int)launch_mask_f32(dy, ldd, mask, ldm, y, ldy, M, C, hi, S(st));
+}
+int dd_op_add_f32(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int M, int C, void* st) {
+  return (int)launch_add_f32(a, lda, b, ldb, y, ldy, M, C, S(st));
+}
+int dd_op_copy_f32(const float* a, int lda, float* y, int ldy, int M, int C, void* st) { return (int)launch_copy_f32(a, lda, y, ldy, M, C, S(st)); }
+int dd_op_maxpool3x3s2_f32(const float* x, float* y, int B, int H, int W, int C, void* st) { return (int)launch_maxpool3x3s2_f32(x, y, B, H, W, C, S(st)); }
+int dd_op_maxpool3x3s2_bwd_f32(const float* x, const float* dy, float* dx, int B, int H, int W, int C, void* st) {
+  return (int)launch_maxpool3x3s2_bwd_f32(x, dy, dx, B, H, W, C, S(st));
+}
+int dd_op_bicubic_f32(const float* src, int ld_s, float* dst, int ld_d, int B, int Hs, int Ws, int Hd, int Wd, int C, int Cpad, void* st) {
+  return (int)launch_bicubic_f32(src, ld_s, dst, ld_d, B, Hs, Ws, Hd, Wd, C, Cpad, S(st));
+}
+int dd_op_bicubic_bwd_f32(const float* ddst, int ld_d, void* dsrc, int dsrc_bf16, int ld_s, int B, int Hs, int Ws, int Hd, int Wd, int C,
+                          void* st) {
+  return (int)launch_bicubic_bwd_f32(ddst, ld_d, dsrc, dsrc_bf16, ld_s, B, Hs, Ws, Hd, Wd, C, S(st));
+}
+int dd_op_gap_f32(const float* x, int ld, float* f, int* argmax, int B, int HW, int C, int use_max, void* st) {
+  return (int)launch_gap_f32(x, ld, f, argmax, B, HW, C, use_max, S(st));
+}
+int dd_op_gap_bwd_f32(const float* gf, float* dx, int ld, int B, int HW, int C, const int* argmax, void* st) {
+  return (int)launch_gap_bwd_f32(gf, dx, ld, B, HW, C, argmax, S(st));
+}
+int dd_op_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int H, int W, int Cpad, int ld, void* st) {
+  return (int)launch_nchw_to_nhwc_f32(src, dst, B, C, H, W, Cpad, ld, S(st));
 }
 }

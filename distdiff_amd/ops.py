@@ -75,12 +75,14 @@ class PackedConvF32:
         self.bias = bias.detach().float().to(device) if bias is not None else None
 
 
-def conv_f32(x, pk, B, H, W, Ho, Wo, stride=1, shift=0, parity=0, res=None, mask=None, relu=False):
-    """x: fp32 [B*H*W, ld] (ld % 4 == 0); returns fp32 y [B*Ho*Wo, roundup(N, 4)]."""
+def conv_f32(x, pk, B, H, W, Ho, Wo, stride=1, shift=0, parity=0, res=None, mask=None, relu=False, y=None):
+    """x: fp32 [B*H*W, ld] (ld % 4 == 0); returns fp32 y [B*Ho*Wo, roundup(N, 4)].  y: the output rows to write (at least N columns);
+    res may be that same tensor (the accumulating input-gradient of the reverse pass)."""
     from ._lib import ConvF32Params
     p = ConvF32Params()
     M = B * Ho * Wo
-    y = torch.zeros((M, (pk.N + 3) // 4 * 4), device=x.device, dtype=torch.float32)
+    if y is None:
+        y = torch.zeros((M, (pk.N + 3) // 4 * 4), device=x.device, dtype=torch.float32)
     p.x, p.w, p.taptab, p.y = _ptr(x), _ptr(pk.w), _ptr(pk.taptab), _ptr(y)
     p.x_ld, p.y_ld = x.stride(0), y.stride(0)
     flags = 0
@@ -198,7 +200,28 @@ def conv_gemm_kind(x, pk, B, H, W, Ho, Wo, *args, **kw):
     return kind
 
 
-def groupnorm(x, gamma, beta, B, HW, G, eps, silu, dy=None, stats=None, chan_part=None):
+# the forms inside kind "general" (dd_op_conv_gemm_plan): conv_gemm_kernel's two tile shapes, then conv_gemm_big_kernel's configurations
+CONV_GEMM_FORMS = ("small_128x128", "big_128x256", "big_256x160", "big_256x128", "big_128x160_two_workgroups", "big_128x128_two_workgroups")
+
+
+def conv_gemm_plan(x, pk, B, H, W, Ho, Wo, *args, **kw):
+    """(kind, form, split) of the launch conv_gemm would make for the same arguments (nothing is launched; buffers as for conv_gemm_kind):
+    kind as conv_gemm_kind; form names the kernel form inside kind "general" (CONV_GEMM_FORMS, or "small_256x64"), None for the other
+    kinds; split is the split-K (the chunk split at the 8 x 8 halo level) in use, 1 = none."""
+    p, cap, _y, _keep = _conv_gemm_params(x, pk, B, H, W, Ho, Wo, *args, dry=True, **kw)
+    out4 = (C.c_int * 4)()
+    kind = _lib.lib().dd_op_conv_gemm_plan(C.byref(p), cap, out4)
+    if kind < 0:
+        raise RuntimeError("conv_gemm_plan: the launcher refuses this problem (status %d)" % kind)
+    form = None
+    if kind == 0:
+        form = "small_256x64" if (out4[1] == 0 and out4[3]) else CONV_GEMM_FORMS[out4[1]]
+    return CONV_GEMM_KINDS[kind], form, out4[2]
+
+
+def groupnorm(x, gamma, beta, B, HW, G, eps, silu, dy=None, stats=None, chan_part=None, accumulate_into=None):
+    """Forward (y, stats), or with dy the input-gradient dx.  accumulate_into: a dx buffer that already holds a gradient -- the result
+    is added to it in place (GroupNormParams.accumulate) and it is returned."""
     Cc = x.shape[1]
     L = _lib.lib()
     p = GroupNormParams()
@@ -214,8 +237,8 @@ def groupnorm(x, gamma, beta, B, HW, G, eps, silu, dy=None, stats=None, chan_par
     if dy is None:
         check(L.dd_op_groupnorm_fwd(C.byref(p), _stream()), "gn_fwd")
         return y, stats
-    dx = torch.empty_like(x)
-    p.dy, p.dy_ld, p.dx, p.dx_ld, p.accumulate = _ptr(dy), dy.stride(0), _ptr(dx), dx.stride(0), 0
+    dx = torch.empty_like(x) if accumulate_into is None else accumulate_into
+    p.dy, p.dy_ld, p.dx, p.dx_ld, p.accumulate = _ptr(dy), dy.stride(0), _ptr(dx), dx.stride(0), int(accumulate_into is not None)
     check(L.dd_op_groupnorm_bwd(C.byref(p), _stream()), "gn_bwd")
     return dx
 
@@ -232,7 +255,8 @@ def layernorm_stats(x, eps, rowpart=None, spans=0):
     return stats
 
 
-def layernorm(x, gamma, beta, eps, dy=None, stats=None):
+def layernorm(x, gamma, beta, eps, dy=None, stats=None, accumulate_into=None):
+    """Forward (y, stats), or with dy the input-gradient dx; accumulate_into as for groupnorm (LayerNormParams.accumulate)."""
     M, Cc = x.shape
     L = _lib.lib()
     p = LayerNormParams()
@@ -244,8 +268,8 @@ def layernorm(x, gamma, beta, eps, dy=None, stats=None):
     if dy is None:
         check(L.dd_op_layernorm_fwd(C.byref(p), _stream()), "ln_fwd")
         return y, stats
-    dx = torch.empty_like(x)
-    p.dy, p.dy_ld, p.dx, p.dx_ld, p.accumulate = _ptr(dy), dy.stride(0), _ptr(dx), dx.stride(0), 0
+    dx = torch.empty_like(x) if accumulate_into is None else accumulate_into
+    p.dy, p.dy_ld, p.dx, p.dx_ld, p.accumulate = _ptr(dy), dy.stride(0), _ptr(dx), dx.stride(0), int(accumulate_into is not None)
     check(L.dd_op_layernorm_bwd(C.byref(p), _stream()), "ln_bwd")
     return dx
 

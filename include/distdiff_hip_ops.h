@@ -42,6 +42,10 @@ int dd_op_conv_gemm(const struct ConvGemmParams* p, size_t partial_cap_bytes, vo
  * device access; the pointers are only tested for null): 0 the general implicit-GEMM kernels (conv_gemm_kernel / conv_gemm_big_kernel),
  * 1 conv_halo_kernel, 2 conv_halo_persist_kernel, 3 gemm_ws_kernel, 4 gemm_pps_kernel; DD_ERR_ARG (-1) for a problem the launcher refuses. */
 int dd_op_conv_gemm_kind(const struct ConvGemmParams* p, size_t partial_cap_bytes);
+/* The same dry decision with the form inside the kind: returns the kind and fills out4 = {kind, configuration of conv_gemm_big_kernel (0:
+ * the small conv_gemm_kernel; 1 128 x 256, 2 256 x 160, 3 256 x 128 tiles on 8 waves; 4 128 x 160, 5 128 x 128 as two 4-wave workgroups
+ * per CU), split-K (chunk split at the 8 x 8 halo level) the launch uses, 1 when the small kernel runs 256 x 64 instead of 128 x 128 tiles} */
+int dd_op_conv_gemm_plan(const struct ConvGemmParams* p, size_t partial_cap_bytes, int* out4);
 /* Synchronous check of that contract against the DEVICE table (waits for the stream, copies the table back): 0 when every entry is in
  * range and a pointwise launch carries the centre tap.  For ABI users without a host copy of their tables; never called by the engine. */
 int dd_op_conv_gemm_check(const struct ConvGemmParams* p, void* stream);
@@ -94,6 +98,44 @@ int dd_op_energy(const float* f, const float* Pc, const float* Pg, const int* ta
 int dd_op_transform_update(const float* z, const float* g, const float* e, const float* b, float* z_out, int BC, int HW,
                            float rho, float c, void* stream);
 int dd_op_affine(const float* z, const float* e, const float* b, float* out, int BC, int HW, void* stream);
+
+/* ---- side kernels of the reverse programs (the launchers of distdiff_amd/csrc/kernels.h, one thin forward each) ----
+ * bf16 rows [M, ld]: the 8-wide kernels (add, copy, mask, sumpool2x2, maxpool, geglu_bwd) refuse C or a row stride that is not a
+ * multiple of 8, the max pools odd H / W (hipErrorInvalidValue, nothing is launched); the fp32 forms below the same with 4. */
+int dd_op_mask_bf16(const uint16_t* dy, int ldd, const uint16_t* mask, int ldm, uint16_t* y, int ldy, int M, int C, void* stream);
+int dd_op_add_bf16(const uint16_t* a, int lda, const uint16_t* b, int ldb, uint16_t* y, int ldy, int M, int C, void* stream);
+int dd_op_copy_bf16(const uint16_t* a, int lda, uint16_t* y, int ldy, int M, int C, void* stream);
+int dd_op_dup_bwd(const uint16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, void* stream);
+int dd_op_gap_bwd(const float* gf, uint16_t* dx, int ld, int B, int HW, int C, const uint16_t* mask, int mask_ld, void* stream);
+int dd_op_act_bf16(const uint16_t* x, int ldx, uint16_t* y, int ldy, int M, int C, int kind, void* stream);
+int dd_op_act_bwd_bf16(const uint16_t* x, int ldx, const uint16_t* dy, int ldd, uint16_t* dx, int ldo, int M, int C, int kind,
+                       int accumulate, void* stream);
+int dd_op_patchify(const float* img, int ld, uint16_t* out, int B, int S, int p, int C, void* stream);
+int dd_op_patchify_bwd(const uint16_t* gout, float* gimg, int ld, int B, int S, int p, int C, void* stream);
+int dd_op_vit_embed(const uint16_t* patches, int ldp, const float* cls, const float* pos, uint16_t* out, int ldo, int B, int np, int W,
+                    void* stream);
+int dd_op_vit_embed_bwd(const uint16_t* gout, int ldo, uint16_t* gp, int ldp, int B, int np, int W, void* stream);
+int dd_op_select_rows(const uint16_t* x, int ldx, uint16_t* y, int ldy, int B, int stride, int C, void* stream);
+int dd_op_select_rows_bwd(const uint16_t* dy, int ldy, uint16_t* dx, int ldx, int B, int stride, int C, int accumulate, void* stream);
+int dd_op_sub_scaled(const float* a, const float* g, float* out, size_t n, float rho, void* stream);
+/* dd_op_energy with per-image weights w_i = sample_w[i] (device [B]; NULL: 1 / B) and image_scores[i] += weight * E_i (device [B] or NULL) */
+int dd_op_energy_weighted(const float* f, const float* Pc, const float* Pg, const int* targets, int B, int D, int K, float gs, float ls,
+                          int use_c, int use_g, int normalize, float weight, const float* sample_w, float* score_out,
+                          float* image_scores, float* gf, void* stream);
+/* fp32 rows (guide_f32.hip).  mask: y = dy * (mask > 0 [&& mask < hi when hi > 0]); gap: argmax only for the max form; gap_bwd: argmax
+ * NULL = the average form; bicubic_bwd: dsrc is bf16 rows when dsrc_bf16, else fp32 */
+int dd_op_mask_f32(const float* dy, int ldd, const float* mask, int ldm, float* y, int ldy, int M, int C, float hi, void* stream);
+int dd_op_add_f32(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int M, int C, void* stream);
+int dd_op_copy_f32(const float* a, int lda, float* y, int ldy, int M, int C, void* stream);
+int dd_op_maxpool3x3s2_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
+int dd_op_maxpool3x3s2_bwd_f32(const float* x, const float* dy, float* dx, int B, int H, int W, int C, void* stream);
+int dd_op_bicubic_f32(const float* src, int ld_s, float* dst, int ld_d, int B, int Hs, int Ws, int Hd, int Wd, int C, int Cpad,
+                      void* stream);
+int dd_op_bicubic_bwd_f32(const float* ddst, int ld_d, void* dsrc, int dsrc_bf16, int ld_s, int B, int Hs, int Ws, int Hd, int Wd, int C,
+                          void* stream);
+int dd_op_gap_f32(const float* x, int ld, float* f, int* argmax, int B, int HW, int C, int use_max, void* stream);
+int dd_op_gap_bwd_f32(const float* gf, float* dx, int ld, int B, int HW, int C, const int* argmax, void* stream);
+int dd_op_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int H, int W, int Cpad, int ld, void* stream);
 
 /* ---- test-only hooks into a dd_engine (include/distdiff_hip.h); no production caller ----
  * debug introspection of the op graph: host copy of an activation or gradient of tensor idx (negative: from the end, -1 = the
