@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DD_LIB") or os.path.join(_HERE, "libdistdiff_hip.so")   # DD_LIB: A/B builds for benchmarking
 
-ABI_VERSION = 7      # DD_ABI_VERSION of include/distdiff_hip.h this package's ctypes mirrors were written against
+ABI_VERSION = 8      # DD_ABI_VERSION of include/distdiff_hip.h this package's ctypes mirrors were written against
 
 _lib = None
 
@@ -103,6 +103,7 @@ OPS_SYMBOLS = [
     "dd_op_patchify", "dd_op_patchify_bwd", "dd_op_vit_embed", "dd_op_vit_embed_bwd", "dd_op_select_rows", "dd_op_select_rows_bwd",
     "dd_op_sub_scaled", "dd_op_energy_weighted", "dd_op_mask_f32", "dd_op_add_f32", "dd_op_copy_f32", "dd_op_maxpool3x3s2_f32",
     "dd_op_maxpool3x3s2_bwd_f32", "dd_op_bicubic_f32", "dd_op_bicubic_bwd_f32", "dd_op_gap_f32", "dd_op_gap_bwd_f32", "dd_op_nchw_to_nhwc_f32",
+    "dd_op_step_coefs", "dd_op_sampler_step_scratch_floats", "dd_op_sampler_step", "dd_op_sampler_step_bwd",
     "dd_debug_tensor", "dd_debug_num_tensors", "dd_debug_set_image", "dd_debug_set_images",
 ]
 ENGINE_SYMBOLS = [
@@ -134,6 +135,11 @@ def _declare(l):
     l.dd_op_nhwc_to_nchw_f32.argtypes = [vp, i, vp, i, i, i, i, i, f, f, i, f, f, vp]
     l.dd_op_cfg_ddim.argtypes = [vp, i, vp, vp, vp, i, i, i, vp, vp]
     l.dd_op_cfg_ddim_bwd.argtypes = [vp, vp, vp, i, vp, i, i, i, vp, vp]
+    l.dd_op_step_coefs.argtypes = [i, C.c_double, C.c_double, vp]
+    l.dd_op_sampler_step_scratch_floats.argtypes = [i, i]
+    l.dd_op_sampler_step_scratch_floats.restype = sz
+    l.dd_op_sampler_step.argtypes = [vp, i, vp, vp, vp, i, i, i, vp, vp, i, f, vp, vp, vp]
+    l.dd_op_sampler_step_bwd.argtypes = [vp, vp, vp, i, vp, i, i, i, vp, vp, i, f, vp, vp, vp, vp]
     l.dd_op_sumpool2x2.argtypes = [vp, i, vp, i, i, i, i, i, i, vp]
     l.dd_op_geglu_bwd.argtypes = [vp, i, vp, i, vp, i, i, i, vp]
     l.dd_op_maxpool3x3s2.argtypes = [vp, vp, i, i, i, i, vp]

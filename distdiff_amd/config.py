@@ -31,6 +31,7 @@ class UNetConfig:
     # no additional conditioning)
     transformer_depth: Tuple[int, ...] = ()
     level_heads: Tuple[int, ...] = ()
+    use_linear_projection: bool = False      # proj_in / proj_out of every Transformer2DModel are nn.Linear (SDXL, SD-2.x), not 1x1 convs
     add_time_dim: int = 0              # addition_time_embed_dim (256): sinusoid width of each of the 6 time ids
     add_text_dim: int = 0              # pooled text embedding width (1280); add_embedding input = add_text_dim + 6 * add_time_dim
 
@@ -131,7 +132,8 @@ def guide_config(arch="resnet50", **kw):
 
 @dataclass
 class SchedulerConfig:
-    """DDIMScheduler as configured by the SD-1.x repo scheduler_config.json."""
+    """DDIMScheduler as configured by the SD-1.x repo scheduler_config.json.  Built values: beta_schedule
+    scaled_linear | linear, prediction_type epsilon | v_prediction | sample, timestep_spacing leading | trailing | linspace."""
     num_train_timesteps: int = 1000
     beta_start: float = 0.00085
     beta_end: float = 0.012
@@ -141,6 +143,12 @@ class SchedulerConfig:
     clip_sample: bool = False
     prediction_type: str = "epsilon"
     timestep_spacing: str = "leading"
+    rescale_betas_zero_snr: bool = False
+
+
+PREDICTION_TYPES = ("epsilon", "v_prediction", "sample")
+TIMESTEP_SPACINGS = ("leading", "trailing", "linspace")
+BETA_SCHEDULES = ("scaled_linear", "linear")
 
 
 @dataclass
@@ -173,7 +181,7 @@ def sdxl_config(latent_size=128, max_batch=1):
     cfg = EngineConfig(latent_size=latent_size, max_batch=max_batch)
     cfg.unet = UNetConfig(block_out_channels=(320, 640, 1280), layers_per_block=2, down_attn=(False, True, True), up_attn=(True, True, False),
                           num_heads=10, cross_attention_dim=2048, transformer_depth=(1, 2, 10), level_heads=(5, 10, 20),
-                          add_time_dim=256, add_text_dim=1280)
+                          use_linear_projection=True, add_time_dim=256, add_text_dim=1280)
     cfg.vae.scaling_factor = 0.13025
     # text_encoder/ = CLIP ViT-L/14 text tower (the SD-1.x one), text_encoder_2/ = OpenCLIP ViT-bigG/14 text tower
     cfg.text2 = TextConfig(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=20, hidden_act="gelu",
@@ -189,7 +197,7 @@ def tiny_sdxl_config(latent_size=16, max_batch=2):
     cfg = tiny_config(latent_size, max_batch)
     cfg.unet = UNetConfig(block_out_channels=(64, 128, 128), layers_per_block=1, down_attn=(False, True, True), up_attn=(True, True, False),
                           num_heads=2, cross_attention_dim=96, norm_num_groups=8, transformer_depth=(1, 2, 3), level_heads=(2, 2, 4),
-                          add_time_dim=8, add_text_dim=24)
+                          use_linear_projection=True, add_time_dim=8, add_text_dim=24)
     # two text towers whose widths add up to the cross-attention width (32 + 64, head dim 32 like the tiny SD-1.x tower); the second
     # one projects its pooled token to add_text_dim
     cfg.text = TextConfig(vocab_size=97, hidden_size=32, intermediate_size=64, num_hidden_layers=2, num_attention_heads=1,
@@ -197,6 +205,29 @@ def tiny_sdxl_config(latent_size=16, max_batch=2):
     cfg.text2 = TextConfig(vocab_size=97, hidden_size=64, intermediate_size=128, num_hidden_layers=3, num_attention_heads=2,
                            max_position_embeddings=13, hidden_act="gelu", projection_dim=24)
     cfg.text_hidden_layer = -2
+    return cfg
+
+
+def sd21_config(latent_size=96, max_batch=1, v_prediction=True):
+    """Stable Diffusion 2.x: the SD-1.x block widths with head dim 64 everywhere (attention_head_dim [5, 10, 20, 20] = head COUNTS),
+    linear proj_in / proj_out, cross-attention on the 1024-wide OpenCLIP ViT-H/14 text tower (23 layers kept, erf-GELU, read at
+    last_hidden_state as dataloader.py:633-646 reads any model).  v_prediction=True: 768-v (96 x 96 latents); False: 2.1-base at 512."""
+    cfg = EngineConfig(latent_size=latent_size, max_batch=max_batch)
+    cfg.unet = UNetConfig(num_heads=20, level_heads=(5, 10, 20, 20), cross_attention_dim=1024, use_linear_projection=True)
+    cfg.text = TextConfig(hidden_size=1024, intermediate_size=4096, num_hidden_layers=23, num_attention_heads=16, hidden_act="gelu")
+    cfg.scheduler.prediction_type = "v_prediction" if v_prediction else "epsilon"
+    return cfg
+
+
+def tiny_sd2_config(latent_size=16, max_batch=2):
+    """The SD-2.x structure at test size: head dim 64 on every level, a cross-attention width that differs from the UNet's, linear
+    projections, an erf-GELU text tower with head dim 64, v-prediction."""
+    cfg = tiny_config(latent_size, max_batch)
+    cfg.unet = UNetConfig(block_out_channels=(64, 128, 128, 128), layers_per_block=1, num_heads=2, level_heads=(1, 2, 2, 2),
+                          cross_attention_dim=128, norm_num_groups=8, use_linear_projection=True)
+    cfg.text = TextConfig(vocab_size=97, hidden_size=128, intermediate_size=256, num_hidden_layers=3, num_attention_heads=2,
+                          max_position_embeddings=13, hidden_act="gelu")
+    cfg.scheduler.prediction_type = "v_prediction"
     return cfg
 
 
@@ -213,8 +244,12 @@ def tiny_config(latent_size=16, max_batch=2):
         latent_size=latent_size, text_len=13, max_batch=max_batch)
 
 
-def from_model_dir(path, latent_size=64, max_batch=1):
-    """Populates the config from a local HF Stable-Diffusion directory when its JSON files exist."""
+def from_model_dir(path, latent_size=64, max_batch=1, sampler_variants=False):
+    """Populates the config from a local HF Stable-Diffusion directory when its JSON files exist.
+    Called as is, this is the strict SD-1.x reader: any scheduler setting other than epsilon / leading / scaled_linear is refused.
+    sampler_variants=True (what the CLI passes) accepts what the engine's sampler has since learnt: prediction_type epsilon |
+    v_prediction | sample, timestep_spacing leading | trailing | linspace, beta_schedule scaled_linear | linear and
+    rescale_betas_zero_snr -- an SD-2.x directory.  clip_sample, thresholding and unknown values are refused either way."""
     cfg = sd15_config(latent_size, max_batch)
     cfg.text_len = None
 
@@ -232,11 +267,12 @@ def from_model_dir(path, latent_size=64, max_batch=1):
         cfg.unet.norm_eps = u.get("norm_eps", cfg.unet.norm_eps)
         cfg.unet.freq_shift = u.get("freq_shift", cfg.unet.freq_shift)
         cfg.unet.flip_sin_to_cos = u.get("flip_sin_to_cos", cfg.unet.flip_sin_to_cos)
+        cfg.unet.use_linear_projection = bool(u.get("use_linear_projection", False))
         if "down_block_types" in u:
             cfg.unet.down_attn = tuple("CrossAttn" in t for t in u["down_block_types"])
             cfg.unet.up_attn = tuple("CrossAttn" in t for t in u["up_block_types"])
         nl = len(cfg.unet.block_out_channels)
-        if isinstance(u.get("attention_head_dim"), (list, tuple)):          # SDXL: per-level head COUNTS
+        if isinstance(u.get("attention_head_dim"), (list, tuple)):          # SDXL, SD-2.x: per-level head COUNTS
             cfg.unet.level_heads = tuple(u["attention_head_dim"])
             cfg.unet.num_heads = cfg.unet.level_heads[-1]
         tl = u.get("transformer_layers_per_block", 1)
@@ -277,18 +313,31 @@ def from_model_dir(path, latent_size=64, max_batch=1):
     s = _load("scheduler/scheduler_config.json")
     if s:
         for k in ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "steps_offset", "set_alpha_to_one",
-                  "clip_sample", "prediction_type", "timestep_spacing"):
+                  "clip_sample", "prediction_type", "timestep_spacing", "rescale_betas_zero_snr"):
             if k in s:
                 setattr(cfg.scheduler, k, s[k])
-    # the engine implements the sampler the SD-1.x repos configure; anything else would run with silently wrong
-    # results, so it is refused
-    sc = cfg.scheduler
-    if sc.prediction_type != "epsilon":
-        raise NotImplementedError("scheduler prediction_type=%r: only epsilon-prediction models are built" % sc.prediction_type)
-    if sc.clip_sample:
-        raise NotImplementedError("scheduler clip_sample=true is not built (SD-1.x uses clip_sample=false)")
-    if sc.timestep_spacing != "leading":
-        raise NotImplementedError("scheduler timestep_spacing=%r: only 'leading' is built" % sc.timestep_spacing)
-    if sc.beta_schedule != "scaled_linear":
-        raise NotImplementedError("scheduler beta_schedule=%r: only 'scaled_linear' is built" % sc.beta_schedule)
+        if s.get("thresholding"):
+            raise NotImplementedError("scheduler thresholding=true is not built (no latent-space model sets it)")
+    check_scheduler(cfg.scheduler, sampler_variants)
     return cfg
+
+
+def check_scheduler(sc, sampler_variants=True):
+    """Refuses, by key, every scheduler setting the engine would run with silently wrong results.  sampler_variants=False: the sampler the
+    SD-1.x repos configure and nothing else."""
+    if sc.clip_sample:
+        raise NotImplementedError("scheduler clip_sample=true is not built (no latent-space model sets it)")
+    if not sampler_variants:
+        if sc.prediction_type != "epsilon":
+            raise NotImplementedError("scheduler prediction_type=%r: the SD-1.x reader takes epsilon-prediction models only "
+                                      "(from_model_dir(..., sampler_variants=True) reads the others)" % sc.prediction_type)
+        if sc.timestep_spacing != "leading":
+            raise NotImplementedError("scheduler timestep_spacing=%r: the SD-1.x reader takes 'leading' only" % sc.timestep_spacing)
+        if sc.beta_schedule != "scaled_linear":
+            raise NotImplementedError("scheduler beta_schedule=%r: the SD-1.x reader takes 'scaled_linear' only" % sc.beta_schedule)
+        if sc.rescale_betas_zero_snr:
+            raise NotImplementedError("scheduler rescale_betas_zero_snr=true: not an SD-1.x setting")
+        return
+    for key, built in (("prediction_type", PREDICTION_TYPES), ("timestep_spacing", TIMESTEP_SPACINGS), ("beta_schedule", BETA_SCHEDULES)):
+        if getattr(sc, key) not in built:
+            raise NotImplementedError("scheduler %s=%r is not built (built: %s)" % (key, getattr(sc, key), ", ".join(built)))

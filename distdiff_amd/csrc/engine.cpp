@@ -114,16 +114,31 @@ void guide_vae_bwd(dd_engine* E, int k, float* g_x0, hipStream_t s) {
                                  1.f / c.vae_scaling_factor, 0.f, 0, 0.f, 0.f, s));
 }
 
+// CFG + scheduler step on the UNet output of instance k, and its VJP: today's cfg_ddim pair for (epsilon, no rescale), the linear-form
+// kernels for every other (prediction_type, guidance_rescale) -- the choice is made inside the launchers
+void sampler_step(dd_engine* E, int k, const float* z, int step_index, float* z_prev, float* x0, hipStream_t s) {
+  const dd_config& c = E->cfg;
+  const Tn& out = E->unet.t[E->unet_out];
+  HIPCHK(launch_sampler_step((const float*)(E->inst[k].unet + out.off), out.ld, z, z_prev, x0, c.max_batch, c.unet_out_channels,
+                             c.latent_size * c.latent_size, E->coef_table + (size_t)step_index * 8, E->step_table + (size_t)step_index * 4,
+                             E->sp.prediction_type, E->sp.guidance_rescale, E->inst[k].rs_stats, E->rs_part, s));
+}
+void sampler_step_bwd(dd_engine* E, int k, const Ctx& uc, int step_index, const float* g_x0, const float* g_znext, float* g_z, hipStream_t s) {
+  const dd_config& c = E->cfg;
+  const Tn& out = E->unet.t[E->unet_out];
+  HIPCHK(launch_sampler_step_bwd(g_x0, g_znext, grad_ptr(uc, out), out.ld, g_z, c.max_batch, c.unet_out_channels,
+                                 c.latent_size * c.latent_size, E->coef_table + (size_t)step_index * 8,
+                                 E->step_table + (size_t)step_index * 4, E->sp.prediction_type, E->sp.guidance_rescale,
+                                 (const float*)(E->inst[k].unet + out.off), E->inst[k].rs_stats, E->rs_part, s));
+}
+
 // one guided forward step on instance k: z_in -> (z_next, x0, feat) ; energy accumulates into score, writes gfeat
 void guided_forward(dd_engine* E, int k, const float* z_in, int step_index, const int* targets, int normalize, float weight,
                     float* score, hipStream_t s) {
   const dd_config& c = E->cfg;
   auto& I = E->inst[k];
-  const int HW = c.latent_size * c.latent_size;
   unet_fwd(E, k, z_in, step_index, s);
-  const Tn& out = E->unet.t[E->unet_out];
-  HIPCHK(launch_cfg_ddim((const float*)(I.unet + out.off), out.ld, z_in, I.z_next, I.x0, c.max_batch, c.unet_out_channels, HW,
-                         E->coef_table + (size_t)step_index * 8, s));
+  sampler_step(E, k, z_in, step_index, I.z_next, I.x0, s);
   vae_fwd(E, k, I.x0, s);
   guide_fwd_from_image(E, k, s);
   HIPCHK(launch_energy(I.feat, E->Pc, E->Pg, targets, c.max_batch, E->pD, E->pK, E->sp.gs, E->sp.ls, E->sp.use_global, E->sp.use_local,
@@ -138,9 +153,7 @@ void guided_backward(dd_engine* E, int k, int step_index, const float* g_znext, 
   guide_vae_bwd(E, k, g_x0_tmp, s);
   Ctx uc = r.ctx(E->unet, E->inst[k].unet);
   uc.step_index = step_index;
-  const Tn& out = E->unet.t[E->unet_out];
-  HIPCHK(launch_cfg_ddim_bwd(g_x0_tmp, g_znext, grad_ptr(uc, out), out.ld, g_z_out, c.max_batch, c.unet_out_channels, HW,
-                             E->coef_table + (size_t)step_index * 8, s));
+  sampler_step_bwd(E, k, uc, step_index, g_x0_tmp, g_znext, g_z_out, s);
   run_bwd(E->unet, uc);
   const Tn& in = E->unet.t[E->unet_in];
   HIPCHK(launch_dup_bwd(grad_ptr(uc, in), in.ld, g_z_out, c.max_batch, c.unet_in_channels, HW, 1, in.B == 2 * c.max_batch ? 2 : 1, s));
@@ -289,7 +302,11 @@ int dd_finalize_weights(dd_engine* E) {
       I.z_in = (float*)E->dmalloc(zbytes); I.z_next = (float*)E->dmalloc(zbytes); I.x0 = (float*)E->dmalloc(zbytes);
       I.feat = (float*)E->dmalloc((size_t)B * guide_feat_dim(c) * 4);
       I.gfeat = (float*)E->dmalloc((size_t)B * guide_feat_dim(c) * 4);
+      I.rs_stats = (float*)E->dmalloc((size_t)B * 8 * 4);
     }
+    // the CFG-rescale backward re-reads the UNet's forward output of its step: it must live in the instance slab
+    if (E->unet.t[E->unet_out].transient) throw std::runtime_error("the UNet output is a transient tensor");
+    E->rs_part = (float*)E->dmalloc(sampler_step_scratch_floats(B, L * L) * 4);
     E->tr_slab = (char*)E->dmalloc(2 * std::max({E->unet.tr_max, E->vae.tr_max, E->guide.tr_max, E->venc.tr_max, E->text.tr_max, E->text2.tr_max, (size_t)256}));
     if (c.enable_grad) {
       // UNet gradients alone; VAE and guide gradients live side by side (bicubic^T bridges them)
@@ -338,12 +355,9 @@ int dd_set_schedule(dd_engine* E, const int* timesteps, int n, const float* alph
   if (!E->finalized) { E->err = "finalize first"; return DD_ERR_STATE; }
   DD_TRY(E, {
     const dd_config& c = E->cfg;
-    E->timesteps.assign(timesteps, timesteps + n);
-    E->sp = *sp;
-    HIPCHK(hipDeviceSynchronize());
-    for (void* q : E->sched_allocs) E->dfree(q);
-    E->sched_allocs.clear();
-    std::vector<float> coef((size_t)n * 8, 0.f);
+    if (sp->prediction_type < 0 || sp->prediction_type > 2) throw std::runtime_error("prediction_type must be 0 (epsilon), 1 (v_prediction) or 2 (sample)");
+    if (!(sp->guidance_rescale >= 0.f && sp->guidance_rescale <= 1.f)) throw std::runtime_error("guidance_rescale must be in [0, 1]");
+    std::vector<float> coef((size_t)n * 8, 0.f), lin((size_t)n * 4, 0.f);
     const int ratio = num_train / n;
     for (int i = 0; i < n; ++i) {
       const int t = timesteps[i], prev = t - ratio;
@@ -351,7 +365,19 @@ int dd_set_schedule(dd_engine* E, const int* timesteps, int n, const float* alph
       const double a = alphas_cumprod[t], ap = prev >= 0 ? alphas_cumprod[prev] : final_alpha;
       float* q = &coef[(size_t)i * 8];
       q[0] = sp->guidance_scale; q[1] = (float)sqrt(a); q[2] = (float)sqrt(1 - a); q[3] = (float)sqrt(ap); q[4] = (float)sqrt(1 - ap);
+      if (sampler_step_coefs(sp->prediction_type, a, ap, &lin[(size_t)i * 4]))      // the cfg_ddim kernels divide by sqrt(a) as well
+        throw std::runtime_error(sp->prediction_type == 0 ? "epsilon-prediction with alphas_cumprod = 0 at timestep " + std::to_string(t) +
+                                 " (zero terminal SNR): x0 is undefined there" : "sample-prediction with alphas_cumprod = 1 at timestep " + std::to_string(t));
     }
+    // every refusal is above: from here on the engine's schedule is replaced
+    E->timesteps.assign(timesteps, timesteps + n);
+    E->sp = *sp;
+    HIPCHK(hipDeviceSynchronize());
+    for (void* q : E->sched_allocs) E->dfree(q);
+    E->sched_allocs.clear();
+    E->step_table = (float*)E->dmalloc(lin.size() * 4, false);
+    E->sched_allocs.push_back(E->step_table);
+    HIPCHK(hipMemcpy(E->step_table, lin.data(), lin.size() * 4, hipMemcpyHostToDevice));
     E->coef_table = (float*)E->dmalloc(coef.size() * 4, false);
     E->sched_allocs.push_back(E->coef_table);
     HIPCHK(hipMemcpy(E->coef_table, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
@@ -486,11 +512,8 @@ int dd_unet_forward(dd_engine* E, const float* z, int step_index, float* eps2_ou
 
 // the launch sequence of one plain step: UNet forward (no stash) + CFG + DDIM
 static void denoise_step_enqueue(dd_engine* E, const float* z, int step_index, float* z_prev_out, float* x0_out, hipStream_t s) {
-  const dd_config& c = E->cfg;
   unet_fwd(E, 0, z, step_index, s, /*stash=*/false);
-  const Tn& out = E->unet.t[E->unet_out];
-  HIPCHK(launch_cfg_ddim((const float*)(E->inst[0].unet + out.off), out.ld, z, z_prev_out, x0_out, c.max_batch, c.unet_out_channels,
-                         c.latent_size * c.latent_size, E->coef_table + (size_t)step_index * 8, s));
+  sampler_step(E, 0, z, step_index, z_prev_out, x0_out, s);
 }
 
 int dd_denoise_step(dd_engine* E, const float* z, int step_index, float* z_prev_out, float* x0_out, int B, void* stream) {

@@ -267,6 +267,8 @@ struct dd_engine {
   // schedule
   std::vector<int> timesteps;
   float* coef_table = nullptr;   // [n][8]: guidance_scale, sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev), -, -, -
+  float* step_table = nullptr;   // [n][4]: A_z, A_m, B_z, B_m of the linear step form (v_prediction / sample models, CFG rescale)
+  float* rs_part = nullptr;      // CFG rescale: block partials of the per-image reductions (scratch, consumed by the next kernel)
   dd_sampler_params sp{};
   // prototypes
   float* Pc = nullptr; float* Pg = nullptr; int pC = 0, pK = 0, pD = 0;
@@ -276,6 +278,7 @@ struct dd_engine {
     char* unet = nullptr; char* vae = nullptr; char* guide = nullptr;
     float* eps2 = nullptr;  // view into unet slab (conv_out fp32 output)
     float* z_in = nullptr; float* z_next = nullptr; float* x0 = nullptr; float* feat = nullptr; float* gfeat = nullptr;
+    float* rs_stats = nullptr;   // CFG rescale: [B][8] per-image statistics of this step's forward, read again by its backward
   };
   std::vector<Inst> inst;
   char* grad_slab = nullptr;   // shared by the three programs (max of their grad sizes)

@@ -182,6 +182,21 @@ hipError_t launch_cfg_ddim(const float* eps2, int ld, const float* z, float* z_p
 //   g_x0, g_zprev NCHW fp32 (either may be null) -> g_eps2 NHWC bf16 [2B*HW, ld] and g_z_direct NCHW fp32
 hipError_t launch_cfg_ddim_bwd(const float* g_x0, const float* g_zprev, bf16_t* g_eps2, int ld, float* g_z, int B, int C,
                                int HW, const float* coef_dev, hipStream_t s);
+// The step for every prediction type (0 epsilon, 1 v_prediction, 2 sample) with optional CFG rescale phi (Lin et al. 2023; diffusers
+// rescale_noise_cfg): x0 = A_z z + A_m m^, z' = B_z z + B_m m^, m = u + s (c - u), m^ = m (phi sigma_c / sigma_m + 1 - phi) per image.
+//   coef_dev = the cfg_ddim row ([0] = guidance scale), lin_dev = {A_z, A_m, B_z, B_m} (sampler_step_coefs)
+//   (prediction_type 0, phi 0) IS launch_cfg_ddim / launch_cfg_ddim_bwd on coef_dev: lin_dev, stats and part are not read
+//   phi != 0: stats [B][8] receives {k, sigma_c, sigma_m, mean_c, mean_m, N, phi} (kept for the backward), part is scratch of
+//   sampler_step_scratch_floats(B, HW) floats.  The backward re-reads m2, the model output of that step, when phi != 0.
+//   ld: a multiple of 8; C <= 8.  No atomics: bitwise deterministic.
+int sampler_step_coefs(int prediction_type, double a, double a_prev, float* out4);      // host; -1: unknown type or a singular step
+size_t sampler_step_scratch_floats(int B, int HW);
+hipError_t launch_sampler_step(const float* m2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW,
+                               const float* coef_dev, const float* lin_dev, int prediction_type, float phi, float* stats, float* part,
+                               hipStream_t s);
+hipError_t launch_sampler_step_bwd(const float* g_x0, const float* g_zprev, bf16_t* g_m2, int ld, float* g_z, int B, int C, int HW,
+                                   const float* coef_dev, const float* lin_dev, int prediction_type, float phi, const float* m2,
+                                   const float* stats, float* part, hipStream_t s);
 // backward of cat[z, z] + NCHW->NHWC: g_z[b,c,pix] (+)= gin[b*HW+pix, c] + gin[(B+b)*HW+pix, c]   (halves = 2), or of the plain
 // layout change when the UNet input itself is not duplicated (halves = 1: the two CFG halves share their prefix, engine.cpp)
 hipError_t launch_dup_bwd(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, hipStream_t s);

@@ -80,6 +80,21 @@ int dd_op_cfg_ddim_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_eps2
                        const float* coef, void* st) {
   return (int)launch_cfg_ddim_bwd(g_x0, g_zprev, g_eps2, ld, g_z, B, C, HW, coef, S(st));
 }
+int dd_op_step_coefs(int prediction_type, double a, double a_prev, float* out4) {
+  if (!out4) return -1;
+  return sampler_step_coefs(prediction_type, a, a_prev, out4);
+}
+size_t dd_op_sampler_step_scratch_floats(int B, int HW) { return sampler_step_scratch_floats(B, HW); }
+int dd_op_sampler_step(const float* m2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW, const float* coef,
+                       const float* lin, int prediction_type, float guidance_rescale, float* stats, float* part, void* st) {
+  return (int)launch_sampler_step(m2, ld, z, z_prev, x0, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part, S(st));
+}
+int dd_op_sampler_step_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_m2, int ld, float* g_z, int B, int C, int HW,
+                           const float* coef, const float* lin, int prediction_type, float guidance_rescale, const float* m2,
+                           const float* stats, float* part, void* st) {
+  return (int)launch_sampler_step_bwd(g_x0, g_zprev, g_m2, ld, g_z, B, C, HW, coef, lin, prediction_type, guidance_rescale, m2, stats, part,
+                                      S(st));
+}
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int acc, void* st) {
   return (int)launch_sumpool2x2(src, src_ld, dst, dst_ld, B, H, W, C, acc, S(st));
 }

@@ -41,7 +41,10 @@ class DDConfig(C.Structure):
 class DDSamplerParams(C.Structure):
     _fields_ = [("guidance_scale", C.c_float), ("gs", C.c_float), ("ls", C.c_float), ("rho", C.c_float),
                 ("constraint_value", C.c_float), ("use_global", C.c_int), ("use_local", C.c_int),
-                ("guidance_period", C.c_int)]
+                ("guidance_period", C.c_int), ("prediction_type", C.c_int), ("guidance_rescale", C.c_float)]
+
+
+PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1, "sample": 2}       # dd_sampler_params.prediction_type
 
 
 class DDExpandArgs(C.Structure):
@@ -260,10 +263,16 @@ class Engine:
 
     # ---- setup -------------------------------------------------------------------------------
     def set_schedule(self, timesteps, alphas_cumprod, final_alpha_cumprod, guidance_scale=7.5, gs=1.0, ls=1.0, rho=10.0,
-                     constraint_value=0.2, use_global=True, use_local=True, guidance_period=2):
+                     constraint_value=0.2, use_global=True, use_local=True, guidance_period=2, prediction_type="epsilon",
+                     guidance_rescale=0.0):
+        """prediction_type: what the UNet predicts, 'epsilon' | 'v_prediction' | 'sample' (scheduler_config.json); guidance_rescale: the
+        CFG rescale factor phi in [0, 1] (diffusers rescale_noise_cfg).  The defaults are the SD-1.x sampler."""
+        if prediction_type not in PREDICTION_TYPES:
+            raise NotImplementedError("prediction_type=%r (built: %s)" % (prediction_type, ", ".join(PREDICTION_TYPES)))
         ts = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int32))
         ac = np.ascontiguousarray(np.asarray(alphas_cumprod, dtype=np.float32))
-        sp = DDSamplerParams(guidance_scale, gs, ls, rho, constraint_value, int(use_global), int(use_local), int(guidance_period))
+        sp = DDSamplerParams(guidance_scale, gs, ls, rho, constraint_value, int(use_global), int(use_local), int(guidance_period),
+                             PREDICTION_TYPES[prediction_type], float(guidance_rescale))
         self._chk(self.L.dd_set_schedule(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
                                          float(final_alpha_cumprod), C.byref(sp)), "dd_set_schedule")
         self.n_steps = len(ts)

@@ -26,6 +26,13 @@ draw for draw: one draw per reference batch, in loop order, is exactly the order
 `--text_to_img` runs what the reference's branch intends (:1150-1158; there it fails on `generator` used before assignment, :1155 vs
 :1194, and on `start_index` never being set): the loop starts from randn * init_noise_sigma (1 for DDIM) at the first timestep whatever
 --strength says, guidance as usual; image latents are not needed, so the latent cache / VAE encoder stage is skipped.
+Model families: a model directory is read whatever its scheduler file asks of DDIM within what diffusers' `DDIMScheduler.step` does
+for the reference (generate_data.py:119, :863): `prediction_type` epsilon / v_prediction / sample, `timestep_spacing` leading / trailing /
+linspace, `beta_schedule` scaled_linear / linear, `rescale_betas_zero_snr` -- so a Stable Diffusion 2.x directory (768-v included)
+runs as it does there.  `--timestep_spacing`, `--rescale_betas_zero_snr` and `--prediction_type` override the file (fine-tunes often
+document these settings without shipping them); `--guidance_rescale PHI` is the classifier-free-guidance rescale that goes with
+v-prediction / zero-SNR checkpoints (Lin et al. 2023; diffusers `rescale_noise_cfg`) -- beyond the reference, which mixes CFG by hand;
+`--synthetic_arch sd21` is the SD-2.1 structure with synthetic weights.  `clip_sample` and `thresholding` are refused.
 The stage before the loop runs on the engine too: image latents come from the reference's cache
 `save/vae_embedding/<dataset>/<model>/image_latents.pt` when it exists and are otherwise produced by the HIP VAE encoder and
 written to that path in the same format (dataloader.py:788-811); class prompts go through the Hugging Face tokenizer of the
@@ -100,9 +107,19 @@ def parse_args(argv=None):
     p.add_argument("--synthetic_encode", action="store_true",
                    help="with --synthetic: produce latents / prompt embeddings with the HIP VAE encoder and CLIP text encoder")
     p.add_argument("--tiny", action="store_true", help="use the tiny test architecture (with --synthetic)")
-    p.add_argument("--synthetic_arch", default="sd15", choices=["sd15", "sdxl"],
-                   help="with --synthetic: the SD-1.x structure or the SDXL-base one (two text towers, text_time conditioning; BASELINE "
-                   "configs[4]).  A real model directory is recognised by its text_encoder_2/ sub-folder")
+    p.add_argument("--synthetic_arch", default="sd15", choices=["sd15", "sdxl", "sd21"],
+                   help="with --synthetic: the SD-1.x structure, the SDXL-base one (two text towers, text_time conditioning; BASELINE "
+                   "configs[4]) or the SD-2.1 one (head dim 64, 1024-wide text tower, linear projections, v-prediction; 768-v is "
+                   "--resolution 768).  A real model directory is recognised by its config files")
+    p.add_argument("--guidance_rescale", type=float, default=0.0,
+                   help="classifier-free-guidance rescale phi in [0, 1] (Lin et al. 2023; diffusers rescale_noise_cfg): the mixed model output "
+                   "is scaled per image by phi * std(conditional) / std(mixed) + 1 - phi.  0 (default) = off, the reference's behaviour")
+    p.add_argument("--prediction_type", default=None, choices=["epsilon", "v_prediction", "sample"],
+                   help="override scheduler_config.json's prediction_type (chiefly for --synthetic)")
+    p.add_argument("--timestep_spacing", default=None, choices=["leading", "trailing", "linspace"],
+                   help="override scheduler_config.json's timestep_spacing")
+    p.add_argument("--rescale_betas_zero_snr", action="store_true", default=False,
+                   help="rescale the betas to zero terminal SNR (diffusers rescale_zero_terminal_snr) whatever scheduler_config.json says")
     p.add_argument("--engine_batch", type=int, default=0, help="images per engine launch (0 = the largest of 32 / 16 / 8 whose workspace fits the free HBM -- engine.batch_for_free_hbm: "
                    "about 5.85 GB per image with transform guidance at 512x512 + 12 GB, i.e. 199 / 106 / 59 GB; 32 is 4 %% faster than 16 and 16 12 %% "
                    "faster than 8; at another --resolution the per-image part scales with the pixel count and the choice is of 32 / 16 / 8 / 4 / 2 / 1, "
@@ -121,6 +138,8 @@ def parse_args(argv=None):
     env_local_rank = int(os.environ.get("LOCAL_RANK", -1))
     if env_local_rank != -1:
         args.local_rank = env_local_rank
+    if not 0.0 <= args.guidance_rescale <= 1.0:
+        raise SystemExit("--guidance_rescale must be in [0, 1]")
     if not args.do_classifier_free_guidance:
         raise SystemExit("the engine always runs classifier-free guidance (the reference's type=bool flag cannot be switched off either)")
     return args
@@ -455,13 +474,16 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
 
 def load_config_and_weights(args, B):
     """The model objects the reference builds at generate_data.py:863-922 and :1100-1104, as (EngineConfig, state dicts)."""
-    from .config import GUIDE_ARCHS, from_model_dir, guide_config, sd15_config, sdxl_config, tiny_config, tiny_sdxl_config
+    from .config import (GUIDE_ARCHS, from_model_dir, guide_config, sd15_config, sd21_config, sdxl_config, tiny_config, tiny_sd2_config,
+                         tiny_sdxl_config)
     from .model_utils import SUPPORTED, create_model
     from .weights import load_safetensors_dir, synthetic_weights
     latent = args.resolution // 8
     if args.synthetic:
         if args.synthetic_arch == "sdxl":
             cfg = tiny_sdxl_config(max_batch=B) if args.tiny else sdxl_config(latent, B)
+        elif args.synthetic_arch == "sd21":
+            cfg = tiny_sd2_config(max_batch=B) if args.tiny else sd21_config(latent, B)
         else:
             cfg = tiny_config(max_batch=B) if args.tiny else sd15_config(latent, B)
         if args.arch in GUIDE_ARCHS:                 # -a resnext50 / wideresnet50 / open_clip_vit_b32 (full-size guide only)
@@ -478,7 +500,7 @@ def load_config_and_weights(args, B):
     if not os.path.isdir(path):
         raise SystemExit("%s is not a local model directory (no network access here); pass a local Hugging Face layout with unet/, vae/, "
                          "text_encoder/, tokenizer/, scheduler/, or use --synthetic N" % path)
-    cfg = from_model_dir(path, latent, B)
+    cfg = from_model_dir(path, latent, B, sampler_variants=True)
     arch = args.arch if (args.guidance_type or args.arch in SUPPORTED) else "resnet50"   # unguided runs never evaluate the guide
     cfg.guide = guide_config(arch)
     guide = create_model(arch, pretrained=False, num_classes=1, weight_path=args.encoder_weight_path if args.guidance_type else None)
@@ -519,6 +541,20 @@ def auto_engine_batch(args, dev, distributed=False):
     return B
 
 
+def apply_scheduler_overrides(args, cfg):
+    """--prediction_type / --timestep_spacing / --rescale_betas_zero_snr over the model directory's scheduler file."""
+    from .config import check_scheduler
+    sc = cfg.scheduler
+    if getattr(args, "prediction_type", None):
+        sc.prediction_type = args.prediction_type
+    if getattr(args, "timestep_spacing", None):
+        sc.timestep_spacing = args.timestep_spacing
+    if getattr(args, "rescale_betas_zero_snr", False):
+        sc.rescale_betas_zero_snr = True
+    check_scheduler(sc)
+    return cfg
+
+
 def build_engine(args, device=None, distributed=False):
     from .engine import Engine
     from .scheduler import DDIMSchedule
@@ -538,12 +574,14 @@ def build_engine(args, device=None, distributed=False):
     else:
         cfg, weights = load_config_and_weights(args, B)
         eng = make_engine(cfg, weights, None)
+    apply_scheduler_overrides(args, cfg)
     sched = DDIMSchedule(cfg.scheduler)
     ts = sched.set_timesteps(args.steps)
     targets = (args.optimize_targets or "").split("-")
     eng.set_schedule(ts, sched.alphas_cumprod, sched.final_alpha_cumprod, guidance_scale=args.guidance_scale, gs=args.gs, ls=args.ls,
                      rho=args.rho, constraint_value=args.constraint_value, use_global="global_prototype" in targets,
-                     use_local="local_prototype" in targets, guidance_period=args.guidance_period)
+                     use_local="local_prototype" in targets, guidance_period=args.guidance_period,
+                     prediction_type=cfg.scheduler.prediction_type, guidance_rescale=args.guidance_rescale)
     return cfg, eng, sched
 
 

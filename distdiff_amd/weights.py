@@ -96,7 +96,7 @@ def synthetic_unet(cfg: EngineConfig, seed=0):
 
     def transformer(p, c, depth=1):
         b.norm(p + ".norm", c)
-        if u.transformer_depth:              # SDXL: use_linear_projection -> nn.Linear weights [C, C]
+        if u.transformer_depth or u.use_linear_projection:      # SDXL, SD-2.x: nn.Linear weights [C, C]
             b.linear(p + ".proj_in", c, c)
         else:
             b.conv(p + ".proj_in", c, c, 1)
@@ -111,7 +111,7 @@ def synthetic_unet(cfg: EngineConfig, seed=0):
                 b.linear(t + "." + a + ".to_out.0", c, c)
             b.linear(t + ".ff.net.0.proj", 8 * c, c)
             b.linear(t + ".ff.net.2", c, 4 * c)
-        if u.transformer_depth:
+        if u.transformer_depth or u.use_linear_projection:
             b.linear(p + ".proj_out", c, c)
         else:
             b.conv(p + ".proj_out", c, c, 1)

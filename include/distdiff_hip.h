@@ -13,7 +13,8 @@
  *   dd_set_prototypes      total_global_proto / total_local_proto               generate_data.py:1113-1125
  *   dd_set_prompt          prompt_embeds = cat[negative, prompt]                generate_data.py:1147-1148, 1184
  *   dd_add_noise           noise_scheduler.add_noise                            generate_data.py:1176
- *   dd_denoise_step        denoise_one_step                                     generate_data.py:109-121
+ *   dd_denoise_step        denoise_one_step (noise_scheduler.step for epsilon /   generate_data.py:109-121
+ *                          v_prediction / sample models: dd_sampler_params)
  *   dd_transform_guidance  transform_guidance (+ linfball_proj)                 generate_data.py:687-732, 124-137
  *   dd_direct_guidance     direct_guidance                                      generate_data.py:735-767
  *   dd_decode              vae.decode + image_processor.postprocess             generate_data.py:1221-1228
@@ -46,10 +47,11 @@ enum dd_status { DD_OK = 0, DD_ERR_ARG = -1, DD_ERR_HIP = -2, DD_ERR_STATE = -3,
 /* Layout version of the structs and argument lists of this header and distdiff_hip_ops.h.  A caller sets dd_config.abi_version =
  * DD_ABI_VERSION (after zero-initialising the struct: every struct of this ABI must be zero-initialised, new fields are appended and
  * mean "off" at 0); dd_create refuses another value with DD_ERR_ARG, and dd_abi_version() tells what the loaded library was built
- * as.  7: dd_expand_args gained seed / unit_ids / noise_mode / offset_noise / text_to_img (all 0 = the call of version 6), dd_randn_units
+ * as.  8: dd_sampler_params gained prediction_type / guidance_rescale (0 = the sampler of version 7), the dd_op_sampler_step* entry
+ * points are new; 7: dd_expand_args gained seed / unit_ids / noise_mode / offset_noise / text_to_img (all 0 = the call of version 6), dd_randn_units
  * is new; 6: dd_config gained unet_attn_fp8 + abi_version, AttnParams gained no_shortk; 5 (unversioned): workspace_bytes in the dd_op_attention_gemm_* lists,
  * ConvGemmParams.wgroup_rows / wgroup_elems, AttnParams.pv_fp8. */
-#define DD_ABI_VERSION 7
+#define DD_ABI_VERSION 8
 
 typedef struct dd_config {
   /* UNet2DConditionModel (unet/config.json) */
@@ -113,6 +115,19 @@ typedef struct dd_sampler_params {
   float constraint_value; /* L-inf radius (--constraint_value) */
   int use_global, use_local; /* --optimize_targets "global_prototype-local_prototype" */
   int guidance_period;    /* score divisor (args.guidance_period, generate_data.py:719) */
+  /* version 8, both 0 = the SD-1.x sampler.  What the UNet predicts (scheduler_config.json `prediction_type`; the reference gets all of
+   * them from diffusers' DDIMScheduler.step, generate_data.py:119): 0 epsilon, 1 v_prediction (SD-2.x 768-v), 2 sample.  With m the
+   * CFG-mixed output and a, a' = alphas_cumprod at t and at t - num_train / n (below 0: final_alpha_cumprod):
+   *   epsilon       x0 = (z - sqrt(1-a) m) / sqrt(a)    eps = m
+   *   v_prediction  x0 = sqrt(a) z - sqrt(1-a) m        eps = sqrt(a) m + sqrt(1-a) z     (no division: a = 0 is a legal first step
+   *   sample        x0 = m                              eps = (z - sqrt(a) m) / sqrt(1-a)  of a zero-terminal-SNR table)
+   *   z' = sqrt(a') x0 + sqrt(1-a') eps   (eta = 0)
+   * epsilon at a = 0 is refused by dd_set_schedule. */
+  int prediction_type;
+  /* classifier-free-guidance rescale phi in [0, 1] (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed";
+   * diffusers rescale_noise_cfg; beyond the reference, which mixes CFG by hand): m <- m (phi std(c) / std(m) + 1 - phi), std per image
+   * over all C*H*W elements (unbiased), c the conditional half.  Differentiated by the guidance calls like the rest of the step. */
+  float guidance_rescale;
 } dd_sampler_params;
 
 typedef struct dd_expand_args {

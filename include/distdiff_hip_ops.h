@@ -12,6 +12,7 @@
  *   dd_op_layernorm_*    LayerNorm in BasicTransformerBlock (:112)
  *   dd_op_attention_*    scaled-dot-product attention (self, cross, VAE mid block) (:112, :701)
  *   dd_op_cfg_ddim*      classifier-free guidance + DDIMScheduler.step (:116-119)
+ *   dd_op_sampler_step*  the same for v_prediction / sample models and with CFG rescale
  *   dd_op_bicubic*       F.interpolate(..., (224,224), 'bicubic') (:704, :745)
  *   dd_op_conv_f32       timm conv+BN(+ReLU) of image_encoder.encode_image and its input-gradient in exact fp32
  *                        (model_utils.py:29-41; generate_data.py:705, :721, :746, :761): v_mfma_f32_32x32x2_f32
@@ -82,6 +83,24 @@ int dd_op_cfg_ddim(const float* eps2, int ld, const float* z, float* z_prev, flo
                    const float* coef_dev, void* stream);
 int dd_op_cfg_ddim_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_eps2, int ld, float* g_z, int B, int C, int HW,
                        const float* coef_dev, void* stream);
+/* The step for every prediction_type (0 epsilon, 1 v_prediction, 2 sample; diffusers DDIMScheduler.step, eta = 0) with optional
+ * classifier-free-guidance rescale (guidance_rescale = phi of Lin et al. 2023, diffusers rescale_noise_cfg):
+ *   m = u + s (c - u),  m^ = m (phi std(c) / std(m) + 1 - phi) per image (unbiased std over the C*HW real elements),
+ *   x0 = A_z z + A_m m^,  z' = B_z z + B_m m^.
+ * coef_dev: the 5-float row of dd_op_cfg_ddim ([0] = s); lin_dev = {A_z, A_m, B_z, B_m}, filled by dd_op_step_coefs (host, double
+ * arithmetic; -1 for an unknown type or a singular step: epsilon at a = 0, sample at a = 1) from alphas_cumprod at t and at the
+ * previous timestep.  (prediction_type 0, guidance_rescale 0) runs dd_op_cfg_ddim / dd_op_cfg_ddim_bwd on coef_dev, bit for bit.
+ * guidance_rescale != 0: stats DEVICE [B][8] receives {k, std_c, std_m, mean_c, mean_m, N, phi} and is read again by the backward,
+ * part is DEVICE scratch of dd_op_sampler_step_scratch_floats(B, HW) floats, and the backward re-reads m2 (the forward's model
+ * output); all three may be NULL otherwise.  m2 fp32 rows [2B*HW, ld], g_m2 bf16 rows (every column written, padding 0); ld a
+ * multiple of 8, C <= 8.  Two-stage reductions in a fixed order, no atomics: the same call gives the same bits. */
+int dd_op_step_coefs(int prediction_type, double a, double a_prev, float* out4);
+size_t dd_op_sampler_step_scratch_floats(int B, int HW);
+int dd_op_sampler_step(const float* m2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW, const float* coef_dev,
+                       const float* lin_dev, int prediction_type, float guidance_rescale, float* stats, float* part, void* stream);
+int dd_op_sampler_step_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_m2, int ld, float* g_z, int B, int C, int HW,
+                           const float* coef_dev, const float* lin_dev, int prediction_type, float guidance_rescale, const float* m2,
+                           const float* stats, float* part, void* stream);
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int accumulate,
                      void* stream);
 int dd_op_geglu_bwd(const uint16_t* raw, int ld_raw, const uint16_t* dout, int ld_dout, uint16_t* draw, int ld_draw, int M,
