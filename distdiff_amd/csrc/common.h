@@ -87,3 +87,33 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// One 1 KB LDS-DMA piece: buffer_load_dwordx4 ... lds from base + voff (per lane) + soff (scalar); a lane whose voff is beyond the
+// 4 GB - 256 B range gets zeros written to its LDS slot (hardware range check) -- that is how padding taps and ragged rows are
+// staged.  The resource builtins only exist in the device pass (a kernel template that names them loses its host stub otherwise).
+__device__ __forceinline__ void dma16(const void* base, void* lds, unsigned voff, unsigned soff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0xffffff00u, 0x00020000);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
+#endif
+}
+
+// sum over the 16 lanes of a DPP row (the 16 pixel rows of an MFMA tile); every lane of the row receives the total
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float row16_sum(float v) {
+  v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
+  v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
+  v = dpp_add<0x141>(v);   // row_half_mirror
+  v = dpp_add<0x140>(v);   // row_mirror
+  return v;
+}
+
+// Host: grid of the persistent kernels that run one workgroup per CU -- the device's CU count rounded down to whole XCD rounds of 8
+// (256 on an MI355X, which is also what a process without a device plans with).  Read once per process.
+inline int persistent_cus() {
+  static const int cus = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 8 ? n & ~7 : 8; }();
+  return cus;
+}

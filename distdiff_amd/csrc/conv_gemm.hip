@@ -13,7 +13,7 @@
 // The MFMA is issued "swapped" (A = weight rows, B = pixel rows) so each lane owns 4 consecutive
 // output channels of one pixel: epilogue loads/stores are 8-byte (bf16x4) / 16-byte (fp32x4) vectors.
 #include "common.h"
-#include "kernels.h"
+#include "conv_dispatch.h"
 #include "conv_epilogue.h"
 
 namespace {
@@ -274,18 +274,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(ConvGemmParams p) {
 
 }  // namespace
 
-int conv_gemm_big_config(int M, int N, int K, int flags);
-int conv_halo_config(const ConvGemmParams& p);           // conv_halo.hip: 0, or the tile form of the halo-resident 3x3 kernel
-int conv_halo_split(const ConvGemmParams& p);            // conv_halo.hip: chunk split of the 8 x 8 level (1: none)
-hipError_t launch_conv_halo(const ConvGemmParams& p, int tn, hipStream_t stream);
-int gemm_pp_config(const ConvGemmParams& p);             // conv_halo.hip: pointwise ping-pong GEMM (narrow N)
-hipError_t launch_gemm_pp(const ConvGemmParams& p, int tn, hipStream_t stream);
-int gemm_ws_config(const ConvGemmParams& p);             // gemm_ws.hip: weight-stationary GEMM (K = 320 pointwise layers)
-int gemm_ws_rowstat_spans(const ConvGemmParams& p);
-hipError_t launch_gemm_ws(const ConvGemmParams& p, int tn, hipStream_t stream);
-void conv_gemm_big_tile(int cfg, int* bm, int* bn);
-hipError_t launch_conv_gemm_big(const ConvGemmParams& p, int cfg, hipStream_t stream);
-
 static int small_split(int M, int N, int K) {
   // 128x128 (or 256x64) tiles: split K when the grid is small and K is deep
   const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
@@ -297,10 +285,12 @@ static int small_split(int M, int N, int K) {
   if (s < 1) s = 1;
   return s;
 }
+static int big_tiles(int cfg, int M, int N) {
+  const BigForm& f = BIG_FORMS[cfg];
+  return ((M + f.bm() - 1) / f.bm()) * ((N + f.bn() - 1) / f.bn());
+}
 static int big_split(int cfg, int M, int N, int K) {
-  int bm, bn;
-  conv_gemm_big_tile(cfg, &bm, &bn);
-  const int tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+  const int tiles = big_tiles(cfg, M, N);
   const int ksteps = K / 64;
   if (tiles >= 200) return 1;
   int s = (256 + tiles - 1) / tiles;
@@ -332,18 +322,13 @@ int conv_gemm_pick_split(int M, int N, int K) {
   return s;
 }
 
-// kernel / split-K selection shared by the launcher and conv_gemm_can_emit_stats
+// form (conv_gemm_big_kernel configuration, 0: conv_gemm_kernel) and split-K of the general kernels
 static void select_config(const ConvGemmParams& p, size_t partial_cap_bytes, int* cfg_out, int* split_out) {
   const int ksteps = p.K / 64;
   int cfg = ((p.force_small & 1) ? 0 : conv_gemm_big_config(p.M, p.N, p.K, p.flags));
-  if (cfg && p.ksplit <= 0) {
-    // the persistent kernel runs one 8-wave workgroup per CU: it needs >= ~3/4 of the 256 CUs busy, else the
-    // 128x128 kernel (2-3 workgroups per CU, more of them) wins
-    int bm, bn;
-    conv_gemm_big_tile(cfg, &bm, &bn);
-    const int items = ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * big_split(cfg, p.M, p.N, p.K);
-    if (items < 192) cfg = 0;
-  }
+  // the persistent kernel runs one 8-wave workgroup per CU: it needs >= ~3/4 of the 256 CUs busy, else the
+  // 128x128 kernel (2-3 workgroups per CU, more of them) wins
+  if (cfg && p.ksplit <= 0 && big_tiles(cfg, p.M, p.N) * big_split(cfg, p.M, p.N, p.K) < 192) cfg = 0;
   int split = p.ksplit > 0 ? p.ksplit : (cfg ? big_split(cfg, p.M, p.N, p.K) : small_split(p.M, p.N, p.K));
   while (split > 1 && (size_t)split * p.M * p.N * sizeof(float) > partial_cap_bytes) --split;
   if (!p.partial) split = 1;
@@ -351,64 +336,47 @@ static void select_config(const ConvGemmParams& p, size_t partial_cap_bytes, int
   *split_out = nonempty_split(split, ksteps);
 }
 
-bool conv_gemm_can_emit_stats(ConvGemmParams p, size_t partial_cap_bytes) {
-  if ((p.K & 63) || p.M <= 0 || p.N <= 0 || (p.M & 63) || (p.N & 7) || (p.y_ld & 7)) return false;
+// What every kernel that honours CF_STATS / CF_ROWSTATS asks of the problem besides its own *_config (which kernels do: the flag lists
+// there).  CF_STATS: whole 64-row blocks, 16-byte stores of plain bf16 rows.
+static bool stats_shape_ok(const ConvGemmParams& p) {
+  if ((p.M & 63) || (p.N & 7) || (p.y_ld & 7)) return false;
   if (p.flags & (CF_GEGLU | CF_OUT_F32 | CF_MASK | CF_RES_F32)) return false;
-  if ((p.flags & CF_RES) && (p.res_ld & 7)) return false;
-  { ConvGemmParams q = p; q.flags |= CF_STATS; if (conv_halo_config(q) || gemm_pp_config(q)) return true; }
-  int cfg, split;
-  select_config(p, partial_cap_bytes, &cfg, &split);
-  if (!cfg || split != 1) return false;
-  return true;
+  return !((p.flags & CF_RES) && (p.res_ld & 7));
 }
-
-int conv_gemm_big_rowstat_span(int cfg);
-
-bool conv_gemm_can_emit_rowstats(ConvGemmParams p, size_t partial_cap_bytes, int* spans) {
-  if ((p.K & 63) || p.M <= 0 || p.N <= 0 || (p.N & 7) || (p.y_ld & 7)) return false;
+// CF_ROWSTATS: the batched epilogues of the pointwise forms only (fast staging: Cin % 64 == 0, one tap, no upsample, the whole input
+// within 32-bit byte offsets), one statistics epilogue per launch
+static bool rowstats_shape_ok(const ConvGemmParams& p) {
+  if ((p.N & 7) || (p.y_ld & 7)) return false;
   if (p.flags & (CF_GEGLU | CF_OUT_F32 | CF_MASK | CF_RES_F32 | CF_STATS | CF_LNFOLD)) return false;
   if ((p.flags & CF_RES) && (p.res_ld & 7)) return false;
-  // the batched epilogue of the two-workgroup pointwise forms only (fast staging: Cin % 64 == 0, one tap, no upsample)
   if ((p.cin & 63) || p.shift || p.ntaps != 1 || p.stride != 1 || p.H != p.Ho || p.W != p.Wo) return false;
-  if ((size_t)p.B * p.H * p.W * (size_t)p.x_ld * 2 >= 0xF0000000ull) return false;
-  { ConvGemmParams q = p; q.flags |= CF_ROWSTATS;
-    if (gemm_ws_config(q)) { if (spans) *spans = gemm_ws_rowstat_spans(q); return true; }
-    if (gemm_pp_config(q)) { if (spans) *spans = p.N / 80; return true; } }
-  int cfg, split;
-  select_config(p, partial_cap_bytes, &cfg, &split);
-  const int span = cfg ? conv_gemm_big_rowstat_span(cfg) : 0;
-  if (!span || split != 1 || p.N % (2 * span)) return false;
-  if (spans) *spans = p.N / span;
-  return true;
+  return (size_t)p.B * p.H * p.W * (size_t)p.x_ld * 2 < 0xF0000000ull;
 }
 
-int conv_halo_kernel_kind(const ConvGemmParams& p, int tn);   // conv_halo.hip: 1 conv_halo_kernel, 2 conv_halo_persist_kernel, 0 launch_conv_halo refuses
-
-// The launcher's decision, in one place: launch_conv_gemm acts on it, conv_gemm_kind reports it.  On return p is the problem as the chosen
-// kernel gets it (ksplit set; partial dropped when the 8 x 8 chunk split does not fit the scratch).
-enum { PLAN_GENERAL = 0, PLAN_HALO = 1, PLAN_WS = 3, PLAN_PPS = 4, PLAN_EMPTY = 5, PLAN_GROUPED = 6 };
-struct ConvPlan { int path, tn, cfg, split, narrow; };   // narrow: the small kernel's 256 x 64 tiles instead of 128 x 128
-static hipError_t conv_gemm_plan(ConvGemmParams& p, size_t partial_cap_bytes, ConvPlan* pl) {
-  pl->path = PLAN_EMPTY; pl->tn = 0; pl->cfg = 0; pl->split = 1; pl->narrow = 0;
+// The launcher's decision, in one place and in this order: refusal, path, form inside the path, split, and whether CF_STATS / CF_ROWSTATS
+// are honoured (with how many row spans).  launch_conv_gemm acts on it, conv_gemm_plan_query reports it, conv_gemm_can_emit_* ask it with
+// the flag set.  Only the buffers of the two statistics flags are not looked at here (conv_gemm_plan).  On return p is the problem as the
+// chosen kernel gets it (ksplit set; partial dropped when the 8 x 8 chunk split does not fit the scratch).
+static hipError_t plan_problem(ConvGemmParams& p, size_t partial_cap_bytes, ConvPlan* pl) {
+  *pl = ConvPlan{KIND_GENERAL, 0, 1, 0, false, false, 0};
+  const bool stats = (p.flags & CF_STATS) != 0, rowstats = (p.flags & CF_ROWSTATS) != 0;
   if (p.K & 63) return hipErrorInvalidValue;
   if ((p.flags & CF_LNFOLD) && (!p.ln_stats || !p.ln_c1 || p.ntaps != 1)) return hipErrorInvalidValue;
-  if (p.flags & CF_ROWSTATS) {
-    int spans = 0;
-    if (!p.rowpart || !conv_gemm_can_emit_rowstats(p, partial_cap_bytes, &spans) || p.rowpart_ld < spans) return hipErrorInvalidValue;
-  }
   // the kernels index the input with 32-bit element offsets (outputs and residuals use 64-bit offsets)
   if ((size_t)p.B * p.H * p.W * (size_t)p.x_ld >= 0xFFFF0000ull) return hipErrorInvalidValue;
-  if (p.M <= 0 || p.N <= 0) return hipSuccess;
-  if ((p.flags & CF_STATS) && (!p.stats || !conv_gemm_can_emit_stats(p, partial_cap_bytes))) return hipErrorInvalidValue;
+  if (p.M <= 0 || p.N <= 0) {
+    if (rowstats) return hipErrorInvalidValue;             // (no rows to describe: refused; CF_STATS is accepted and writes nothing)
+    pl->empty = true;
+    return hipSuccess;
+  }
+  if ((stats && !stats_shape_ok(p)) || (rowstats && !rowstats_shape_ok(p))) return hipErrorInvalidValue;
   if (p.wgroup_rows > 0) {
     // grouped weights (a batch of GEMMs stacked along M): the persistent big-tile kernel only, whole tiles per group, no split-K
     int cfg, split;
     select_config(p, 0, &cfg, &split);
-    int bm = 0, bn = 0;
-    if (cfg) conv_gemm_big_tile(cfg, &bm, &bn);
-    if (!cfg || split != 1 || p.wgroup_rows % bm || p.ntaps != 1 || (p.flags & ~(CF_OUT_F32 | CF_BIAS))) return hipErrorInvalidValue;
+    if (!cfg || split != 1 || p.wgroup_rows % BIG_FORMS[cfg].bm() || p.ntaps != 1 || (p.flags & ~(CF_OUT_F32 | CF_BIAS))) return hipErrorInvalidValue;
     p.ksplit = 1;
-    pl->path = PLAN_GROUPED; pl->cfg = cfg;
+    pl->form = cfg;
     return hipSuccess;
   }
   {
@@ -416,100 +384,105 @@ static hipError_t conv_gemm_plan(ConvGemmParams& p, size_t partial_cap_bytes, Co
     ConvGemmParams q = p;
     const int hs = conv_halo_split(q);
     if (hs > 1 && (size_t)hs * p.M * p.N * sizeof(float) > partial_cap_bytes) q.partial = nullptr;     // scratch too small: no split form
-    if (const int tn = conv_halo_config(q)) {
-      q.ksplit = conv_halo_split(q) > 1 ? hs : q.ksplit;
+    if (const int form = conv_halo_config(q)) {
+      if (conv_halo_split(q) > 1) { q.ksplit = hs; pl->split = hs; }
       p = q;
-      pl->path = PLAN_HALO; pl->tn = tn;
-      return hipSuccess;
+      pl->kind = conv_halo_kernel_kind(p, form); pl->form = form; pl->stats = stats;
+      return pl->kind ? hipSuccess : hipErrorInvalidValue;
     }
   }
-  if (const int tn = gemm_ws_config(p)) { pl->path = PLAN_WS; pl->tn = tn; return hipSuccess; }     // K = 320 pointwise layers: weight-stationary GEMM
-  if (const int tn = gemm_pp_config(p)) { pl->path = PLAN_PPS; pl->tn = tn; return hipSuccess; }    // narrow pointwise layers: ping-pong GEMM
-  select_config(p, partial_cap_bytes, &pl->cfg, &pl->split);
+  // K = 320 pointwise layers: weight-stationary GEMM.  It has no residual and no GroupNorm-partials epilogue (gemm_ws_config refuses
+  // CF_RES and CF_STATS), so the SAME problem with CF_STATS set is not refused but moves on to the ping-pong GEMM below, which has both.
+  if (const int tn = gemm_ws_config(p)) {
+    pl->kind = KIND_WS; pl->form = tn; pl->row_spans = rowstats ? gemm_ws_rowstat_spans(p) : 0;
+    return hipSuccess;
+  }
+  // narrow-N pointwise layers (N % 320 == 0, GEGLU N % 256 == 0): persistent ping-pong GEMM
+  if (const int tn = gemm_pp_config(p)) {
+    pl->kind = KIND_PPS; pl->form = tn; pl->stats = stats; pl->row_spans = rowstats ? gemm_pp_rowstat_spans(p) : 0;
+    return hipSuccess;
+  }
+  // everything else: conv_gemm_big_kernel, or conv_gemm_kernel for small grids.  The statistics epilogues exist in the big kernel's
+  // unsplit forms (CF_ROWSTATS: its two-workgroup forms, whole pairs of wave spans)
+  select_config(p, partial_cap_bytes, &pl->form, &pl->split);
   p.ksplit = pl->split;
-  pl->narrow = (!pl->cfg && (p.N % 128) != 0 && (p.N % 128) <= 64 && p.M >= 256) ? 1 : 0;
-  pl->path = PLAN_GENERAL;
+  pl->narrow = (!pl->form && (p.N % 128) != 0 && (p.N % 128) <= 64 && p.M >= 256) ? 1 : 0;
+  if (stats && (!pl->form || pl->split != 1)) return hipErrorInvalidValue;
+  if (rowstats) {
+    const int span = BIG_FORMS[pl->form].rowstat_span;
+    if (!span || pl->split != 1 || p.N % (2 * span)) return hipErrorInvalidValue;
+    pl->row_spans = p.N / span;
+  }
+  pl->stats = stats;
   return hipSuccess;
 }
 
-// The kernel launch_conv_gemm(p, partial_cap_bytes) would run, without launching: 0 conv_gemm_kernel / conv_gemm_big_kernel, 1 conv_halo_kernel,
-// 2 conv_halo_persist_kernel, 3 gemm_ws_kernel, 4 gemm_pps_kernel; -1 when the launcher would refuse the problem
-int conv_gemm_kind(ConvGemmParams p, size_t partial_cap_bytes) {
-  ConvPlan pl;
-  if (conv_gemm_plan(p, partial_cap_bytes, &pl) != hipSuccess) return -1;
-  if (pl.path == PLAN_HALO) { const int k = conv_halo_kernel_kind(p, pl.tn); return k ? k : -1; }
-  return pl.path == PLAN_WS || pl.path == PLAN_PPS ? pl.path : 0;
+// plan_problem + the buffers the statistics flags need
+static hipError_t conv_gemm_plan(ConvGemmParams& p, size_t partial_cap_bytes, ConvPlan* pl) {
+  const hipError_t e = plan_problem(p, partial_cap_bytes, pl);
+  if (e != hipSuccess) return e;
+  if (pl->stats && !p.stats) return hipErrorInvalidValue;
+  if (pl->row_spans && (!p.rowpart || p.rowpart_ld < pl->row_spans)) return hipErrorInvalidValue;
+  return hipSuccess;
 }
 
-// conv_gemm_kind plus the form inside the kind: out4 = {kind, configuration of conv_gemm_big_kernel (0: conv_gemm_kernel; 1 128 x 256,
-// 2 256 x 160, 3 256 x 128 on 8 waves; 4 128 x 160, 5 128 x 128 as two 4-wave workgroups), split-K / chunk split the launch uses,
-// 1 when conv_gemm_kernel runs its 256 x 64 tiles instead of 128 x 128}
+bool conv_gemm_can_emit_stats(ConvGemmParams p, size_t partial_cap_bytes) {
+  ConvPlan pl;
+  p.flags |= CF_STATS;
+  return plan_problem(p, partial_cap_bytes, &pl) == hipSuccess && pl.stats;
+}
+
+bool conv_gemm_can_emit_rowstats(ConvGemmParams p, size_t partial_cap_bytes, int* spans) {
+  ConvPlan pl;
+  p.flags |= CF_ROWSTATS;
+  if (plan_problem(p, partial_cap_bytes, &pl) != hipSuccess || !pl.row_spans) return false;
+  if (spans) *spans = pl.row_spans;
+  return true;
+}
+
 int conv_gemm_plan_query(ConvGemmParams p, size_t partial_cap_bytes, int* out4) {
   ConvPlan pl;
   if (conv_gemm_plan(p, partial_cap_bytes, &pl) != hipSuccess) return -1;
-  int kind = pl.path == PLAN_WS || pl.path == PLAN_PPS ? pl.path : 0;
-  if (pl.path == PLAN_HALO) { kind = conv_halo_kernel_kind(p, pl.tn); if (!kind) return -1; }
-  if (out4) { out4[0] = kind; out4[1] = pl.cfg; out4[2] = pl.path == PLAN_HALO ? (p.ksplit > 1 ? p.ksplit : 1) : pl.split; out4[3] = pl.narrow; }
-  return kind;
+  if (out4) { out4[0] = pl.kind; out4[1] = pl.kind == KIND_GENERAL ? pl.form : 0; out4[2] = pl.split; out4[3] = pl.narrow; }
+  return pl.kind;
+}
+
+int conv_gemm_kind(ConvGemmParams p, size_t partial_cap_bytes) { return conv_gemm_plan_query(p, partial_cap_bytes, nullptr); }
+
+// adds the split's fp32 partial sums and applies the epilogue
+static hipError_t launch_splitk_reduce(const ConvGemmParams& p, hipStream_t stream) {
+  const int ncols = (p.flags & CF_GEGLU) ? p.N / 2 : p.N;
+  const size_t total = (size_t)p.M * ((ncols + 3) / 4);
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
+  return hipGetLastError();
 }
 
 hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStream_t stream) {
   ConvPlan pl;
-  const hipError_t pe = conv_gemm_plan(p, partial_cap_bytes, &pl);
-  if (pe != hipSuccess) return pe;
-  if (pl.path == PLAN_EMPTY) return hipSuccess;
-  if (pl.path == PLAN_GROUPED) return launch_conv_gemm_big(p, pl.cfg, stream);
-  if (pl.path == PLAN_HALO) {
-    hipError_t e = launch_conv_halo(p, pl.tn, stream);
-    if (e == hipSuccess && p.ksplit > 1) {
-      const size_t total = (size_t)p.M * ((p.N + 3) / 4);
-      int blocks = (int)((total + 255) / 256);
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
-      e = hipGetLastError();
+  hipError_t e = conv_gemm_plan(p, partial_cap_bytes, &pl);
+  if (e != hipSuccess || pl.empty) return e;
+  if (pl.kind == KIND_WS) return launch_gemm_ws(p, pl.form, stream);
+  if (pl.kind == KIND_PPS) return launch_gemm_pp(p, pl.form, stream);
+  if (pl.kind == KIND_HALO || pl.kind == KIND_HALO_PERSIST) e = launch_conv_halo(p, pl.form, pl.kind, stream);
+  else if (pl.form) e = launch_conv_gemm_big(p, pl.form, stream);
+  else {
+    static bool attr_done = false;
+    if (!attr_done) {
+      hipFuncSetAttribute((const void*)conv_gemm_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 64) * 128);
+      hipFuncSetAttribute((const void*)conv_gemm_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 128) * 128);
+      attr_done = true;
     }
-    return e;
-  }
-  if (pl.path == PLAN_WS) return launch_gemm_ws(p, pl.tn, stream);
-  if (pl.path == PLAN_PPS) return launch_gemm_pp(p, pl.tn, stream);
-  const int cfg = pl.cfg, split = pl.split;
-  if (cfg) {
-    hipError_t e = launch_conv_gemm_big(p, cfg, stream);
-    if (e != hipSuccess) return e;
-    if (split > 1) {
-      const int ncols = (p.flags & CF_GEGLU) ? p.N / 2 : p.N;
-      const size_t total = (size_t)p.M * ((ncols + 3) / 4);
-      int blocks = (int)((total + 255) / 256);
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
-      e = hipGetLastError();
+    if (pl.narrow) {
+      const int ntm = (p.M + 255) / 256, ntn = (p.N + 63) / 64;
+      hipLaunchKernelGGL((conv_gemm_kernel<4, 1>), dim3(ntm * ntn, pl.split), dim3(256), 2 * (256 + 64) * 128, stream, p);
+    } else {
+      const int ntm = (p.M + 127) / 128, ntn = (p.N + 127) / 128;
+      hipLaunchKernelGGL((conv_gemm_kernel<2, 2>), dim3(ntm * ntn, pl.split), dim3(256), 2 * (128 + 128) * 128, stream, p);
     }
-    return e;
-  }
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)conv_gemm_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 64) * 128);
-    hipFuncSetAttribute((const void*)conv_gemm_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 128) * 128);
-    attr_done = true;
-  }
-  if (pl.narrow) {
-    const int ntm = (p.M + 255) / 256, ntn = (p.N + 63) / 64;
-    dim3 grid(ntm * ntn, split);
-    hipLaunchKernelGGL((conv_gemm_kernel<4, 1>), grid, dim3(256), 2 * (256 + 64) * 128, stream, p);
-  } else {
-    const int ntm = (p.M + 127) / 128, ntn = (p.N + 127) / 128;
-    dim3 grid(ntm * ntn, split);
-    hipLaunchKernelGGL((conv_gemm_kernel<2, 2>), grid, dim3(256), 2 * (128 + 128) * 128, stream, p);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (split > 1) {
-    const int ncols = (p.flags & CF_GEGLU) ? p.N / 2 : p.N;
-    const size_t total = (size_t)p.M * ((ncols + 3) / 4);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
     e = hipGetLastError();
   }
+  if (e == hipSuccess && pl.split > 1) e = launch_splitk_reduce(p, stream);
   return e;
 }

@@ -14,9 +14,8 @@
 //     dealt to XCDs in contiguous chunks (blocks b, b+8, ... share an L2) with n-tiles fastest.
 //   * Epilogue: paired output columns -> 16-byte residual loads / stores; a batched form (FE) for short items, the generic
 //     Epi::apply form for deep / split-K items (its instantiation has the faster K loop).
-#include <cstdlib>
 #include "common.h"
-#include "kernels.h"
+#include "conv_dispatch.h"
 #include "conv_epilogue.h"
 
 namespace {
@@ -33,29 +32,6 @@ __device__ __forceinline__ void trace_stamp(int& n, int tag) {
   }
 }
 #endif   // zero page for padded taps / ragged rows (device globals are zero-initialised)
-
-// One 1 KB LDS-DMA piece: buffer_load_dwordx4 ... lds from base + voff (per lane) + soff (scalar); a lane whose voff is beyond the
-// 4 GB - 256 B range gets zeros written to its LDS slot (hardware range check) -- that is how padding taps and ragged rows are
-// staged.  The resource builtins only exist in the device pass (a kernel template that names them loses its host stub otherwise).
-__device__ __forceinline__ void dma16(const void* base, void* lds, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0xffffff00u, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-#endif
-}
-
-// sum over the 16 lanes of a DPP row (the 16 pixel rows of an MFMA tile); every lane of the row receives the total
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
-  v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
-  v = dpp_add<0x141>(v);   // row_half_mirror
-  v = dpp_add<0x140>(v);   // row_mirror
-  return v;
-}
 
 // FM: 1 = fast staging path only (Cin % 64 == 0, no fused upsample / dilation, <= 32 taps: buffer loads with scalar tap offsets),
 //     0 = general path only (per-lane address arithmetic, global_load_lds).  FE: batched epilogue compiled in.
@@ -717,7 +693,7 @@ hipError_t run_big_fe3(const ConvGemmParams& p, hipStream_t stream) {
 }
 template <int WM, int WN, int TM, int TN, int NS, bool FE, int FM>
 hipError_t run_big_fe2(const ConvGemmParams& p, hipStream_t stream) {
-  // the LayerNorm forms only exist for the batched epilogue of the two-workgroup (shallow-K, pointwise) tiles: conv_gemm_ln_form()
+  // the LayerNorm forms only exist for the batched epilogue of the two-workgroup (shallow-K, pointwise) tiles
   if constexpr (WM * WN == 4 && FE && FM == 1) {
     if ((p.flags & CF_LNFOLD) && p.K >= 192 && !(p.M & 1)) return run_big_fe3<WM, WN, TM, TN, NS, FE, FM, 3>(p, stream);
     if (p.flags & CF_ROWSTATS) return run_big_fe3<WM, WN, TM, TN, NS, FE, FM, 2>(p, stream);
@@ -744,6 +720,12 @@ hipError_t run_big(const ConvGemmParams& p, hipStream_t stream) {
   return p.ksplit == 1 ? run_big_fe<WM, WN, TM, TN, NS, true>(p, stream) : run_big_fe<WM, WN, TM, TN, NS, false>(p, stream);
 }
 
+template <int CFG>
+hipError_t run_big_form(const ConvGemmParams& p, hipStream_t stream) {
+  constexpr BigForm f = BIG_FORMS[CFG];
+  return run_big<f.wm, f.wn, f.tm, f.tn, f.ns>(p, stream);
+}
+
 }  // namespace
 
 #ifdef DD_TRACE
@@ -756,7 +738,7 @@ extern "C" int dd_debug_read_trace(unsigned long long* host, int n) {
 }
 #endif
 
-// tile choice for the big kernel: 0 = not applicable (use the 128x128 kernel), else config id
+// tile choice for the big kernel: 0 = not applicable (use the 128x128 kernel), else the configuration (index into BIG_FORMS)
 int conv_gemm_big_config(int M, int N, int K, int flags) {
   if (M < 1024 || N < 64 || K < 128) return 0;
   const bool geglu = (flags & CF_GEGLU) != 0;
@@ -774,22 +756,14 @@ int conv_gemm_big_config(int M, int N, int K, int flags) {
   return 0;
 }
 
-// columns per wave of a tile (the span of one CF_ROWSTATS partial): 0 unless the configuration has a row-statistics form
-int conv_gemm_big_rowstat_span(int cfg) { return cfg == 4 ? 80 : cfg == 5 ? 64 : 0; }
-
-void conv_gemm_big_tile(int cfg, int* bm, int* bn) {
-  *bm = (cfg == 1 || cfg == 4 || cfg == 5) ? 128 : 256;
-  *bn = cfg == 1 ? 256 : (cfg == 2 || cfg == 4) ? 160 : 128;
-}
-
 hipError_t launch_conv_gemm_big(const ConvGemmParams& p, int cfg, hipStream_t stream) {
   switch (cfg) {
-    // three LDS stages + counted vmcnt + partner waves one phase apart: +0..7 % over two stages in same-device A/B (tools/ab_conv.sh)
-    case 1: return run_big<2, 4, 4, 4, 3>(p, stream);    // 128 x 256, 8 waves
-    case 2: return run_big<4, 2, 4, 5, 3>(p, stream);    // 256 x 160, 8 waves
-    case 3: return run_big<4, 2, 4, 4, 3>(p, stream);    // 256 x 128, 8 waves
-    case 4: return run_big<2, 2, 4, 5, 2>(p, stream);    // 128 x 160, 4 waves, two workgroups per CU (shallow K)
-    case 5: return run_big<2, 2, 4, 4, 2>(p, stream);    // 128 x 128, 4 waves, two workgroups per CU (GEGLU / N % 128 == 0)
+    // (8 waves: three LDS stages + counted vmcnt + partner waves one phase apart: +0..7 % over two stages in same-device A/B, tools/ab_conv.sh)
+    case 1: return run_big_form<1>(p, stream);
+    case 2: return run_big_form<2>(p, stream);
+    case 3: return run_big_form<3>(p, stream);
+    case 4: return run_big_form<4>(p, stream);
+    case 5: return run_big_form<5>(p, stream);
     default: return hipErrorInvalidValue;
   }
 }

@@ -23,10 +23,9 @@
 // History: commit 7d952d8 is the first form (K split over the two waves of a SIMD, fp32 partial hand-off through LDS, a barrier per
 // 16-row step): parity green, slower than the ping-pong GEMM -- the finishing wave's epilogue serialised behind its own MFMAs.
 // tools/ws_trace.py (-DWS_TRACE stamps) and timing ablations are what the current form was derived from (profiles/r05_ws_*.txt).
-#include <cstdlib>
 #include <type_traits>
 #include "common.h"
-#include "kernels.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -296,7 +295,7 @@ hipError_t run_ws(const ConvGemmParams& p, hipStream_t stream) {
   const int lds = WS_AUX + 2 * BN * 4;
   static bool attr = false;
   if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_ws_kernel<TN, GEGLU, RS, RAW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
-  static const int cus = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 8 ? n & ~7 : 8; }();
+  const int cus = persistent_cus();
   const int per = cus / 8;                               // workgroups per XCD label
   const int CB = p.N / BN, RL = per / CB;
   hipLaunchKernelGGL((gemm_ws_kernel<TN, GEGLU, RS, RAW>), dim3(cus), dim3(512), lds, stream, p, CB, RL);
@@ -304,18 +303,17 @@ hipError_t run_ws(const ConvGemmParams& p, hipStream_t stream) {
 }
 
 }  // namespace
-// weight-stationary GEMM for K = 320 pointwise layers: 0 = not eligible, 5: 320-column blocks, 4: 256-column blocks (GEGLU)
+// weight-stationary GEMM for K = 320 pointwise layers: 0 = not eligible, 5: 320-column blocks, 4: 256-column blocks (GEGLU).  Epilogues: bias,
+// ReLU, CF_ROWSTATS, CF_LNFOLD; GEGLU with bias, raw stash and CF_LNFOLD -- no residual and no CF_STATS (see the header)
 int gemm_ws_config(const ConvGemmParams& p) {
-  static const int on = getenv("DD_GEMM_WS") ? atoi(getenv("DD_GEMM_WS")) : 1;
   constexpr int mmin = 32768;
-  static const int mask = getenv("DD_GEMM_WS_MASK") ? atoi(getenv("DD_GEMM_WS_MASK")) : 15;   // diagnostics: 1 GEGLU, 2 row statistics, 4 LayerNorm-folded, 8 the rest
-  if (!on || p.force_small) return 0;
+  const int mask = conv_env().gemm_ws_mask;               // diagnostics: 1 GEGLU, 2 row statistics, 4 LayerNorm-folded, 8 the rest
+  if (!conv_env().gemm_ws || p.force_small) return 0;
   if (!(mask & ((p.flags & CF_GEGLU) ? 1 : (p.flags & CF_ROWSTATS) ? 2 : (p.flags & CF_LNFOLD) ? 4 : 8))) return 0;
   if (p.ntaps != 1 || p.stride != 1 || p.shift || p.parity || p.H != p.Ho || p.W != p.Wo || p.cin != 320 || p.K != 320) return 0;
   if ((p.M & 63) || p.M < mmin || p.ksplit > 1 || p.bias_sel || (p.x_ld & 7) || (p.y_ld & 7)) return 0;
   if ((size_t)64 * p.x_ld * 2 >= 0xF0000000ull) return 0;
-  static const int cus = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 8 ? n & ~7 : 8; }();
-  const int per = cus / 8;
+  const int per = persistent_cus() / 8;
   if (p.flags & CF_GEGLU) {
     if (p.flags & ~(CF_BIAS | CF_GEGLU | CF_GEGLU_RAW | CF_LNFOLD)) return 0;
     if ((p.N & 255) || p.N / 256 > per || ((p.flags & CF_GEGLU_RAW) && (p.raw_ld & 3))) return 0;

@@ -344,7 +344,7 @@ def test_layernorm_folded_into_linear(ops, M, Cc, N, geglu):
     statistics -- the transformer blocks' LayerNorm -> QKV / to_q / GEGLU projections (diffusers BasicTransformerBlock).
     Checked against torch's layer_norm + linear on the same bf16 inputs (the folded form never rounds LayerNorm(x) to bf16, so it is
     the more accurate of the two); M = 300 takes the small kernel's generic epilogue, M = 49152 (>= 192 tiles of 256 rows, N <= 1280) the
-    ping-pong GEMM of conv_halo.hip (GEGLU: its 256 x 256 form, a ragged number of tiles per persistent workgroup), the others the batched
+    ping-pong GEMM of gemm_pps.hip (GEGLU: its 256 x 256 form, a ragged number of tiles per persistent workgroup), the others the batched
     two-workgroup forms."""
     g = torch.Generator().manual_seed(77)
     x = bf(torch.randn(M, Cc, generator=g) * 1.7 + torch.randn(M, 1, generator=g) * 0.8)      # row means of the size of the row std

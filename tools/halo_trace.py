@@ -27,7 +27,7 @@ def run(name, B, H, Cin, Cout, res=False):
     torch.cuda.synchronize()
     tiles = min((M // 512) * (Cout // 128), 8192)
     buf = (ctypes.c_ulonglong * (tiles * 6))()
-    L.dd_debug_read_pp_trace(buf, tiles * 6)
+    L.dd_debug_read_halo_trace(buf, tiles * 6)
     rec = [[buf[i * 6 + j] for j in range(5)] for i in range(tiles)]
     rec = [r_ for r_ in rec if r_[4] > r_[0] > 0]
     n = len(rec)

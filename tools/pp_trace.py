@@ -1,4 +1,4 @@
-"""Per-workgroup timeline of gemm_pp_kernel (debug build into ab/: tools/build_variant.sh trace conv_halo.hip -DDD_TRACE, run with DD_LIB):
+"""Per-workgroup timeline of gemm_pps_kernel (debug build into ab/: tools/build_variant.sh trace gemm_pps.hip -DDD_TRACE, run with DD_LIB):
 per tile: wait for its first K-step -> K loop -> epilogue of the persistent kernel."""
 import collections, ctypes, math, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
