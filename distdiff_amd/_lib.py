@@ -96,6 +96,7 @@ OPS_SYMBOLS = [
     "dd_op_conv_gemm", "dd_op_conv_gemm_kind", "dd_op_conv_gemm_plan", "dd_op_conv_gemm_check", "dd_op_groupnorm_fwd", "dd_op_groupnorm_bwd", "dd_op_groupnorm_scratch_bytes",
     "dd_op_layernorm_fwd", "dd_op_layernorm_bwd", "dd_op_attention_fwd", "dd_op_attention_bwd",
     "dd_op_attention_gemm_workspace", "dd_op_attention_gemm_fwd", "dd_op_attention_gemm_bwd",
+    "dd_op_attention", "dd_op_attention_plan", "dd_op_attention_scratch_bytes",
     "dd_pack_conv_weight", "dd_op_conv_f32", "dd_pack_conv_weight_f32", "dd_op_nchw_f32_to_nhwc_bf16", "dd_op_nhwc_to_nchw_f32", "dd_op_cfg_ddim",
     "dd_op_cfg_ddim_bwd", "dd_op_sumpool2x2", "dd_op_geglu_bwd", "dd_op_maxpool3x3s2", "dd_op_maxpool3x3s2_bwd",
     "dd_op_bicubic", "dd_op_bicubic_bwd", "dd_op_gap", "dd_op_energy", "dd_op_transform_update", "dd_op_affine",
@@ -128,6 +129,10 @@ def _declare(l):
     l.dd_op_layernorm_bwd.argtypes = [C.POINTER(LayerNormParams), vp]
     l.dd_op_attention_fwd.argtypes = [C.POINTER(AttnParams), vp]
     l.dd_op_attention_bwd.argtypes = [C.POINTER(AttnParams), vp]
+    l.dd_op_attention.argtypes = [C.POINTER(AttnParams), vp, sz, vp, vp, sz, i, vp]
+    l.dd_op_attention_plan.argtypes = [C.POINTER(AttnParams), sz, i, vp]
+    l.dd_op_attention_scratch_bytes.argtypes = [i] * 8
+    l.dd_op_attention_scratch_bytes.restype = sz
     l.dd_pack_conv_weight.argtypes = [vp, i, i, i, i, i, i, i, vp, vp, vp]
     l.dd_op_conv_f32.argtypes = [C.POINTER(ConvF32Params), vp]
     l.dd_pack_conv_weight_f32.argtypes = [vp, i, i, i, i, i, i, i, vp, vp, vp]

@@ -17,36 +17,11 @@
 #include <type_traits>
 #include "common.h"
 #include "kernels.h"
+#include "attention_dispatch.h"
+#include "attention_frag.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-
-__device__ __forceinline__ bf16x8 lds_row_frag(const unsigned char* base, int row, int S, int slot) {
-  return *(const bf16x8*)(base + row * S + slot * 16);
-}
-// 8 k-values (permuted order, see header) of column `col16 + (lane&15)`: rows r0 + 4*(lane>>4) + {0..3} and +16
-__device__ __forceinline__ bf16x8 lds_col_frag(const unsigned char* base, int r0, int S, int col16, int lane) {
-  const int i = lane & 15, g = lane >> 4;
-  const unsigned char* a = base + (r0 + 4 * g + (i >> 2)) * S + (col16 * 16 + 4 * (i & 3)) * 2;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * S));
-  s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-// Maxima of MFMA results as single instructions the COMPILER sees: fmaxf() makes it put a canonicalising v_max_f32 v, v, v in front of
-// every operand that comes out of an MFMA, and an inline-asm v_max3_f32 (round 3) is invisible to its hazard recogniser -- nothing then
-// guarantees the wait states between an MFMA and a vector instruction that reads its result, and with one MFMA per score tile (d = 32)
-// the asm read registers the MFMA had not written yet (NaN outputs; found with tools/attn_dbg.py).  v_med3_f32(a, b, +inf) = max(a, b) is
-// a target intrinsic: no canonicalisation, hazards handled.  The maxima only run in the first key tile and the safe sweep now.
-__device__ __forceinline__ float vmax2(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, __builtin_inff()); }
-__device__ __forceinline__ float vmax3(float a, float b, float c) { return vmax2(vmax2(a, b), c); }
-__device__ __forceinline__ bf16x8 pack_frag(const f32x4& a, const f32x4& b) {
-  uint4 u;
-  u.x = pack2bf(a[0], a[1]); u.y = pack2bf(a[2], a[3]); u.z = pack2bf(b[0], b[1]); u.w = pack2bf(b[2], b[3]);
-  return __builtin_bit_cast(bf16x8, u);
-}
 // stage ROWS x DPK bf16 (zero padded beyond D columns / nvalid rows) into LDS with row stride S bytes
 // ONES: column D of the tile (a padding column) is set to 1.0, so that P.V also accumulates the softmax row sums (forward V tile)
 template <int ROWS, int DPK, bool ONES = false>
@@ -97,8 +72,6 @@ __device__ __forceinline__ void load_row_frags(bf16x8* f, const bf16_t* g, bool 
     f[ks] = __builtin_bit_cast(bf16x8, v);
   }
 }
-
-constexpr float LOG2E = 1.4426950408889634f;
 
 // ------------------------------------------------------------------------------------------------
 // forward.  grid (ceil(Nq / QB), H, B), 256 threads. DSPLIT=1: each wave owns QT 16-query tiles;
@@ -292,18 +265,6 @@ __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams 
 // 1.0 that makes P.V deliver the softmax row sums (ONES).  Row strides (96 B at d <= 40, 160 B at d = 64 / 80) are bank-conflict free for
 // the ds_read_b128 row fragments and the ds_read_b64_tr_b16 column fragments (tools/lds_conflicts.py).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void adma16(const void* base, void* lds, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0xffffff00u, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-#endif
-}
-template <int D>
-struct AttnDmaGeo {
-  static constexpr int DPK = (D + 31) / 32 * 32;
-  static constexpr int RB = D <= 40 ? 96 : D <= 80 ? 160 : DPK * 2 + 32;     // LDS row bytes (d = 64 / 80: no padding granule, or none past column 79: the over-read of the last K-step lands in the next row)
-  static constexpr int RG = RB / 16, DG = D / 8;             // granules per row, data granules
-};
 // NW waves per workgroup (4 or 8: eight waves share one K/V ring, half the DMA instructions per query; same waves per SIMD)
 // LZ ("lazy reference"): the scores leave the QK^T MFMAs as log2-domain differences to a per-row reference -- Q carries scale * log2(e),
 // the first MFMA of every score chain starts from -reference instead of 0 -- so p = exp2(score) needs no fma, and the reference only
@@ -323,7 +284,7 @@ typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 template <int D, int QT, int KT, int NW, bool LZ, bool FP8 = false>
 __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_kernel(AttnParams p) {
   static_assert(!FP8 || (D == 64 && KT == 128 && LZ), "fp8 P.V: d = 64, 128-key tiles, lazy-reference softmax");
-  using G = AttnDmaGeo<D>;
+  using G = AttnLdsGeo<D>;
   constexpr int DPK = G::DPK, KS = DPK / 32, DVT = (D + 15) / 16, S = G::RB, RG = G::RG, DG = G::DG;
   constexpr int NKT = KT / 16, NC = KT / 32;
   constexpr int QB = NW * QT * 16;
@@ -404,7 +365,7 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
         const bool isv = pc >= NPM;
         unsigned char* dst = smem + buf * 2 * TILE + (isv ? TILE : 0) + (isv ? pc - NPM : pc) * 1024;
         if (prow_[i] >= 0)                                   // rows behind the last key are zero-filled by the range check
-          adma16(isv ? vg : kg, dst, prow_[i] < nvalid ? voff[i] : OOR, (unsigned)k0 * (unsigned)(isv ? p.ldv : p.ldk) * 2u);
+          dma16(isv ? vg : kg, dst, prow_[i] < nvalid ? voff[i] : OOR, (unsigned)k0 * (unsigned)(isv ? p.ldv : p.ldk) * 2u);
       }
     }
   };
@@ -943,130 +904,183 @@ __global__ __launch_bounds__(256, DD_AW_DKV(D)) void attn_bwd_dkv_kernel(AttnPar
   }
 }
 
-template <int D, int QT, int KT, int DSPLIT, bool CAUSAL>
-hipError_t run_fwd2(const AttnParams& p, hipStream_t s) {
-  constexpr int DPK = (D + 31) / 32 * 32, S = DPK * 2 + 32;
-  constexpr int QB = (DSPLIT == 1 ? 4 : 1) * QT * 16;
-  constexpr size_t lds = 2 * KT * S;
-  static bool attr = false;
-  if (!attr) { hipFuncSetAttribute((const void*)attn_fwd_kernel<D, QT, KT, DSPLIT, CAUSAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  hipLaunchKernelGGL((attn_fwd_kernel<D, QT, KT, DSPLIT, CAUSAL>), dim3((p.Nq + QB - 1) / QB, p.H, p.B), dim3(256), lds, s, p);
-  return hipGetLastError();
-}
-template <int D, int QT, int KT, int NW, bool LZ, bool FP8 = false>
-hipError_t run_fwd_dma2(const AttnParams& p, hipStream_t s) {
-  constexpr int QB = NW * QT * 16;
-  constexpr size_t lds = 4 * KT * AttnDmaGeo<D>::RB + 128 + (FP8 ? 8192 : 0);
-  static bool attr = false;
-  if (!attr) { hipFuncSetAttribute((const void*)attn_fwd_dma_kernel<D, QT, KT, NW, LZ, FP8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  hipLaunchKernelGGL((attn_fwd_dma_kernel<D, QT, KT, NW, LZ, FP8>), dim3((p.Nq + QB - 1) / QB, p.H, p.B), dim3(NW * 64), lds, s, p);
-  return hipGetLastError();
-}
-template <int D, int QT, int KT, int NW>
-hipError_t run_fwd_dma(const AttnParams& p, hipStream_t s) {
-  return p.q_prescaled ? run_fwd_dma2<D, QT, KT, NW, true>(p, s) : run_fwd_dma2<D, QT, KT, NW, false>(p, s);
-}
-// the causal mask (CLIP text encoder, forward only) is a template flag: the UNet / VAE loops carry no per-score mask code
-template <int D, int QT, int KT, int DSPLIT>
-hipError_t run_fwd(const AttnParams& p, hipStream_t s) {
-  // LDS-DMA staging: head dims whose rows are whole 16-byte granules, key / value row pitches within the 32-bit offset of one batch image
-  if constexpr (DSPLIT == 1 && D % 8 == 0 && D <= 80 && (KT * AttnDmaGeo<D>::RG) % 64 == 0) {   // d = 160: the two-deep ring would cost a workgroup per CU
-    if (!p.causal && (size_t)p.Nk * (size_t)(p.ldk > p.ldv ? p.ldk : p.ldv) * 2 < 0xF0000000ull) {
-      if constexpr (D <= 40) { if (p.Nq % (8 * QT * 16) == 0) return run_fwd_dma<D, QT, KT, 8>(p, s); }
-      return run_fwd_dma<D, QT, KT, 4>(p, s);
+
+// ------------------------------------------------------------------------------------------------
+// host side: the kernels of one plan.  The causal mask (CLIP text encoder, forward only) and the prescaled query are template flags:
+// the UNet / VAE loops carry no per-score mask code
+// ------------------------------------------------------------------------------------------------
+template <int I>
+hipError_t launch_fwd_form(const AttnParams& p, const AttnPlan& plan, hipStream_t s) {
+  constexpr AttnForm F = ATTN_FORMS[I];
+  const AttnLaunch& l = plan.launch[0];
+  if (plan.route == ATTN_DMA) {
+    if constexpr (F.fp8) return launch_dyn_lds<attn_fwd_dma_kernel<F.d, F.qt, F.kt, 8, true, true>>(l.grid, l.block, l.lds, s, p);
+    else if constexpr (F.dma()) {
+      if constexpr (F.dma8()) {
+        if (plan.waves == 8)
+          return plan.lazy ? launch_dyn_lds<attn_fwd_dma_kernel<F.d, F.qt, F.kt, 8, true>>(l.grid, l.block, l.lds, s, p)
+                           : launch_dyn_lds<attn_fwd_dma_kernel<F.d, F.qt, F.kt, 8, false>>(l.grid, l.block, l.lds, s, p);
+      }
+      return plan.lazy ? launch_dyn_lds<attn_fwd_dma_kernel<F.d, F.qt, F.kt, 4, true>>(l.grid, l.block, l.lds, s, p)
+                       : launch_dyn_lds<attn_fwd_dma_kernel<F.d, F.qt, F.kt, 4, false>>(l.grid, l.block, l.lds, s, p);
     }
+    return hipErrorInvalidValue;
   }
-  return p.causal ? run_fwd2<D, QT, KT, DSPLIT, true>(p, s) : run_fwd2<D, QT, KT, DSPLIT, false>(p, s);
+  if constexpr (!F.fp8)
+    return plan.causal ? launch_dyn_lds<attn_fwd_kernel<F.d, F.qt, F.kt, F.dsplit, true>>(l.grid, l.block, l.lds, s, p)
+                       : launch_dyn_lds<attn_fwd_kernel<F.d, F.qt, F.kt, F.dsplit, false>>(l.grid, l.block, l.lds, s, p);
+  return hipErrorInvalidValue;
 }
-template <int D, int QT, int KT, int DSPLIT, bool PS>
-hipError_t run_dq2(const AttnParams& p, hipStream_t s) {
-  constexpr int DPK = (D + 31) / 32 * 32, S = DPK * 2 + 32;
-  constexpr int QB = (DSPLIT == 1 ? 4 : 1) * QT * 16;
-  constexpr size_t lds = 2 * KT * S;
-  static bool attr = false;
-  if (!attr) { hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, QT, KT, DSPLIT, PS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, QT, KT, DSPLIT, PS>), dim3((p.Nq + QB - 1) / QB, p.H, p.B), dim3(256), lds, s, p);
-  return hipGetLastError();
+template <int I>
+hipError_t launch_bwd_form(const AttnParams& p, const AttnPlan& plan, hipStream_t s) {
+  constexpr AttnForm F = ATTN_FORMS[I];
+  if constexpr (F.dq_qt > 0) {
+    const AttnLaunch& q = plan.launch[1];
+    const hipError_t e = plan.prescaled ? launch_dyn_lds<attn_bwd_dq_kernel<F.d, F.dq_qt, F.dq_kt, F.dsplit, true>>(q.grid, q.block, q.lds, s, p)
+                                        : launch_dyn_lds<attn_bwd_dq_kernel<F.d, F.dq_qt, F.dq_kt, F.dsplit, false>>(q.grid, q.block, q.lds, s, p);
+    if (e != hipSuccess || plan.launches < 3) return e;
+    const AttnLaunch& k = plan.launch[2];
+    return plan.prescaled ? launch_dyn_lds<attn_bwd_dkv_kernel<F.d, F.ktw, F.qtl, F.dsplit, true>>(k.grid, k.block, k.lds, s, p)
+                          : launch_dyn_lds<attn_bwd_dkv_kernel<F.d, F.ktw, F.qtl, F.dsplit, false>>(k.grid, k.block, k.lds, s, p);
+  }
+  return hipErrorInvalidValue;
 }
-template <int D, int QT, int KT, int DSPLIT>
-hipError_t run_dq(const AttnParams& p, hipStream_t s) {
-  return p.q_prescaled ? run_dq2<D, QT, KT, DSPLIT, true>(p, s) : run_dq2<D, QT, KT, DSPLIT, false>(p, s);
+
+AttnLaunch delta_launch(const AttnParams& p) {
+  const size_t total = (size_t)p.B * p.H * p.Nq;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  return AttnLaunch{dim3(blocks), 256, 0};
 }
-template <int D, int KTW, int QTL, int DSPLIT, bool PS>
-hipError_t run_dkv2(const AttnParams& p, hipStream_t s) {
-  constexpr int DPK = (D + 31) / 32 * 32, S = DPK * 2 + 32;
-  constexpr int KB = (DSPLIT == 1 ? 4 : 1) * KTW * 16;
-  constexpr size_t lds = 2 * QTL * S + 2 * QTL * sizeof(float);
-  static bool attr = false;
-  if (!attr) { hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<D, KTW, QTL, DSPLIT, PS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, KTW, QTL, DSPLIT, PS>), dim3((p.Nk + KB - 1) / KB, p.H, p.B), dim3(256), lds, s, p);
-  return hipGetLastError();
-}
-template <int D, int KTW, int QTL, int DSPLIT>
-hipError_t run_dkv(const AttnParams& p, hipStream_t s) {
-  return p.q_prescaled ? run_dkv2<D, KTW, QTL, DSPLIT, true>(p, s) : run_dkv2<D, KTW, QTL, DSPLIT, false>(p, s);
+
+hipError_t run_plan(const AttnParams& p, const AttnScratch& scratch, const AttnPlan& plan, bool bwd, hipStream_t s) {
+  switch (plan.route) {
+    case ATTN_GEMM:
+      if (bwd) { const hipError_t e = launch_attention_delta(p, s); if (e != hipSuccess) return e; }
+      return launch_attention_gemm(p, scratch, plan.group, bwd, s);
+    case ATTN_SHORTK: return launch_attention_shortk(p, plan, s);
+    case ATTN_DMA:
+    case ATTN_STREAM: return attn_with_form(plan.form, [&](auto i) { return launch_fwd_form<decltype(i)::value>(p, plan, s); });
+    case ATTN_FLASH_BWD: {
+      const hipError_t e = launch_attention_delta(p, s);
+      if (e != hipSuccess) return e;
+      return attn_with_form(plan.form, [&](auto i) { return launch_bwd_form<decltype(i)::value>(p, plan, s); });
+    }
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace
 
-static bool attn_check(const AttnParams& p) {
-  return !(p.ldq & 7) && !(p.ldk & 7) && !(p.ldv & 7) && !(p.ldo & 3) && p.Nq > 0 && p.Nk > 0;
+// The only place that decides refusal, route and form.  Order: the GEMM route if scratch is offered, the shape is its own and (backward)
+// dk / dv are asked for; then the short-key kernel; fp8 P.V; the LDS-DMA staged kernel on 8 or 4 waves; the register-staged kernel.
+AttnPlan attention_plan(const AttnParams& p, const AttnScratch& sc, bool bwd, int force) {
+  AttnPlan plan;
+  if (p.Nq <= 0 || p.Nk <= 0) return plan;
+  const bool ld8 = !(p.ldq & 7) && !(p.ldk & 7) && !(p.ldv & 7);
+  if (sc.workspace && sc.tap1x1 && attn_gemm_shape(p.Nq, p.Nk, p.D, p.causal) && ld8 && !(p.ldo & 7) && (!bwd || (p.dk && p.dv)) &&
+      sc.workspace_bytes >= attention_gemm_workspace(p.Nq, p.Nk, p.D, bwd)) {
+    if (!p.lse) return plan;
+    if (bwd && (!p.delta || !p.d_o || !p.o || !p.dq || (p.lddo & 7) || (p.lddq & 7) || (p.lddk & 7) || (p.lddv & 7))) return plan;
+    plan.route = ATTN_GEMM;
+    const size_t fit = sc.workspace_bytes / attention_gemm_workspace(p.Nq, p.Nk, p.D, bwd);
+    const int gmax = attn_gemm_group_max(p.B, p.H, p.Nq, p.Nk);
+    plan.group = fit < (size_t)gmax ? (int)fit : gmax;
+    return plan;
+  }
+  if (force == ATTN_GEMM || !ld8 || (p.ldo & 3)) return plan;
+  const int form = attn_form_of(p.D);
+  const auto grid = [&](int rows, int per) { return dim3((rows + per - 1) / per, p.H, p.B); };
+  if (bwd) {
+    if ((p.lddo & 7) || (p.lddq & 3) || !p.delta || !p.lse || !p.d_o || !p.o || form < 0) return plan;
+    if (p.dk && ((p.lddk & 3) || (p.lddv & 3))) return plan;
+    const AttnForm& f = ATTN_FORMS[form];
+    const int span = (f.dsplit == 1 ? 4 : 1) * 16, S = attn_dpk(f.d) * 2 + 32;      // rows of a 16-row tile over the workgroup, LDS row bytes
+    plan.route = ATTN_FLASH_BWD; plan.form = form; plan.waves = 4; plan.prescaled = p.q_prescaled != 0;
+    plan.launch[0] = delta_launch(p);
+    plan.launch[1] = AttnLaunch{grid(p.Nq, span * f.dq_qt), 256, (size_t)2 * f.dq_kt * S};
+    plan.launch[2] = AttnLaunch{grid(p.Nk, span * f.ktw), 256, (size_t)2 * f.qtl * S + 2 * f.qtl * sizeof(float)};
+    plan.launches = p.dk ? 3 : 2;
+    return plan;
+  }
+  const bool kv_fit = offsets_fit_32bit(p.Nk, p.ldk > p.ldv ? p.ldk : p.ldv);
+  // short keys: non-causal, <= 80 keys, whole 32-query tiles, a head dim with a short-key kernel, rows within the 32-bit byte offsets of one image
+  if (form >= 0 && ATTN_FORMS[form].sk_nw && attn_env().shortk && !p.no_shortk && !p.causal && !p.pv_fp8 && p.Nk <= 80 && !(p.Nq & 31) &&
+      offsets_fit_32bit(p.Nq, p.ldq) && kv_fit) {
+    const int nw = ATTN_FORMS[form].sk_nw, rb = attn_dma_row_bytes(p.D);
+    const int qslot = (32 * rb + 1023) / 1024 * 1024, npk = (96 * rb + 1023) / 1024;   // bytes of a wave's Q slot, 1 KB pieces of the K (or V) block
+    plan.route = ATTN_SHORTK; plan.form = form; plan.waves = nw;
+    plan.sk_tiles = p.Nq / 32;
+    // tiles per wave: enough workgroups to fill the chip twice over, at most 8 tiles per wave (the K / V staging is amortised over them)
+    int wgs = (plan.sk_tiles + nw - 1) / nw;                   // one tile per wave
+    int per = 8;
+    while (per > 1 && (long long)((wgs + per - 1) / per) * p.H * p.B < 1024) per >>= 1;
+    plan.sk_wgs = (wgs + per - 1) / per;
+    plan.launch[0] = AttnLaunch{dim3(((p.B * plan.sk_wgs + 7) & ~7) * p.H), (unsigned)nw * 64, (size_t)2 * npk * 1024 + (size_t)nw * 2 * qslot};
+    plan.launches = 1;
+    return plan;
+  }
+  if (form < 0) return plan;
+  // fp8 P.V (BASELINE.json configs[4]): opt-in per launch, d = 64, non-causal, key / value rows within the LDS-DMA offset range
+  const bool fp8 = p.pv_fp8 && p.D == ATTN_FORMS[ATTN_FORM_FP8].d && !p.causal && kv_fit;
+  const AttnForm& f = ATTN_FORMS[fp8 ? ATTN_FORM_FP8 : form];
+  plan.form = fp8 ? ATTN_FORM_FP8 : form;
+  plan.launches = 1;
+  if (fp8 || (f.dma() && !p.causal && kv_fit)) {
+    plan.route = ATTN_DMA; plan.fp8 = fp8; plan.lazy = fp8 || p.q_prescaled;
+    plan.waves = fp8 || (f.dma8() && p.Nq % (8 * f.qt * 16) == 0) ? 8 : 4;
+    plan.launch[0] = AttnLaunch{grid(p.Nq, plan.waves * f.qt * 16), (unsigned)plan.waves * 64, (size_t)4 * f.kt * attn_dma_row_bytes(f.d) + 128 + (fp8 ? 8192 : 0)};
+    return plan;
+  }
+  plan.route = ATTN_STREAM; plan.waves = 4; plan.causal = p.causal != 0;
+  plan.launch[0] = AttnLaunch{grid(p.Nq, (f.dsplit == 1 ? 4 : 1) * f.qt * 16), 256, (size_t)2 * f.kt * (attn_dpk(f.d) * 2 + 32)};
+  return plan;
 }
 
-hipError_t launch_attention_fwd(const AttnParams& p, hipStream_t s) {
-  if (!attn_check(p)) return hipErrorInvalidValue;
-  if (attention_shortk_supported(p)) return launch_attention_fwd_shortk(p, s);     // <= 80 keys: K / V resident, per-wave query tiles
-  switch (p.D) {
-    case 32: return run_fwd<32, 2, 64, 1>(p, s);
-    case 40: return run_fwd<40, 2, 64, 1>(p, s);
-    case 64:
-      // fp8 P.V (configs[4]): opt-in per launch, non-causal, key / value rows within the LDS-DMA offset range
-      if (p.pv_fp8 && !p.causal && (size_t)p.Nk * (size_t)(p.ldk > p.ldv ? p.ldk : p.ldv) * 2 < 0xF0000000ull)
-        return run_fwd_dma2<64, 2, 128, 8, true, true>(p, s);
-      return run_fwd<64, 2, 64, 1>(p, s);
-    case 80: return run_fwd<80, 2, 64, 1>(p, s);
-    case 160: return run_fwd<160, 2, 64, 1>(p, s);
-    case 512: return run_fwd<512, 4, 32, 4>(p, s);   // 64 queries per workgroup: K/V stream traffic per query / 4 (+50 %)
-    default: return hipErrorInvalidValue;
+int attention_plan_query(const AttnParams& p, size_t workspace_bytes, bool bwd, int* out) {
+  static int some_scratch;                                     // the planner tests the scratch pointers for null and never follows them
+  const AttnScratch sc = workspace_bytes ? AttnScratch{&some_scratch, workspace_bytes, &some_scratch, nullptr, 0} : AttnScratch{};
+  const AttnPlan plan = attention_plan(p, sc, bwd);
+  for (int i = 0; i < 26; ++i) out[i] = 0;
+  out[0] = plan.route;
+  if (plan.route < 0) return plan.route;
+  if (plan.route == ATTN_GEMM) { out[9] = plan.group; return plan.route; }
+  const AttnForm& f = ATTN_FORMS[plan.form];
+  out[1] = f.d; out[4] = plan.route == ATTN_SHORTK ? 0 : f.dsplit;
+  if (bwd) { out[2] = f.dq_qt; out[3] = f.dq_kt; if (plan.launches == 3) { out[5] = f.ktw; out[6] = f.qtl; } }
+  else if (plan.route != ATTN_SHORTK) { out[2] = f.qt; out[3] = f.kt; }
+  out[7] = plan.waves;
+  out[8] = (plan.lazy ? 1 : 0) | (plan.prescaled ? 2 : 0) | (plan.causal ? 4 : 0) | (plan.fp8 ? 8 : 0);
+  out[10] = plan.launches;
+  for (int i = 0; i < plan.launches; ++i) {
+    const AttnLaunch& l = plan.launch[i];
+    out[11 + 5 * i] = (int)l.grid.x; out[12 + 5 * i] = (int)l.grid.y; out[13 + 5 * i] = (int)l.grid.z; out[14 + 5 * i] = (int)l.block; out[15 + 5 * i] = (int)l.lds;
   }
+  return plan.route;
+}
+
+size_t attention_scratch_bytes(int B, int heads, int Nq, int Nk, int D, bool causal, bool cross, bool want_grad) {
+  if (cross || !attn_gemm_shape(Nq, Nk, D, causal)) return 0;
+  return attention_gemm_workspace(Nq, Nk, D, want_grad ? 1 : 0) * (size_t)attn_gemm_group_max(B, heads, Nq, Nk);
+}
+
+hipError_t launch_attention(const AttnParams& p, const AttnScratch& scratch, bool bwd, hipStream_t s) {
+  return run_plan(p, scratch, attention_plan(p, scratch, bwd), bwd, s);
+}
+hipError_t launch_attention_fwd(const AttnParams& p, hipStream_t s) { return launch_attention(p, AttnScratch{}, false, s); }
+hipError_t launch_attention_bwd(const AttnParams& p, hipStream_t s) { return launch_attention(p, AttnScratch{}, true, s); }
+hipError_t launch_attention_gemm_fwd(const AttnParams& p, void* workspace, size_t workspace_bytes, const int* tap1x1, float* partial, size_t partial_cap, hipStream_t s) {
+  const AttnScratch sc{workspace, workspace_bytes, tap1x1, partial, partial_cap};
+  return run_plan(p, sc, attention_plan(p, sc, false, ATTN_GEMM), false, s);
+}
+hipError_t launch_attention_gemm_bwd(const AttnParams& p, void* workspace, size_t workspace_bytes, const int* tap1x1, float* partial, size_t partial_cap, hipStream_t s) {
+  const AttnScratch sc{workspace, workspace_bytes, tap1x1, partial, partial_cap};
+  return run_plan(p, sc, attention_plan(p, sc, true, ATTN_GEMM), true, s);
 }
 
 hipError_t launch_attention_delta(const AttnParams& p, hipStream_t s) {
   if (!p.delta || !p.d_o || !p.o) return hipErrorInvalidValue;
-  const size_t total = (size_t)p.B * p.H * p.Nq;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3(blocks), dim3(256), 0, s, p);
+  const AttnLaunch l = delta_launch(p);
+  hipLaunchKernelGGL(attn_delta_kernel, l.grid, dim3(l.block), 0, s, p);
   return hipGetLastError();
-}
-
-hipError_t launch_attention_bwd(const AttnParams& p, hipStream_t s) {
-  if (!attn_check(p) || (p.lddo & 7) || (p.lddq & 3) || !p.delta || !p.lse) return hipErrorInvalidValue;
-  {
-    const size_t total = (size_t)p.B * p.H * p.Nq;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3(blocks), dim3(256), 0, s, p);
-  }
-  hipError_t e;
-  switch (p.D) {
-    case 32: e = run_dq<32, 2, 64, 1>(p, s); break;
-    case 40: e = run_dq<40, 2, 64, 1>(p, s); break;
-    case 64: e = run_dq<64, 2, 64, 1>(p, s); break;
-    case 80: e = run_dq<80, 1, 64, 1>(p, s); break;
-    case 160: e = run_dq<160, 1, 64, 1>(p, s); break;
-    case 512: e = run_dq<512, 1, 32, 4>(p, s); break;
-    default: return hipErrorInvalidValue;
-  }
-  if (e != hipSuccess || !p.dk) return e;
-  if ((p.lddk & 3) || (p.lddv & 3)) return hipErrorInvalidValue;
-  switch (p.D) {
-    case 32: return run_dkv<32, 2, 64, 1>(p, s);
-    case 40: return run_dkv<40, 2, 64, 1>(p, s);
-    case 64: return run_dkv<64, 2, 64, 1>(p, s);
-    case 80: return run_dkv<80, 1, 64, 1>(p, s);
-    case 160: return run_dkv<160, 1, 64, 1>(p, s);
-    case 512: return run_dkv<512, 1, 32, 4>(p, s);
-    default: return hipErrorInvalidValue;
-  }
 }

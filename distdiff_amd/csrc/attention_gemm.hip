@@ -16,6 +16,7 @@
 #include <cstring>
 #include "common.h"
 #include "kernels.h"
+#include "attention_dispatch.h"
 
 namespace {
 
@@ -172,10 +173,6 @@ struct Ws {   // carve-out of the caller's scratch (256-byte aligned pieces)
 
 #define AG_CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
-bool attention_gemm_supported(const AttnParams& p) {
-  return p.D >= 256 && (p.D % 64) == 0 && (p.Nq % 64) == 0 && (p.Nk % 64) == 0 && !p.causal && !(p.ldq & 7) && !(p.ldk & 7) && !(p.ldv & 7) && !(p.ldo & 7);
-}
-
 // scratch of ONE image; the launchers take `workspace_bytes` and process as many images per launch as fit (at most 8)
 size_t attention_gemm_workspace(int Nq, int Nk, int D, int bwd) {
   const size_t nn = (size_t)Nq * Nk;
@@ -183,22 +180,10 @@ size_t attention_gemm_workspace(int Nq, int Nk, int D, int bwd) {
   if (bwd) b = 2 * nn * 4 + 4 * nn * 2 + 3 * (size_t)Nk * D * 2 + 2 * (size_t)Nq * D * 2 + 8192;   // S, dP | P, dS, P^T, dS^T | Kc, Vc, K^T | Q^T, dO^T
   return b;
 }
-// images per launch: single-head layers only (with H > 1 the heads of one image interleave along the columns of the same rows, so the
-// images of a group do not stack along M), whole 256-row tiles per image, as many as the scratch holds
-static int group_size(const AttnParams& p, size_t workspace_bytes, int bwd) {
-  constexpr int gmax = 8;
-  if (p.H != 1 || (p.Nq & 255) || (p.Nk & 255)) return 1;
-  const size_t per = attention_gemm_workspace(p.Nq, p.Nk, p.D, bwd);
-  size_t g = workspace_bytes / per;
-  if (g > (size_t)gmax) g = gmax;
-  if (g > (size_t)p.B) g = p.B;
-  return g < 1 ? 1 : (int)g;
-}
 
-hipError_t launch_attention_gemm_fwd(const AttnParams& p, void* workspace, size_t workspace_bytes, const int* tap1x1, float* partial, size_t partial_cap, hipStream_t s) {
-  if (!attention_gemm_supported(p) || !p.lse || workspace_bytes < attention_gemm_workspace(p.Nq, p.Nk, p.D, 0)) return hipErrorInvalidValue;
+// The two launch sequences, G images per launch.  The planner (attention.hip) has checked shape, pointers, alignment and scratch size.
+static hipError_t gemm_fwd(const AttnParams& p, void* workspace, int G, const int* tap1x1, float* partial, size_t partial_cap, hipStream_t s) {
   const int Nq = p.Nq, Nk = p.Nk, D = p.D;
-  const int G = group_size(p, workspace_bytes, 0);
   Ws ws{(char*)workspace};
   float* S = ws.take<float>((size_t)G * Nq * Nk);
   bf16_t* P = ws.take<bf16_t>((size_t)G * Nq * Nk);
@@ -221,13 +206,9 @@ hipError_t launch_attention_gemm_fwd(const AttnParams& p, void* workspace, size_
   return hipSuccess;
 }
 
-hipError_t launch_attention_gemm_bwd(const AttnParams& p, void* workspace, size_t workspace_bytes, const int* tap1x1, float* partial, size_t partial_cap, hipStream_t s) {
-  if (!attention_gemm_supported(p) || !p.lse || !p.delta || !p.dq || !p.dk || !p.dv || (p.lddo & 7) || (p.lddq & 7) || (p.lddk & 7) || (p.lddv & 7) ||
-      workspace_bytes < attention_gemm_workspace(p.Nq, p.Nk, p.D, 1))
-    return hipErrorInvalidValue;
+// (delta = rowsum(dO * O) is already there: launch_attention_delta)
+static hipError_t gemm_bwd(const AttnParams& p, void* workspace, int G, const int* tap1x1, float* partial, size_t partial_cap, hipStream_t s) {
   const int Nq = p.Nq, Nk = p.Nk, D = p.D;
-  AG_CHK(launch_attention_delta(p, s));
-  const int G = group_size(p, workspace_bytes, 1);
   Ws ws{(char*)workspace};
   float* S = ws.take<float>((size_t)G * Nq * Nk);
   float* dP = ws.take<float>((size_t)G * Nq * Nk);
@@ -265,4 +246,8 @@ hipError_t launch_attention_gemm_bwd(const AttnParams& p, void* workspace, size_
     AG_CHK(gemm(dS, Nk, KT, p.dq + (size_t)b * Nq * p.lddq + h * D, p.lddq, Nq, D, Nk, false, 1.f, tap1x1, partial, partial_cap, s, g));
   }
   return hipSuccess;
+}
+
+hipError_t launch_attention_gemm(const AttnParams& p, const AttnScratch& sc, int group, bool bwd, hipStream_t s) {
+  return bwd ? gemm_bwd(p, sc.workspace, group, sc.tap1x1, sc.partial, sc.partial_cap, s) : gemm_fwd(p, sc.workspace, group, sc.tap1x1, sc.partial, sc.partial_cap, s);
 }

@@ -16,31 +16,13 @@
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
+#include "attention_dispatch.h"
+#include "attention_frag.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ bf16x8 sk_row_frag(const unsigned char* base, int row, int S, int slot) {
-  return *(const bf16x8*)(base + row * S + slot * 16);
-}
-// 8 k-values (the permuted order of attention.hip's header) of column col16 * 16 + (lane & 15): rows r0 + 4 * (lane >> 4) + {0 .. 3} and + 16
-__device__ __forceinline__ bf16x8 sk_col_frag(const unsigned char* base, int r0, int S, int col16, int lane) {
-  const int i = lane & 15, g = lane >> 4;
-  const unsigned char* a = base + (r0 + 4 * g + (i >> 2)) * S + (col16 * 16 + 4 * (i & 3)) * 2;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * S));
-  s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-__device__ __forceinline__ float sk_max2(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, __builtin_inff()); }
-__device__ __forceinline__ bf16x8 sk_pack(const f32x4& a, const f32x4& b) {
-  uint4 u;
-  u.x = pack2bf(a[0], a[1]); u.y = pack2bf(a[2], a[3]); u.z = pack2bf(b[0], b[1]); u.w = pack2bf(b[2], b[3]);
-  return __builtin_bit_cast(bf16x8, u);
-}
 __device__ __forceinline__ i32x4 sk_rsrc(const void* base) {
   const unsigned long long a = (unsigned long long)base;
   return i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu)), (int)0xffffff00u, 0x00020000};
@@ -54,14 +36,6 @@ __device__ __forceinline__ unsigned sk_lds_off(const void* p) {
 template <int N>
 __device__ __forceinline__ void sk_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-template <int D>
-struct SkGeo {
-  static constexpr int DPK = (D + 31) / 32 * 32;
-  static constexpr int RB = D <= 40 ? 96 : D <= 80 ? 160 : DPK * 2 + 32;   // LDS row bytes: conflict-free for row and column fragments (attention.hip)
-  static constexpr int RG = RB / 16, DG = D / 8;
-  static constexpr int KS = DPK / 32, DVT = (D + 15) / 16;
-};
-constexpr float SK_LOG2E = 1.4426950408889634f;
 constexpr int SK_NKT = 5;                   // 16-key score tiles: Nk <= 80
 constexpr int SK_KROWS = 96;                // staged key rows (three 32-key chunks of P.V; rows behind the last key are zeros)
 constexpr unsigned SK_OOR = 0xffffff00u;
@@ -69,9 +43,9 @@ constexpr unsigned SK_OOR = 0xffffff00u;
 // One 32-query tile of one head: Q fragments from the wave's LDS slot Qt, scores against the resident K block, exact softmax, P.V against
 // the resident V block, O and LSE stores (2 DVT (+ 2) store instructions, always issued: the callers' counted waits rely on that).
 template <int D>
-__device__ __forceinline__ void sk_tile_frags(const AttnParams& p, const unsigned char* Ks, const unsigned char* Vs, bf16x8 (&qf)[2][SkGeo<D>::KS], float c,
+__device__ __forceinline__ void sk_tile_frags(const AttnParams& p, const unsigned char* Ks, const unsigned char* Vs, bf16x8 (&qf)[2][AttnLdsGeo<D>::KS], float c,
                                               int kfull, int b, int h, int t, int lane) {
-  using G = SkGeo<D>;
+  using G = AttnLdsGeo<D>;
   constexpr int S = G::RB, KS = G::KS, DVT = G::DVT, QROWS = 32;
   constexpr bool ONES = (D % 16) == 8;
   const int i16 = lane & 15, g = lane >> 4;
@@ -90,7 +64,7 @@ __device__ __forceinline__ void sk_tile_frags(const AttnParams& p, const unsigne
     for (int qt = 0; qt < 2; ++qt) st[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      const bf16x8 kf = sk_row_frag(Ks, kt * 16 + i16, S, g + 4 * ks);
+      const bf16x8 kf = lds_row_frag(Ks, kt * 16 + i16, S, g + 4 * ks);
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) st[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][ks], st[qt][kt], 0, 0, 0);
     }
@@ -111,9 +85,9 @@ __device__ __forceinline__ void sk_tile_frags(const AttnParams& p, const unsigne
 #pragma unroll
     for (int kt = 0; kt < SK_NKT; ++kt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) mx = sk_max2(mx, st[qt][kt][r]);
-    mx = sk_max2(mx, __shfl_xor(mx, 16, 64));
-    mx = sk_max2(mx, __shfl_xor(mx, 32, 64));
+      for (int r = 0; r < 4; ++r) mx = vmax2(mx, st[qt][kt][r]);
+    mx = vmax2(mx, __shfl_xor(mx, 16, 64));
+    mx = vmax2(mx, __shfl_xor(mx, 32, 64));
     const float mc = mx * c;
     float ps = 0.f;
 #pragma unroll
@@ -126,13 +100,13 @@ __device__ __forceinline__ void sk_tile_frags(const AttnParams& p, const unsigne
       }
     // ---- O^T = V^T P^T over three 32-key chunks (the sixth score tile is all padding: zeros)
     const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bf16x8 pf[3] = {sk_pack(st[qt][0], st[qt][1]), sk_pack(st[qt][2], st[qt][3]), sk_pack(st[qt][4], zero)};
+    const bf16x8 pf[3] = {pack_frag(st[qt][0], st[qt][1]), pack_frag(st[qt][2], st[qt][3]), pack_frag(st[qt][4], zero)};
 #pragma unroll
     for (int dt = 0; dt < DVT; ++dt) {
       o[qt][dt] = zero;
 #pragma unroll
       for (int cc = 0; cc < 3; ++cc)
-        o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sk_col_frag(Vs, 32 * cc, S, dt, lane), pf[cc], o[qt][dt], 0, 0, 0);
+        o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_col_frag(Vs, 32 * cc, S, dt, lane), pf[cc], o[qt][dt], 0, 0, 0);
     }
     // row sum: d % 16 == 8 (d = 40) -- column D of the staged V block is 1.0, so P.V delivered the sum of the bf16-ROUNDED probabilities in
     // O column D (lane group (D % 16) / 4, register 0): O is then an exact convex combination of the value rows, as in the streaming
@@ -165,12 +139,12 @@ __device__ __forceinline__ void sk_tile_frags(const AttnParams& p, const unsigne
 template <int D>
 __device__ __forceinline__ void sk_tile(const AttnParams& p, const unsigned char* Ks, const unsigned char* Vs, const unsigned char* Qt, float c,
                                         int kfull, int b, int h, int t, int lane) {
-  using G = SkGeo<D>;
+  using G = AttnLdsGeo<D>;
   bf16x8 qf[2][G::KS];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) qf[qt][ks] = sk_row_frag(Qt, qt * 16 + (lane & 15), G::RB, (lane >> 4) + 4 * ks);
+    for (int ks = 0; ks < G::KS; ++ks) qf[qt][ks] = lds_row_frag(Qt, qt * 16 + (lane & 15), G::RB, (lane >> 4) + 4 * ks);
   sk_tile_frags<D>(p, Ks, Vs, qf, c, kfull, b, h, t, lane);
 }
 
@@ -181,7 +155,7 @@ __device__ __forceinline__ void sk_tile(const AttnParams& p, const unsigned char
 // NW waves; wave w of range x (of `wgs` per image and head) walks the 32-query tiles (x + j wgs) * NW + w.
 template <int D, int NW>
 __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_shortk_kernel(AttnParams p, int ntiles, int wgs) {
-  using G = SkGeo<D>;
+  using G = AttnLdsGeo<D>;
   constexpr int S = G::RB, RG = G::RG, DG = G::DG, KS = G::KS, DVT = G::DVT;
   constexpr int QROWS = 32;                                   // queries per wave and tile (two 16-query MFMA tiles)
   constexpr int QSLOT = ((QROWS * S + 1023) / 1024) * 1024;   // bytes of one Q slot (whole 1 KB DMA pieces)
@@ -246,7 +220,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_shortk_kernel(AttnParams 
   sk_wait_vm<0>();
   __syncthreads();                                             // K / V complete for everybody (and this wave's first Q tile)
 
-  const float c = p.q_prescaled ? 1.f : p.scale * SK_LOG2E;    // scores -> log2 domain
+  const float c = p.q_prescaled ? 1.f : p.scale * LOG2E;    // scores -> log2 domain
   const int kfull = p.Nk >> 4;                                 // score tiles that are whole
   for (int it = 0; t < ntiles; ++it, t += wstep) {
     const int slot = it & 1;
@@ -260,44 +234,13 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_shortk_kernel(AttnParams 
   }
 }
 
-template <int D, int NW>
-hipError_t run_shortk(const AttnParams& p, hipStream_t s) {
-  using G = SkGeo<D>;
-  constexpr int QSLOT = ((32 * G::RB + 1023) / 1024) * 1024;
-  constexpr int NPK = (SK_KROWS * G::RB + 1023) / 1024;
-  const size_t lds = 2 * NPK * 1024 + (size_t)NW * 2 * QSLOT;
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)attn_fwd_shortk_kernel<D, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  const int ntiles = p.Nq / 32;
-  // tiles per wave: enough workgroups to fill the chip twice over, at most 8 tiles per wave (the K / V staging is amortised over them)
-  int wgs = (ntiles + NW - 1) / NW;                            // one tile per wave
-  const int heads = p.H * p.B;
-  int per = 8;
-  while (per > 1 && (long long)((wgs + per - 1) / per) * heads < 1024) per >>= 1;
-  wgs = (wgs + per - 1) / per;
-  const int groups = (p.B * wgs + 7) & ~7;
-  hipLaunchKernelGGL((attn_fwd_shortk_kernel<D, NW>), dim3(groups * p.H), dim3(NW * 64), lds, s, p, ntiles, wgs);
-  return hipGetLastError();
-}
-
 }  // namespace
 
-// Eligible: non-causal, <= 80 keys, whole 32-query tiles, d in {40, 64, 80}, rows within the 32-bit byte offsets of one image
-bool attention_shortk_supported(const AttnParams& p) {
-  static const int on = getenv("DD_ATTN_SHORTK") ? atoi(getenv("DD_ATTN_SHORTK")) : 1;
-  if (!on || p.no_shortk || p.causal || p.pv_fp8 || p.Nk < 1 || p.Nk > 80 || (p.Nq & 31) || p.Nq < 32) return false;
-  if (p.D != 40 && p.D != 64 && p.D != 80) return false;
-  if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.ldo & 3)) return false;
-  if ((size_t)p.Nq * (size_t)p.ldq * 2 >= 0xF0000000ull || (size_t)p.Nk * (size_t)(p.ldk > p.ldv ? p.ldk : p.ldv) * 2 >= 0xF0000000ull) return false;
-  return true;
-}
-
-hipError_t launch_attention_fwd_shortk(const AttnParams& p, hipStream_t s) {
-  if (!attention_shortk_supported(p)) return hipErrorInvalidValue;
-  switch (p.D) {
-    case 40: return run_shortk<40, 8>(p, s);
-    case 64: return run_shortk<64, 4>(p, s);
-    case 80: return run_shortk<80, 4>(p, s);
-    default: return hipErrorInvalidValue;
-  }
+hipError_t launch_attention_shortk(const AttnParams& p, const AttnPlan& plan, hipStream_t s) {
+  const AttnLaunch& l = plan.launch[0];
+  return attn_with_form(plan.form, [&](auto i) {
+    constexpr AttnForm F = ATTN_FORMS[decltype(i)::value];
+    if constexpr (F.sk_nw > 0) return launch_dyn_lds<attn_fwd_shortk_kernel<F.d, F.sk_nw>>(l.grid, l.block, l.lds, s, p, plan.sk_tiles, plan.sk_wgs);
+    else return hipErrorInvalidValue;
+  });
 }

@@ -84,6 +84,35 @@ static void fwd_conv_params(const Program& P, const Op& op, const Ctx& c, ConvGe
   p.flags = flags;
 }
 
+// launch parameters of an attention op, forward or backward (cross attention: K, V are the prompt's constants, no dk / dv)
+static AttnParams attn_params(const Program& P, const Op& op, const Ctx& c, bool bwd) {
+  const Tn& q = P.t[op.q]; const Tn& y = P.t[op.y];
+  AttnParams p; memset(&p, 0, sizeof p);
+  p.q = act_ptr(c, q); p.ldq = q.ld;
+  if (op.cross_slot >= 0) {
+    p.k = (*c.cross_kv)[op.cross_slot].first; p.v = (*c.cross_kv)[op.cross_slot].second; p.ldk = p.ldv = q.C;
+  } else {
+    const Tn& k = P.t[op.k]; const Tn& v = P.t[op.v];
+    p.k = act_ptr(c, k); p.v = act_ptr(c, v); p.ldk = k.ld; p.ldv = v.ld;
+    if (bwd) { p.dk = grad_ptr(c, k); p.dv = grad_ptr(c, v); p.lddk = k.ld; p.lddv = v.ld; }
+  }
+  p.o = act_ptr(c, y); p.ldo = y.ld; p.lse = (float*)(c.act + op.stats_off);
+  p.B = q.B; p.H = op.heads; p.Nq = op.Nq; p.Nk = op.Nk; p.D = op.D; p.scale = op.q_prescaled ? 0.6931471805599453f : 1.f / sqrtf((float)op.D); p.q_prescaled = op.q_prescaled;
+  if (bwd) {
+    p.delta = p.lse + (size_t)q.B * op.heads * op.Nq;
+    p.d_o = grad_ptr(c, y); p.lddo = y.ld; p.dq = grad_ptr(c, q); p.lddq = q.ld;
+  } else {
+    p.causal = op.causal;
+    p.pv_fp8 = op.pv_fp8;      // BASELINE configs[4]: fp8 P.V for d = 64 heads (SDXL), opt-in per engine (dd_config.unet_attn_fp8)
+  }
+  return p;
+}
+// the wide-head GEMM route may use the engine's scratch for self attention only
+static AttnScratch attn_scratch(const Op& op, const Ctx& c) {
+  if (op.cross_slot >= 0) return AttnScratch{};
+  return AttnScratch{c.scratch_tmp, c.tmp_cap, c.tap1x1, (float*)c.scratch_partial, c.partial_cap};
+}
+
 void run_fwd(const Program& P, const Ctx& c, int op_begin, int op_end) {
   if (op_end < 0) op_end = (int)P.ops.size();
   if (c.prof) c.prof->new_run();
@@ -180,22 +209,7 @@ void run_fwd(const Program& P, const Ctx& c, int op_begin, int op_end) {
         HIPCHK(launch_layernorm_fwd(p, c.s));
       } break;
       case OP_ATTN: {
-        const Tn& q = P.t[op.q]; const Tn& y = P.t[op.y];
-        AttnParams p; memset(&p, 0, sizeof p);
-        p.q = act_ptr(c, q); p.ldq = q.ld;
-        if (op.cross_slot >= 0) {
-          p.k = (*c.cross_kv)[op.cross_slot].first; p.v = (*c.cross_kv)[op.cross_slot].second; p.ldk = p.ldv = q.C;
-        } else {
-          p.k = act_ptr(c, P.t[op.k]); p.v = act_ptr(c, P.t[op.v]); p.ldk = P.t[op.k].ld; p.ldv = P.t[op.v].ld;
-        }
-        p.o = act_ptr(c, y); p.ldo = y.ld; p.lse = (float*)(c.act + op.stats_off);
-        p.B = q.B; p.H = op.heads; p.Nq = op.Nq; p.Nk = op.Nk; p.D = op.D; p.scale = op.q_prescaled ? 0.6931471805599453f : 1.f / sqrtf((float)op.D); p.q_prescaled = op.q_prescaled;
-        p.causal = op.causal;
-        p.pv_fp8 = op.pv_fp8;      // BASELINE configs[4]: fp8 P.V for d = 64 heads (SDXL), opt-in per engine (dd_config.unet_attn_fp8)
-        if (op.cross_slot < 0 && attention_gemm_supported(p) && c.tap1x1 && attention_gemm_workspace(p.Nq, p.Nk, p.D, 0) <= c.tmp_cap)
-          HIPCHK(launch_attention_gemm_fwd(p, c.scratch_tmp, c.tmp_cap, c.tap1x1, (float*)c.scratch_partial, c.partial_cap, c.s));
-        else
-          HIPCHK(launch_attention_fwd(p, c.s));
+        HIPCHK(launch_attention(attn_params(P, op, c, false), attn_scratch(op, c), false, c.s));
         if (c.flops) *c.flops += op.flops;
       } break;
       case OP_CONCAT: {
@@ -323,25 +337,8 @@ void run_bwd(const Program& P, const Ctx& c) {
         HIPCHK(launch_layernorm_bwd(p, c.s));
       } break;
       case OP_ATTN: {
-        const Tn& q = P.t[op.q]; const Tn& y = P.t[op.y];
-        if (!q.grad) break;
-        AttnParams p; memset(&p, 0, sizeof p);
-        p.q = act_ptr(c, q); p.ldq = q.ld;
-        if (op.cross_slot >= 0) {
-          p.k = (*c.cross_kv)[op.cross_slot].first; p.v = (*c.cross_kv)[op.cross_slot].second; p.ldk = p.ldv = q.C;
-        } else {
-          const Tn& k = P.t[op.k]; const Tn& v = P.t[op.v];
-          p.k = act_ptr(c, k); p.v = act_ptr(c, v); p.ldk = k.ld; p.ldv = v.ld;
-          p.dk = grad_ptr(c, k); p.dv = grad_ptr(c, v); p.lddk = k.ld; p.lddv = v.ld;
-        }
-        p.o = act_ptr(c, y); p.ldo = y.ld; p.lse = (float*)(c.act + op.stats_off);
-        p.delta = p.lse + (size_t)q.B * op.heads * op.Nq;
-        p.B = q.B; p.H = op.heads; p.Nq = op.Nq; p.Nk = op.Nk; p.D = op.D; p.scale = op.q_prescaled ? 0.6931471805599453f : 1.f / sqrtf((float)op.D); p.q_prescaled = op.q_prescaled;
-        p.d_o = grad_ptr(c, y); p.lddo = y.ld; p.dq = grad_ptr(c, q); p.lddq = q.ld;
-        if (op.cross_slot < 0 && attention_gemm_supported(p) && c.tap1x1 && attention_gemm_workspace(p.Nq, p.Nk, p.D, 1) <= c.tmp_cap)
-          HIPCHK(launch_attention_gemm_bwd(p, c.scratch_tmp, c.tmp_cap, c.tap1x1, (float*)c.scratch_partial, c.partial_cap, c.s));
-        else
-          HIPCHK(launch_attention_bwd(p, c.s));
+        if (!P.t[op.q].grad) break;
+        HIPCHK(launch_attention(attn_params(P, op, c, true), attn_scratch(op, c), true, c.s));
         if (c.flops) *c.flops += op.flops * (op.cross_slot >= 0 ? 1.5 : 2.5);
       } break;
       case OP_CONCAT: {

@@ -88,9 +88,8 @@ struct Builder {
     Op op; op.kind = OP_ATTN; op.q = q; op.k = k; op.v = v; op.y = y; op.heads = heads; op.D = tq.C / heads; op.Nq = Nq; op.Nk = Nk;
     op.cross_slot = cross_slot; op.causal = causal; op.q_prescaled = q_prescaled;
     // wide heads (AutoencoderKL mid block) run through GEMMs on a materialised score matrix: scratch for up to 8 images per launch
-    // (single-head layers: grouped GEMMs over the images, attention_gemm.hip), one image otherwise
-    if (op.D >= 256 && cross_slot < 0 && !causal)
-      P.scratch_tmp = std::max(P.scratch_tmp, attention_gemm_workspace(Nq, Nk, op.D, P.want_grad ? 1 : 0) * (size_t)(heads == 1 ? std::min(tq.B, 8) : 1));
+    // (single-head layers: grouped GEMMs over the images, attention_gemm.hip), one image otherwise -- sized by the launch's own planner
+    P.scratch_tmp = std::max(P.scratch_tmp, attention_scratch_bytes(tq.B, heads, Nq, Nk, op.D, causal != 0, cross_slot >= 0, P.want_grad));
     op.stats_off = P.fp32_block((size_t)tq.B * heads * Nq * 2);  // lse + delta
     op.flops = 4.0 * tq.B * heads * (double)Nq * Nk * op.D;
     P.ops.push_back(op);

@@ -145,17 +145,30 @@ struct AttnParams {
   int pv_fp8;                               // forward only, D = 64: P.V on the block-scaled fp8 MFMA (e4m3 probabilities and values)
   int no_shortk;                            // diagnostics: keep <= 80-key launches on the streaming forward (accuracy A/B inside one process)
 };
+// Scratch a launch may use for the GEMM route (wide heads, d >= 256: the AutoencoderKL mid-block attention, attention_gemm.hip, with a
+// materialised N x N score matrix per image).  workspace: attention_gemm_workspace() bytes per image; with more, single-head layers run
+// up to 8 images per launch (grouped GEMMs); tap1x1: device int holding the 1x1 tap ((32 << 6) | 32); partial: split-K scratch of
+// launch_conv_gemm.  Empty (all zero): the flash kernels only -- what the engine passes for cross-attention.
+struct AttnScratch {
+  void* workspace; size_t workspace_bytes;
+  const int* tap1x1;
+  float* partial; size_t partial_cap;
+};
+// The one entry: plans (attention.hip: attention_plan -- GEMM route when the scratch allows it, else short keys, fp8, LDS-DMA staged,
+// register-staged) and launches.  hipErrorInvalidValue and nothing launched for a problem the planner refuses.
+hipError_t launch_attention(const AttnParams& p, const AttnScratch& scratch, bool bwd, hipStream_t stream);
+// The same decision without a launch (no device access; the pointers are only tested for null): returns the route (ATTN_* of
+// attention_dispatch.h, -1 refused) and fills out[26] = {route, head dim of the form, QT, KT, DSPLIT (backward: of the dQ kernel), KTW, QTL
+// (dK/dV kernel, 0 when it does not run), waves, bits (1 lazy reference, 2 prescaled backward, 4 causal, 8 fp8), images per GEMM group,
+// launches, then (grid x, y, z, block, dynamic LDS bytes) of each}.  The GEMM route reports route and group only.
+int attention_plan_query(const AttnParams& p, size_t workspace_bytes, bool bwd, int* out);
+// scratch_tmp bytes the engine has to offer an attention op so that the launch takes the route it can (0: none needed)
+size_t attention_scratch_bytes(int B, int heads, int Nq, int Nk, int D, bool causal, bool cross, bool want_grad);
+// the flash kernels only (empty scratch) ...
 hipError_t launch_attention_fwd(const AttnParams& p, hipStream_t stream);
 hipError_t launch_attention_bwd(const AttnParams& p, hipStream_t stream);
-// short key sequences (<= 80 keys: the 77-token cross-attention), attention_shortk.hip; launch_attention_fwd takes it when it applies
-bool attention_shortk_supported(const AttnParams& p);
-hipError_t launch_attention_fwd_shortk(const AttnParams& p, hipStream_t stream);
 hipError_t launch_attention_delta(const AttnParams& p, hipStream_t stream);   // delta[b,h,q] = sum_d dO*O (first stage of the backward)
-// Wide heads (d >= 256: the AutoencoderKL mid-block attention) through the GEMM kernel with a materialised N x N score matrix per image
-// (attention_gemm.hip).  workspace: at least attention_gemm_workspace() bytes (one image); with more, single-head layers run up to 8
-// images per launch (grouped GEMMs); tap1x1: device int holding the 1x1 tap ((32 << 6) | 32);
-// partial: split-K scratch of launch_conv_gemm.  Same arguments / results as the flash launchers.
-bool attention_gemm_supported(const AttnParams& p);
+// ... and the GEMM route or a refusal.  Same arguments / results as the flash launchers.
 size_t attention_gemm_workspace(int Nq, int Nk, int D, int bwd);
 hipError_t launch_attention_gemm_fwd(const AttnParams& p, void* workspace, size_t workspace_bytes, const int* tap1x1, float* partial, size_t partial_cap, hipStream_t stream);
 hipError_t launch_attention_gemm_bwd(const AttnParams& p, void* workspace, size_t workspace_bytes, const int* tap1x1, float* partial, size_t partial_cap, hipStream_t stream);

@@ -41,6 +41,16 @@ int dd_op_layernorm_fwd(const LayerNormParams* p, void* st) { return (int)launch
 int dd_op_layernorm_bwd(const LayerNormParams* p, void* st) { return (int)launch_layernorm_bwd(*p, S(st)); }
 int dd_op_attention_fwd(const AttnParams* p, void* st) { return (int)launch_attention_fwd(*p, S(st)); }
 int dd_op_attention_bwd(const AttnParams* p, void* st) { return (int)launch_attention_bwd(*p, S(st)); }
+int dd_op_attention(const AttnParams* p, void* ws, size_t ws_bytes, const int* tap1x1, float* partial, size_t cap, int bwd, void* st) {
+  return (int)launch_attention(*p, AttnScratch{ws, ws_bytes, tap1x1, partial, cap}, bwd != 0, S(st));
+}
+int dd_op_attention_plan(const AttnParams* p, size_t ws_bytes, int bwd, int* out) {
+  if (!p || !out) return -1;                            // DD_ERR_ARG
+  return attention_plan_query(*p, ws_bytes, bwd != 0, out);
+}
+size_t dd_op_attention_scratch_bytes(int B, int heads, int Nq, int Nk, int D, int causal, int cross, int want_grad) {
+  return attention_scratch_bytes(B, heads, Nq, Nk, D, causal != 0, cross != 0, want_grad != 0);
+}
 size_t dd_op_attention_gemm_workspace(int Nq, int Nk, int D, int bwd) { return attention_gemm_workspace(Nq, Nk, D, bwd); }
 int dd_op_attention_gemm_fwd(const AttnParams* p, void* ws, size_t ws_bytes, const int* tap1x1, float* partial, size_t cap, void* st) {
   return (int)launch_attention_gemm_fwd(*p, ws, ws_bytes, tap1x1, partial, cap, S(st));

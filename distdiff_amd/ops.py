@@ -274,39 +274,7 @@ def layernorm(x, gamma, beta, eps, dy=None, stats=None, accumulate_into=None):
     return dx
 
 
-def attention_gemm(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, ws_images=8):
-    """wide-head attention through the GEMM kernel (dd_op_attention_gemm_*): same arguments / results as `attention`.  ws_images: scratch
-    for that many images (single-head layers then run min(ws_images, 8, B) images per launch)."""
-    L = _lib.lib()
-    L.dd_op_attention_gemm_workspace.restype = C.c_size_t
-    p = AttnParams()
-    o = torch.zeros((B * Nq, H * D), device=q.device, dtype=torch.bfloat16)
-    lse = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
-    p.q, p.k, p.v, p.o, p.lse = _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse)
-    p.ldq, p.ldk, p.ldv, p.ldo = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
-    p.B, p.H, p.Nq, p.Nk, p.D, p.scale = B, H, Nq, Nk, D, scale
-    ws = torch.empty(L.dd_op_attention_gemm_workspace(Nq, Nk, D, 1) * max(1, ws_images), device=q.device, dtype=torch.uint8)
-    tap = torch.tensor([(32 << 6) | 32], device=q.device, dtype=torch.int32)
-    part = torch.empty(32 * 1024 * 1024, device=q.device, dtype=torch.float32)
-    check(L.dd_op_attention_gemm_fwd(C.byref(p), _ptr(ws), C.c_size_t(ws.numel()), _ptr(tap), _ptr(part), C.c_size_t(part.numel() * 4), _stream()), "attn_gemm_fwd")
-    if d_o is None:
-        return o, lse
-    dq = torch.zeros_like(o)
-    dk = torch.zeros((B * Nk, H * D), device=q.device, dtype=torch.bfloat16)
-    dv = torch.zeros_like(dk)
-    delta = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
-    p.d_o, p.lddo, p.dq, p.lddq, p.delta = _ptr(d_o), d_o.stride(0), _ptr(dq), dq.stride(0), _ptr(delta)
-    p.dk, p.dv, p.lddk, p.lddv = _ptr(dk), _ptr(dv), dk.stride(0), dv.stride(0)
-    check(L.dd_op_attention_gemm_bwd(C.byref(p), _ptr(ws), C.c_size_t(ws.numel()), _ptr(tap), _ptr(part), C.c_size_t(part.numel() * 4), _stream()), "attn_gemm_bwd")
-    torch.cuda.synchronize()
-    return o, lse, dq, dk, dv
-
-
-def attention(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, need_dkv=True, causal=False, q_prescaled=False, pv_fp8=False, no_shortk=False):
-    """q [B*Nq, >=H*D], k/v [B*Nk, >=H*D] bf16 (row strides taken from the tensors).  q_prescaled: q already carries
-    1/sqrt(D) * log2(e) (the engine folds it into the to_q weights); pass scale = ln 2 then.  pv_fp8 (D = 64, forward): the P.V product
-    on the block-scaled fp8 MFMA (e4m3 probabilities and values)."""
-    L = _lib.lib()
+def _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, causal=False, q_prescaled=False, pv_fp8=False, no_shortk=False):
     p = AttnParams()
     o = torch.zeros((B * Nq, H * D), device=q.device, dtype=torch.bfloat16)
     lse = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
@@ -317,18 +285,91 @@ def attention(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, need_dkv=True, causal=F
     p.q_prescaled = 1 if q_prescaled else 0
     p.pv_fp8 = 1 if pv_fp8 else 0
     p.no_shortk = 1 if no_shortk else 0       # diagnostics: <= 80 keys on the streaming kernel (accuracy A/B)
-    check(L.dd_op_attention_fwd(C.byref(p), _stream()), "attn_fwd")
-    if d_o is None:
-        return o, lse
+    return p, o, lse
+
+
+def _attn_bwd_params(p, o, d_o, need_dkv=True):
+    """adds the backward's buffers to p; returns (dq, dk, dv, delta): delta only has to stay alive"""
     dq = torch.zeros_like(o)
-    dk = torch.zeros((B * Nk, H * D), device=q.device, dtype=torch.bfloat16) if need_dkv else None
+    dk = torch.zeros((p.B * p.Nk, p.H * p.D), device=o.device, dtype=torch.bfloat16) if need_dkv else None
     dv = torch.zeros_like(dk) if need_dkv else None
-    delta = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
+    delta = torch.empty((p.B, p.H, p.Nq), device=o.device, dtype=torch.float32)
     p.d_o, p.lddo, p.dq, p.lddq, p.delta = _ptr(d_o), d_o.stride(0), _ptr(dq), dq.stride(0), _ptr(delta)
     if need_dkv:
         p.dk, p.dv, p.lddk, p.lddv = _ptr(dk), _ptr(dv), dk.stride(0), dv.stride(0)
+    return dq, dk, dv, delta
+
+
+def _attn_scratch(q, Nq, Nk, D, ws_images):
+    """(workspace, bytes, tap1x1, partial, bytes) of the dd_op_attention* argument lists, and the tensors behind them"""
+    L = _lib.lib()
+    L.dd_op_attention_gemm_workspace.restype = C.c_size_t
+    if ws_images <= 0:
+        return (None, C.c_size_t(0), None, None, C.c_size_t(0)), None
+    ws = torch.empty(L.dd_op_attention_gemm_workspace(Nq, Nk, D, 1) * ws_images, device=q.device, dtype=torch.uint8)
+    tap = torch.tensor([(32 << 6) | 32], device=q.device, dtype=torch.int32)
+    part = torch.empty(32 * 1024 * 1024, device=q.device, dtype=torch.float32)
+    return (_ptr(ws), C.c_size_t(ws.numel()), _ptr(tap), _ptr(part), C.c_size_t(part.numel() * 4)), (ws, tap, part)
+
+
+def attention_gemm(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, ws_images=8):
+    """wide-head attention through the GEMM kernel (dd_op_attention_gemm_*): same arguments / results as `attention`.  ws_images: scratch
+    for that many images (single-head layers then run min(ws_images, 8, B) images per launch)."""
+    L = _lib.lib()
+    p, o, lse = _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale)
+    sc, _keep = _attn_scratch(q, Nq, Nk, D, max(1, ws_images))
+    check(L.dd_op_attention_gemm_fwd(C.byref(p), *sc, _stream()), "attn_gemm_fwd")
+    if d_o is None:
+        return o, lse
+    dq, dk, dv, _delta = _attn_bwd_params(p, o, d_o)
+    check(L.dd_op_attention_gemm_bwd(C.byref(p), *sc, _stream()), "attn_gemm_bwd")
+    torch.cuda.synchronize()
+    return o, lse, dq, dk, dv
+
+
+def attention(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, need_dkv=True, **flags):
+    """q [B*Nq, >=H*D], k/v [B*Nk, >=H*D] bf16 (row strides taken from the tensors), on the flash kernels.  flags: causal; q_prescaled: q
+    already carries 1/sqrt(D) * log2(e) (the engine folds it into the to_q weights); pass scale = ln 2 then.  pv_fp8 (D = 64, forward): the
+    P.V product on the block-scaled fp8 MFMA (e4m3 probabilities and values); no_shortk."""
+    L = _lib.lib()
+    p, o, lse = _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, **flags)
+    check(L.dd_op_attention_fwd(C.byref(p), _stream()), "attn_fwd")
+    if d_o is None:
+        return o, lse
+    dq, dk, dv, _delta = _attn_bwd_params(p, o, d_o, need_dkv)
     check(L.dd_op_attention_bwd(C.byref(p), _stream()), "attn_bwd")
     return o, lse, dq, dk, dv
+
+
+ATTENTION_ROUTES = ("gemm", "shortk", "dma", "stream", "flash_bwd")      # dd_op_attention_plan
+
+
+def _attention_plan(p, ws_bytes, bwd):
+    out = (C.c_int * 26)()
+    route = _lib.lib().dd_op_attention_plan(C.byref(p), ws_bytes, int(bwd), out)
+    if route < 0:
+        raise RuntimeError("attention_plan: the launcher refuses this problem (status %d)" % route)
+    return {"route": ATTENTION_ROUTES[route], "d": out[1], "qt": out[2], "kt": out[3], "dsplit": out[4], "ktw": out[5], "qtl": out[6],
+            "waves": out[7], "lazy": bool(out[8] & 1), "prescaled": bool(out[8] & 2), "causal": bool(out[8] & 4), "fp8": bool(out[8] & 8),
+            "group": out[9], "launches": [tuple(out[11 + 5 * j:16 + 5 * j]) for j in range(out[10])]}
+
+
+def attention_planned(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, need_dkv=True, ws_images=0, **flags):
+    """The launcher's one entry (dd_op_attention): `attention` with scratch for ws_images images offered (0: none), so that the planner
+    may take the GEMM route.  Returns the results of `attention` and the plans (dd_op_attention_plan, asked with the same arguments) of
+    the forward and, with d_o, the backward: dicts of route (ATTENTION_ROUTES), tile form, flags, group and launches."""
+    L = _lib.lib()
+    p, o, lse = _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, **flags)
+    sc, _keep = _attn_scratch(q, Nq, Nk, D, ws_images)
+    plans = [_attention_plan(p, sc[1], False)]
+    check(L.dd_op_attention(C.byref(p), *sc, 0, _stream()), "attention fwd")
+    if d_o is None:
+        return (o, lse), plans
+    dq, dk, dv, _delta = _attn_bwd_params(p, o, d_o, need_dkv)
+    plans.append(_attention_plan(p, sc[1], True))
+    check(L.dd_op_attention(C.byref(p), *sc, 1, _stream()), "attention bwd")
+    torch.cuda.synchronize()
+    return (o, lse, dq, dk, dv), plans
 
 
 def to_nhwc_bf16(x_nchw, cpad=None):

@@ -64,6 +64,19 @@ int dd_op_attention_bwd(const struct AttnParams* p, void* stream);
 size_t dd_op_attention_gemm_workspace(int Nq, int Nk, int D, int bwd);
 int dd_op_attention_gemm_fwd(const struct AttnParams* p, void* workspace, size_t workspace_bytes, const int* tap1x1, float* partial, size_t partial_cap, void* stream);
 int dd_op_attention_gemm_bwd(const struct AttnParams* p, void* workspace, size_t workspace_bytes, const int* tap1x1, float* partial, size_t partial_cap, void* stream);
+/* The one entry behind the four above: plans and launches the forward (bwd = 0) or the backward.  With workspace (as for
+ * dd_op_attention_gemm_*) a problem the GEMM route takes runs there, everything else -- and everything when workspace is NULL -- on the
+ * flash kernels: short keys, fp8 P.V, LDS-DMA staged, register-staged, in that order. */
+int dd_op_attention(const struct AttnParams* p, void* workspace, size_t workspace_bytes, const int* tap1x1, float* partial, size_t partial_cap, int bwd, void* stream);
+/* What dd_op_attention(p, a workspace of workspace_bytes, ...) would do, decided by the launcher's own planner without launching anything
+ * (no device access; the pointers are only tested for null).  Returns the route -- 0 GEMM, 1 short-key, 2 LDS-DMA staged, 3
+ * register-staged, 4 flash backward; DD_ERR_ARG (-1) for a problem the launcher refuses -- and fills out[26] = {route, head dim of the tile
+ * form, QT, KT, DSPLIT (backward: of the dQ kernel), KTW, QTL (dK/dV kernel; 0 when it does not run), waves per workgroup, bits (1 lazy
+ * reference, 2 prescaled backward, 4 causal, 8 fp8), images per GEMM group, launches, then (grid x, y, z, block, dynamic LDS bytes) of up to
+ * three launches}.  The GEMM route reports route and group only. */
+int dd_op_attention_plan(const struct AttnParams* p, size_t workspace_bytes, int bwd, int* out26);
+/* Scratch (bytes of workspace) that lets dd_op_attention take the GEMM route for such an op on up to 8 images per launch; 0: no use for any */
+size_t dd_op_attention_scratch_bytes(int B, int heads, int Nq, int Nk, int D, int causal, int cross, int want_grad);
 
 /* fp32 implicit-GEMM convolution / dgrad of the guide network (guide_f32.hip) and its weight packing: w is
  * [Cout][Cin/groups][KH][KW] fp32 (torch grouped layout); out4 = {N, K, cin, ntaps}; wp may be NULL to query sizes */

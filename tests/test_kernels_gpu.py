@@ -776,6 +776,41 @@ def test_attention_causal(ops, case):
     assert_close(lse, torch.logsumexp(s, dim=-1), rtol=1e-3, atol=1e-3, what=name + " LSE")
 
 
+
+@pytest.mark.parametrize("case", [("gemm_route_d512_two_images_of_scratch", 2, 1, 256, 256, 512, 2, False, "gemm"),
+                                  ("register_staged_d512_no_scratch", 2, 1, 256, 256, 512, 0, False, "stream"),
+                                  ("short_keys_d40_prescaled", 1, 8, 64, 77, 40, 0, True, "shortk")], ids=lambda c: c[0])
+def test_attention_one_entry_takes_the_planned_route(ops, case):
+    """dd_op_attention (plan, then launch) against the forced-path ops on the same inputs, bit for bit -- O, LSE and the gradients -- and
+    the plan dd_op_attention_plan reports for the same arguments: with scratch for two images the single-head d = 512 layer runs on the
+    GEMM route, both images in one group; without scratch on the register-staged kernel with the head dim split over the four waves; 77
+    keys at d = 40 on the short-key kernel (cross-attention: dQ only)."""
+    name, B, H, Nq, Nk, D, ws_images, pre, route = case
+    g = torch.Generator().manual_seed(29)
+    dev = lambda n: torch.randn(B * n, H * D, generator=g).to(torch.bfloat16).cuda()
+    q, k, v, d_o = dev(Nq), dev(Nk), dev(Nk), dev(Nq)
+    cross = Nk == 77
+    flags = dict(q_prescaled=True) if pre else {}
+    args = (q, k, v, B, H, Nq, Nk, D, 0.6931471805599453 if pre else 1.0 / math.sqrt(D))
+    got, (fwd, bwd) = ops.attention_planned(*args, d_o=d_o, need_dkv=not cross, ws_images=ws_images, **flags)
+    if route == "gemm":
+        want = ops.attention_gemm(*args, d_o=d_o, ws_images=ws_images)
+    else:
+        want = ops.attention(*args, d_o=d_o, need_dkv=not cross, **flags)
+    torch.cuda.synchronize()
+    assert fwd["route"] == route and bwd["route"] == ("gemm" if route == "gemm" else "flash_bwd"), (fwd, bwd)
+    if route == "gemm":
+        assert fwd["group"] == 2 and bwd["group"] == 2
+    if route == "stream":
+        assert (fwd["d"], fwd["dsplit"], bwd["dsplit"]) == (512, 4, 4) and fwd["launches"] == [(4, 1, 2, 256, 2 * 32 * (512 * 2 + 32))]
+    if route == "shortk":
+        assert (fwd["d"], fwd["waves"]) == (40, 8) and len(bwd["launches"]) == 2 and bwd["prescaled"]
+    for what, a, b in zip(("O", "LSE", "dQ", "dK", "dV"), got, want):
+        assert (a is None) == (b is None) == (cross and what in ("dK", "dV")), what
+        if a is not None:
+            assert torch.equal(a, b), "%s: %s differs from the forced path" % (name, what)
+
+
 def test_elementwise_sampler_ops(ops):
     from distdiff_amd import _lib
     L = _lib.lib()
