@@ -105,7 +105,7 @@ OPS_SYMBOLS = [
     "dd_op_sub_scaled", "dd_op_energy_weighted", "dd_op_mask_f32", "dd_op_add_f32", "dd_op_copy_f32", "dd_op_maxpool3x3s2_f32",
     "dd_op_maxpool3x3s2_bwd_f32", "dd_op_bicubic_f32", "dd_op_bicubic_bwd_f32", "dd_op_gap_f32", "dd_op_gap_bwd_f32", "dd_op_nchw_to_nhwc_f32",
     "dd_op_step_coefs", "dd_op_sampler_step_scratch_floats", "dd_op_sampler_step", "dd_op_sampler_step_bwd",
-    "dd_debug_tensor", "dd_debug_num_tensors", "dd_debug_set_image", "dd_debug_set_images",
+    "dd_debug_tensor", "dd_debug_num_tensors", "dd_debug_fusion_plan", "dd_debug_set_image", "dd_debug_set_images",
 ]
 ENGINE_SYMBOLS = [
     "dd_abi_version", "dd_create", "dd_destroy", "dd_last_error", "dd_load_tensor", "dd_finalize_weights", "dd_set_prototypes",

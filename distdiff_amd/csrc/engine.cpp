@@ -13,10 +13,10 @@ namespace {
 // sampler drivers
 // ---------------------------------------------------------------------------------------------------
 struct Run {
-  dd_engine* E; hipStream_t s; int B;
+  dd_engine* E; hipStream_t s;
   Ctx ctx(const Program& P, char* act) {
     Ctx c; c.act = act; c.grad = E->grad_slab; c.tr = E->tr_slab; c.tr_stride = P.tr_max; c.scratch_partial = E->scratch_partial; c.partial_cap = E->partial_cap;
-    c.scratch_tmp = E->scratch_tmp; c.tmp_cap = E->tmp_cap; c.tap1x1 = E->tap1x1; c.gn_scratch = E->gn_scratch; c.rowpart = E->rowpart; c.s = s; c.B = B; c.cross_kv = &E->cross_kv; c.flops = &E->flops; c.prof = &E->prof;
+    c.scratch_tmp = E->scratch_tmp; c.tmp_cap = E->tmp_cap; c.tap1x1 = E->tap1x1; c.gn_scratch = E->gn_scratch; c.rowpart = E->rowpart; c.s = s; c.cross_kv = &E->cross_kv; c.flops = &E->flops; c.prof = &E->prof;
     return c;
   }
 };
@@ -30,7 +30,7 @@ void check_batch(dd_engine* E, int B) {
 // UNet forward on instance k: z fp32 NCHW -> eps2 fp32 NHWC [2B*HW, ld] inside the slab
 void unet_fwd(dd_engine* E, int k, const float* z, int step_index, hipStream_t s, bool stash = true) {
   const dd_config& c = E->cfg;
-  Run r{E, s, c.max_batch};
+  Run r{E, s};
   Ctx ctx = r.ctx(E->unet, E->inst[k].unet);
   ctx.step_index = step_index;
   ctx.stash = stash;
@@ -46,7 +46,7 @@ void unet_fwd(dd_engine* E, int k, const float* z, int step_index, hipStream_t s
 
 void vae_fwd(dd_engine* E, int k, const float* x0, hipStream_t s) {
   const dd_config& c = E->cfg;
-  Run r{E, s, c.max_batch};
+  Run r{E, s};
   Ctx ctx = r.ctx(E->vae, E->inst[k].vae);
   const Tn& in = E->vae.t[E->vae_in];
   HIPCHK(launch_nchw_f32_to_nhwc_bf16(x0, act_ptr(ctx, in), c.max_batch, c.vae_latent_channels, c.latent_size, c.latent_size, in.ld,
@@ -77,7 +77,7 @@ void guide_features_grad_in(dd_engine* E, const Ctx& gc, const float* gfeat, hip
 // guide forward from the decoded image of instance k (bicubic -> guide network -> features) -> feat [B, D]
 void guide_fwd_from_image(dd_engine* E, int k, hipStream_t s) {
   const dd_config& c = E->cfg;
-  Run r{E, s, c.max_batch};
+  Run r{E, s};
   Ctx gc = r.ctx(E->guide, E->inst[k].guide);
   Ctx vc = r.ctx(E->vae, E->inst[k].vae);
   const Tn& img = E->vae.t[E->vae_out];
@@ -96,7 +96,7 @@ void guide_fwd_from_image(dd_engine* E, int k, hipStream_t s) {
 // reverse of guide_fwd_from_image + vae_fwd: gfeat -> g_x0 (fp32 NCHW)
 void guide_vae_bwd(dd_engine* E, int k, float* g_x0, hipStream_t s) {
   const dd_config& c = E->cfg;
-  Run r{E, s, c.max_batch};
+  Run r{E, s};
   Ctx gc = r.ctx(E->guide, E->inst[k].guide);
   Ctx vc = r.ctx(E->vae, E->inst[k].vae);
   const Tn& f = E->guide.t[E->guide_feat];
@@ -149,7 +149,7 @@ void guided_forward(dd_engine* E, int k, const float* z_in, int step_index, cons
 void guided_backward(dd_engine* E, int k, int step_index, const float* g_znext, float* g_z_out, float* g_x0_tmp, hipStream_t s) {
   const dd_config& c = E->cfg;
   const int HW = c.latent_size * c.latent_size;
-  Run r{E, s, c.max_batch};
+  Run r{E, s};
   guide_vae_bwd(E, k, g_x0_tmp, s);
   Ctx uc = r.ctx(E->unet, E->inst[k].unet);
   uc.step_index = step_index;
@@ -345,6 +345,18 @@ int dd_finalize_weights(dd_engine* E) {
       E->cross_kv.push_back({k, v});
     }
     HIPCHK(hipDeviceSynchronize());
+    // the statistics fusions of every program, asked of the launcher's planner on the context its forward runs get
+    {
+      Run r{E, nullptr};
+      Ctx uc = r.ctx(E->unet, E->inst[0].unet);
+      if (c.unet_add_time_dim > 0) uc.img_bias = 2 * c.max_batch;
+      resolve_fusions(E->unet, uc);
+      resolve_fusions(E->vae, r.ctx(E->vae, E->inst[0].vae));
+      resolve_fusions(E->guide, r.ctx(E->guide, E->inst[0].guide));
+      if (have_venc) resolve_fusions(E->venc, r.ctx(E->venc, E->venc_slab));
+      if (have_text) resolve_fusions(E->text, r.ctx(E->text, E->text_slab));
+      if (have_text2) resolve_fusions(E->text2, r.ctx(E->text2, E->text2_slab));
+    }
     E->finalized = true;
   });
 }
@@ -545,7 +557,7 @@ int dd_vae_encode(dd_engine* E, const float* images, const float* noise, float* 
     if (!E->venc_slab) throw std::runtime_error("no VAE encoder weights were loaded (vae/encoder.* keys)");
     const dd_config& c = E->cfg;
     hipStream_t s = (hipStream_t)stream;
-    Run r{E, s, B};
+    Run r{E, s};
     Ctx ctx = r.ctx(E->venc, E->venc_slab);
     ctx.stash = false;
     const Tn& in = E->venc.t[E->venc_in];
@@ -571,7 +583,7 @@ int dd_text_encode_tower(dd_engine* E, int which, const int* input_ids, float* h
     const int T = c.text_len, Cc = which ? E->text2_hidden : E->text_hidden;
     HIPCHK(hipMemsetAsync(E->text_ids, 0, (size_t)E->text_batch * T * 4, s));
     HIPCHK(hipMemcpyAsync(E->text_ids, input_ids, (size_t)n * T * 4, hipMemcpyDeviceToDevice, s));
-    Run r{E, s, E->text_batch};
+    Run r{E, s};
     Ctx ctx = r.ctx(P, slab);
     ctx.stash = false;
     const Tn& in = P.t[which ? E->text2_in : E->text_in];
@@ -606,7 +618,7 @@ int dd_guide_encode_pooled(dd_engine* E, const float* images, float* feats, int 
     if (use_max && E->cfg.guide_kind == 1) throw std::runtime_error("the ViT guide has no spatial pooling (encode_image = the projected class token)");
     const dd_config& c = E->cfg;
     hipStream_t s = (hipStream_t)stream;
-    Run r{E, s, B};
+    Run r{E, s};
     Ctx gc = r.ctx(E->guide, E->inst[0].guide);
     const Tn& gin = E->guide.t[E->guide_in];
     HIPCHK(launch_nchw_to_nhwc_f32(images, act_f32(gc, gin), B, 3, gin.H, gin.W, gin.ld, gin.ld, s));
@@ -796,7 +808,7 @@ int dd_unet_vjp(dd_engine* E, const float* z, int step_index, const float* g_eps
     hipStream_t s = (hipStream_t)stream;
     const int HW = c.latent_size * c.latent_size;
     unet_fwd(E, 0, z, step_index, s);
-    Run r{E, s, B};
+    Run r{E, s};
     Ctx uc = r.ctx(E->unet, E->inst[0].unet);
     uc.step_index = step_index;
     const Tn& out = E->unet.t[E->unet_out];
@@ -816,7 +828,7 @@ int dd_decode_vjp(dd_engine* E, const float* z, const float* g_image, float* g_z
     if (!c.enable_grad) throw std::runtime_error("engine created with enable_grad=0");
     hipStream_t s = (hipStream_t)stream;
     vae_fwd(E, 0, z, s);
-    Run r{E, s, B};
+    Run r{E, s};
     Ctx vc = r.ctx(E->vae, E->inst[0].vae);
     const Tn& img = E->vae.t[E->vae_out];
     HIPCHK(launch_nchw_f32_to_nhwc_bf16(g_image, grad_ptr(vc, img), B, c.vae_out_channels, img.H, img.W, img.ld, img.ld, 0, 1.f, s));
@@ -834,7 +846,7 @@ int dd_guide_vjp(dd_engine* E, const float* images, const float* g_feats, float*
     const dd_config& c = E->cfg;
     if (!c.enable_grad) throw std::runtime_error("engine created with enable_grad=0");
     hipStream_t s = (hipStream_t)stream;
-    Run r{E, s, B};
+    Run r{E, s};
     Ctx gc = r.ctx(E->guide, E->inst[0].guide);
     const Tn& gin = E->guide.t[E->guide_in];
     HIPCHK(launch_nchw_to_nhwc_f32(images, act_f32(gc, gin), B, 3, gin.H, gin.W, gin.ld, gin.ld, s));
@@ -912,6 +924,20 @@ int dd_debug_set_images(dd_engine* E, const float* images, int count) {
   return DD_OK;
 }
 int dd_debug_set_image(dd_engine* E, const float* image) { return dd_debug_set_images(E, image, 1); }
+// the statistics fusions fixed at finalize, four ints per op (include/distdiff_hip_ops.h); prog 0 unet, 1 vae, 2 guide, 3 vae encoder
+int dd_debug_fusion_plan(dd_engine* E, int prog, int* out, int cap) {
+  if (!E || prog < 0 || prog > 3 || (cap > 0 && !out)) return DD_ERR_ARG;
+  if (!E->finalized) { E->err = "finalize first"; return DD_ERR_STATE; }
+  const Program& P = prog == 0 ? E->unet : prog == 1 ? E->vae : prog == 2 ? E->guide : E->venc;
+  for (int i = 0; i < (int)P.ops.size() && i < cap; ++i) {
+    const Op& op = P.ops[i];
+    out[4 * i] = op.kind;
+    out[4 * i + 1] = (op.kind == OP_CONV || op.kind == OP_GN) && op.part ? (int)op.gn_fused : -1;
+    out[4 * i + 2] = (op.kind == OP_CONV && op.rowstat_emit) || (op.kind == OP_LN && op.ln_fold) ? op.row_spans : -1;
+    out[4 * i + 3] = 0;
+  }
+  return (int)P.ops.size();
+}
 int dd_debug_num_tensors(dd_engine* E, int prog) {
   if (!E || prog < 0 || prog > 2) return DD_ERR_ARG;
   return (int)(prog == 0 ? E->unet : prog == 1 ? E->vae : E->guide).t.size();

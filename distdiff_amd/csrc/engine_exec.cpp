@@ -61,7 +61,7 @@ void run_conv_f32_bwd(const Program& P, const Op& op, const Ctx& c) {
   HIPCHK(launch_conv_f32(p, c.s));
 }
 
-// forward launch parameters of a bf16 convolution / linear op (everything but the run-time fusion flags)
+// forward launch parameters of a bf16 convolution / linear op (everything but the statistics fusions)
 static void fwd_conv_params(const Program& P, const Op& op, const Ctx& c, ConvGemmParams& p) {
   const Tn& x = P.t[op.x_fwd >= 0 ? op.x_fwd : op.x]; const Tn& y = P.t[op.y];
   fill_conv(p, c);
@@ -113,13 +113,64 @@ static AttnScratch attn_scratch(const Op& op, const Ctx& c) {
   return AttnScratch{c.scratch_tmp, c.tmp_cap, c.tap1x1, (float*)c.scratch_partial, c.partial_cap};
 }
 
-void run_fwd(const Program& P, const Ctx& c, int op_begin, int op_end) {
-  if (op_end < 0) op_end = (int)P.ops.size();
+// SDXL text_time conditioning: the time-embedding bias of this conv differs per image, it runs as one launch per image
+static bool per_image_bias(const Op& op, const Ctx& c) { return op.use_table && c.img_bias > 0; }
+
+// What the launcher's planner grants the statistics epilogues of forward conv `op` on its launch parameters p (fwd_conv_params):
+// GroupNorm partials (CF_STATS) yes / no, and the column spans of LayerNorm row partials (CF_ROWSTATS; 0 = none).  An op that is a
+// candidate for both keeps CF_STATS: one statistics epilogue per launch.  A function of shapes, leading dimensions, flags, partial_cap
+// and which pointers are null only, so the answer at finalize (resolve_fusions) is the answer at every launch.
+struct Fusions { bool stats; int spans; };
+static Fusions ask_fusions(const Program& P, const Op& op, const Ctx& c, ConvGemmParams p) {
+  Fusions f{false, 0};
+  if (op.rowstat_emit && !op.part && c.rowpart) {
+    ConvGemmParams q = p;
+    q.rowpart = c.rowpart; q.rowpart_ld = op.rowstat_ld;
+    int spans = 0;
+    if (conv_gemm_can_emit_rowstats(q, c.partial_cap, &spans) && spans <= op.rowstat_ld) f.spans = spans;
+  }
+  if (op.part) {
+    const Tn& y = P.t[op.y];
+    p.stats = (float*)(c.act + op.part_off); p.stats_ld = op.part_ld;
+    bool whole = true;
+    if (per_image_bias(op, c)) { p.B = 1; p.M = y.H * y.W; whole = !(p.M & 63); }      // an image's launch must fill whole 64-row blocks
+    f.stats = whole && conv_gemm_can_emit_stats(p, c.partial_cap);
+  }
+  return f;
+}
+
+void resolve_fusions(Program& P, const Ctx& c) {
+  int ngn = 0, nmerge = 0, nfold = 0, nrows = 0;
+  for (Op& op : P.ops) {
+    if (op.kind == OP_CONV && (op.part || op.rowstat_emit)) {
+      ConvGemmParams p;
+      fwd_conv_params(P, op, c, p);
+      if (op.use_table) p.flags |= CF_BIAS;      // the bias tables arrive with dd_set_schedule
+      const Fusions f = ask_fusions(P, op, c, p);
+      op.gn_fused = f.stats; op.row_spans = f.spans;
+    } else if (op.kind == OP_GN) {
+      op.gn_fused = op.part;
+      for (int pi : op.producers) op.gn_fused = op.gn_fused && P.ops[pi].gn_fused;
+      ++ngn; nmerge += op.gn_fused;
+    } else if (op.kind == OP_LN && op.ln_fold) {
+      op.row_spans = op.rowstat_from >= 0 ? P.ops[op.rowstat_from].row_spans : 0;
+      ++nfold; nrows += op.row_spans > 0;
+    }
+  }
+  if (getenv("DD_PLAN_REPORT"))
+    fprintf(stderr, "[plan] statistics fusions: %d of %d GroupNorms merge their producers' partials, %d of %d folded LayerNorms read row partials\n", nmerge, ngn, nrows, nfold);
+}
+
+static int op_family(const Program& P, const Op& op) {
+  return (op.kind == OP_CONV && !P.f32) ? Profiler::CONV : op.kind == OP_ATTN ? Profiler::ATTN
+         : (op.kind == OP_GN || op.kind == OP_LN) ? Profiler::NORM : Profiler::OTHER;
+}
+
+void run_fwd(const Program& P, const Ctx& c) {
   if (c.prof) c.prof->new_run();
-  for (int i = op_begin; i < op_end; ++i) {
+  for (int i = 0; i < (int)P.ops.size(); ++i) {
     const Op& op = P.ops[i];
-    const int fam = (op.kind == OP_CONV && !P.f32) ? Profiler::CONV : op.kind == OP_ATTN ? Profiler::ATTN
-                    : (op.kind == OP_GN || op.kind == OP_LN) ? Profiler::NORM : Profiler::OTHER;
+    const int fam = op_family(P, op);
     if (c.prof) {
       if (op.kind == OP_CONV) c.prof->begin(fam, op.flops, c.s, P.t[op.y].rows, op.cw->sf.N, op.cw->sf.K, 0);
       else if (op.kind == OP_ATTN) c.prof->begin(fam, op.flops, c.s, op.Nq, op.Nk, op.D, 0);
@@ -132,64 +183,41 @@ void run_fwd(const Program& P, const Ctx& c, int op_begin, int op_end) {
         const ConvW* w = op.cw;
         ConvGemmParams p;
         fwd_conv_params(P, op, c, p);
-        if (op.rowstat_emit) {
-          // LayerNorm row partials for the op that follows: only when the kernel the launcher picks for this shape has the form
-          p.rowpart = c.rowpart; p.rowpart_ld = op.rowstat_ld;
-          int spans = 0;
-          // (an op that is also a GroupNorm-partials producer keeps CF_STATS: one statistics epilogue per launch, and the consumer of the
-          // row partials falls back to its own statistics pass through row_spans == 0)
-          if (!op.part && c.rowpart && conv_gemm_can_emit_rowstats(p, c.partial_cap, &spans) && spans <= op.rowstat_ld) { p.flags |= CF_ROWSTATS; P.row_spans[i] = spans; }
-          else { p.rowpart = nullptr; P.row_spans[i] = 0; }
+        if (g_plan_check && (op.part || op.rowstat_emit)) {
+          const Fusions f = ask_fusions(P, op, c, p);
+          if (f.stats != op.gn_fused || f.spans != op.row_spans)
+            throw std::runtime_error("fusion plan violated: op " + std::to_string(i) + " was planned with (CF_STATS " + std::to_string(op.gn_fused) +
+                                     ", row spans " + std::to_string(op.row_spans) + "), this launch is granted (" + std::to_string(f.stats) + ", " +
+                                     std::to_string(f.spans) + ")");
         }
-        if (op.use_table && c.img_bias > 0 && w->bias_table_img) {
-          // SDXL text_time conditioning: the time-embedding bias differs per image -> one launch per image of the batch (B x H x W
-          // rows each; at 128x128 / 64x64 / 32x32 latents an image still fills the chip), each with its own row of the bias table
-          if (x.B != c.img_bias || op.stride != 1 || op.up) throw std::runtime_error("per-image bias: unexpected conv geometry");
+        // the statistics fusions fixed at finalize (resolve_fusions): LayerNorm row partials for the op that follows, GroupNorm partials
+        if (op.row_spans > 0) { p.flags |= CF_ROWSTATS; p.rowpart = c.rowpart; p.rowpart_ld = op.rowstat_ld; }
+        if (op.gn_fused) { p.flags |= CF_STATS; p.stats = (float*)(c.act + op.part_off); p.stats_ld = op.part_ld; }
+        if (per_image_bias(op, c)) {
+          // one launch per image of the batch (H x W rows each; at 128x128 / 64x64 / 32x32 latents an image still fills the chip),
+          // each with its own row of the bias table
+          if (x.B != c.img_bias || op.stride != 1 || op.up || !w->bias_table_img) throw std::runtime_error("per-image bias: unexpected conv geometry");
           const size_t xrows = (size_t)x.H * x.W, yrows = (size_t)y.H * y.W;
           ConvGemmParams q = p;
           q.B = 1; q.M = (int)yrows;
-          bool emit = false;
-          if (op.part) {
-            q.stats = (float*)(c.act + op.part_off); q.stats_ld = op.part_ld;
-            emit = !(yrows & 63) && conv_gemm_can_emit_stats(q, c.partial_cap);
-            if (emit) q.flags |= CF_STATS; else q.stats = nullptr;
-            P.emitted[i] = emit ? 1 : 0;
-          }
           for (int bi = 0; bi < x.B; ++bi) {
             ConvGemmParams r = q;
             r.x = p.x + bi * xrows * x.ld;
             r.y = (char*)p.y + bi * yrows * y.ld * 2;
             r.bias = w->bias_table_img + ((size_t)c.step_index * c.img_bias + bi) * w->Cout;
-            if (emit) r.stats = q.stats + (size_t)bi * (yrows / 64) * op.part_ld * 2;
+            if (op.gn_fused) r.stats = q.stats + (size_t)bi * (yrows / 64) * op.part_ld * 2;
             HIPCHK(launch_conv_gemm(r, c.partial_cap, c.s));
           }
-          if (c.flops) *c.flops += op.flops;
-          break;
+        } else {
+          HIPCHK(launch_conv_gemm(p, c.partial_cap, c.s));
         }
-        if (op.part) {
-          p.stats = (float*)(c.act + op.part_off); p.stats_ld = op.part_ld;
-          const bool emit = conv_gemm_can_emit_stats(p, c.partial_cap);
-          if (emit) p.flags |= CF_STATS; else p.stats = nullptr;
-          P.emitted[i] = emit ? 1 : 0;
-        }
-        HIPCHK(launch_conv_gemm(p, c.partial_cap, c.s));
         if (c.flops) *c.flops += op.flops;
       } break;
       case OP_GN: {
         const Tn& x = P.t[op.x]; const Tn& y = P.t[op.y];
         GroupNormParams p; memset(&p, 0, sizeof p);
-        const float* chan_part = nullptr;
-        if (op.part) {
-          bool all = true;
-          for (int pi : op.producers) all = all && P.emitted[pi];
-          if (all) chan_part = (const float*)(c.act + op.part_off);
-        }
-        if (getenv("DD_GN_REPORT")) {
-          static int n_total = 0, n_fused = 0;
-          ++n_total; n_fused += chan_part ? 1 : 0;
-          if (n_total % 200 == 0) fprintf(stderr, "[gn] %d of %d GroupNorm forwards took their statistics from the producing convolutions\n", n_fused, n_total);
-        }
-        p.chan_part = chan_part; p.part_ld = op.part_ld;
+        if (op.gn_fused) p.chan_part = (const float*)(c.act + op.part_off);      // every producer emitted its partials
+        p.part_ld = op.part_ld;
         p.x = act_ptr(c, x); p.x_ld = x.ld; p.y = act_ptr(c, y); p.y_ld = y.ld;
         p.gamma = op.nw->gamma; p.beta = op.nw->beta; p.stats = (float*)(c.act + op.stats_off); p.scratch = c.gn_scratch;
         p.B = x.B; p.HW = x.H * x.W; p.C = x.C; p.G = op.G; p.eps = op.eps; p.silu = op.silu;
@@ -202,9 +230,9 @@ void run_fwd(const Program& P, const Ctx& c, int op_begin, int op_end) {
         p.gamma = op.nw->gamma; p.beta = op.nw->beta; p.stats = (float*)(c.act + op.stats_off);
         p.M = x.rows; p.C = x.C; p.eps = op.eps;
         if (op.ln_fold) {
-          // folded into the linear that follows: statistics only, from the producing GEMM's row partials when it emitted them
+          // folded into the linear that follows: statistics only, from the producing GEMM's row partials when it emits them
           p.y = nullptr;
-          if (op.rowstat_from >= 0 && P.row_spans[op.rowstat_from] > 0) { p.rowpart = c.rowpart; p.rowpart_ld = op.rowstat_ld; p.spans = P.row_spans[op.rowstat_from]; }
+          if (op.row_spans > 0) { p.rowpart = c.rowpart; p.rowpart_ld = op.rowstat_ld; p.spans = op.row_spans; }
         }
         HIPCHK(launch_layernorm_fwd(p, c.s));
       } break;
@@ -250,8 +278,9 @@ void run_fwd(const Program& P, const Ctx& c, int op_begin, int op_end) {
   }
 }
 
-// DD_GRAD_CHECK=1: every gradient access of run_bwd is checked against the interval plan_grad_memory packed the slab by
-bool ddi::g_grad_check = getenv("DD_GRAD_CHECK") != nullptr && atoi(getenv("DD_GRAD_CHECK")) != 0;
+// DD_GRAD_CHECK=1 validates the finalize-time plans at run time: every gradient access of run_bwd against the interval plan_grad_memory
+// packed the slab by, every statistics fusion of run_fwd (resolve_fusions) against what the planner grants that launch
+bool ddi::g_plan_check = getenv("DD_GRAD_CHECK") != nullptr && atoi(getenv("DD_GRAD_CHECK")) != 0;
 static thread_local int t_bwd_op = INT32_MIN;     // op whose backward is running (INT32_MIN: outside run_bwd)
 void ddi::grad_access_check(const Tn& t) {
   if (t_bwd_op == INT32_MIN) return;
@@ -266,8 +295,7 @@ void run_bwd(const Program& P, const Ctx& c) {
   for (int i = (int)P.ops.size() - 1; i >= 0; --i) {
     const Op& op = P.ops[i];
     t_bwd_op = i;
-    const int fam = (op.kind == OP_CONV && !P.f32) ? Profiler::CONV : op.kind == OP_ATTN ? Profiler::ATTN
-                    : (op.kind == OP_GN || op.kind == OP_LN) ? Profiler::NORM : Profiler::OTHER;
+    const int fam = op_family(P, op);
     if (c.prof) {
       if (op.kind == OP_CONV) c.prof->begin(fam, op.flops, c.s, P.t[op.x].rows << (2 * op.up), op.cw->sb.N, op.cw->sb.K, 1);
       else if (op.kind == OP_ATTN) c.prof->begin(fam, op.flops * (op.cross_slot >= 0 ? 1.5 : 2.5), c.s, op.Nq, op.Nk, op.D, 1);

@@ -356,12 +356,10 @@ void check_transients(const Program& P) {
 // GroupNorm statistics without a pass over the tensor: when every producer of a GroupNorm's input (possibly several convolutions
 // writing column ranges of one concat buffer) is an implicit-GEMM convolution, those convolutions emit per-(64-row block, channel)
 // partial (mean, M2) from their epilogue registers and the GroupNorm merges them.  Whether a convolution can do that depends on the
-// kernel the launcher picks for its shape (conv_gemm_can_emit_stats), so the final decision is taken per run; this pass only sets up
-// the buffers and the producer lists.
+// kernel the launcher picks for its shape (conv_gemm_can_emit_stats), which needs the engine's scratch sizes: this pass only sets up
+// the buffers and the producer lists (the candidates), resolve_fusions takes the decision once at finalize.
 void plan_gn_stats(Program& P) {
   check_transients(P);
-  P.emitted.assign(P.ops.size(), 0);
-  P.row_spans.assign(P.ops.size(), 0);
   if (P.f32 || getenv("DD_NO_GN_FUSION")) return;
   std::unordered_map<int, size_t> root_part;
   for (size_t gi = 0; gi < P.ops.size(); ++gi) {

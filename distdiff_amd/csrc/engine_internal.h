@@ -111,26 +111,30 @@ struct Op {
   bool x_acc = false, res_acc = false, x2_acc = false;
   bool res_alias = false;   // the residual's gradient buffer IS this op's output-gradient buffer (first write: no copy kernel)
   // GroupNorm statistics from the producing convolutions (plan_gn_stats): conv ops emit per-(64-row block, channel) partials into
-  // the fp32 block at part_off (CF_STATS), the GroupNorm op merges them instead of reading the tensor once more
+  // the fp32 block at part_off (CF_STATS), the GroupNorm op merges them instead of reading the tensor once more.  part = the op has
+  // such a block (a candidate); gn_fused = it is used (resolve_fusions, at finalize): this OP_CONV launches with CF_STATS, this
+  // OP_GN merges the partials because every op of `producers` emits them
   bool part = false; size_t part_off = 0; int part_ld = 0;
   std::vector<int> producers;
+  bool gn_fused = false;
   // LayerNorm folded into the linear that follows (plan_ln_fold): the OP_LN only produces (mean, rstd) -- from the row partials of
   // the producing GEMM (rowstat_from = its op index, CF_ROWSTATS) when that GEMM can emit them, else from one read of the tensor --
-  // and the OP_CONV reads the LayerNorm's INPUT (x_fwd) with CF_LNFOLD; the backward plan is untouched (x stays the LayerNorm output)
+  // and the OP_CONV reads the LayerNorm's INPUT (x_fwd) with CF_LNFOLD; the backward plan is untouched (x stays the LayerNorm output).
+  // rowstat_emit = the GEMM is a candidate; row_spans (resolve_fusions, at finalize) = the column spans this OP_CONV emits with
+  // CF_ROWSTATS / this OP_LN reads, 0 = none: the LayerNorm reads the tensor
   bool ln_fold = false; int x_fwd = -1; size_t ln_stats_off = 0;
   int rowstat_from = -1; bool rowstat_emit = false; int rowstat_ld = 0;
+  int row_spans = 0;
   double flops = 0;
 };
 
-struct Program {
+struct Program {   // built and planned once (engine_graph.cpp, resolve_fusions); run_fwd / run_bwd only read it, every instance slab shares it
   std::vector<Tn> t;
   std::vector<Op> ops;
   size_t act_bytes = 0, grad_bytes = 0;
   size_t scratch_partial = 0, scratch_tmp = 0;  // shared scratch requirements (bytes)
   bool want_grad = false;
   bool f32 = false;      // every activation AND gradient of this program is fp32 (the guide network, guide_f32.hip)
-  mutable std::vector<char> emitted;   // per op, per forward run: this convolution did emit its GroupNorm partials
-  mutable std::vector<int> row_spans;  // per op, per forward run: column spans of the LayerNorm row partials this GEMM emitted (0 = none)
   size_t scratch_rowpart = 0;          // bytes of the shared row-partial buffer (producer GEMM -> LayerNorm statistics, adjacent ops)
   size_t tr_max = 0;     // bytes of one transient ping-pong buffer
   int tr_count = 0;
@@ -208,7 +212,6 @@ struct Ctx {  // per-call execution context
   const int* tap1x1 = nullptr;   // device int: the 1x1 tap, for GEMMs issued outside a ConvW (wide-head attention)
   size_t tmp_cap = 0;
   int step_index = 0;
-  int B = 0;             // live batch of this call (<= built batch)
   hipStream_t s = nullptr;
   const std::vector<std::pair<bf16_t*, bf16_t*>>* cross_kv = nullptr;  // per cross-attention slot
   double* flops = nullptr;
@@ -220,11 +223,11 @@ struct Ctx {  // per-call execution context
 
 inline char* act_raw(const Ctx& c, const Tn& t) { return t.transient ? c.tr + (size_t)t.tr_slot * c.tr_stride : c.act + t.off; }
 inline bf16_t* act_ptr(const Ctx& c, const Tn& t) { return (bf16_t*)act_raw(c, t); }
-extern bool g_grad_check;                       // DD_GRAD_CHECK=1
+extern bool g_plan_check;                       // DD_GRAD_CHECK=1: run_bwd checks the gradient plan, run_fwd the fusion plan
 void grad_access_check(const Tn& t);            // throws when run_bwd touches t's gradient outside [t.glo, t.ghi]
-inline bf16_t* grad_ptr(const Ctx& c, const Tn& t) { if (g_grad_check) grad_access_check(t); return (bf16_t*)(c.grad + t.goff); }
+inline bf16_t* grad_ptr(const Ctx& c, const Tn& t) { if (g_plan_check) grad_access_check(t); return (bf16_t*)(c.grad + t.goff); }
 inline float* act_f32(const Ctx& c, const Tn& t) { return (float*)act_raw(c, t); }
-inline float* grad_f32(const Ctx& c, const Tn& t) { if (g_grad_check) grad_access_check(t); return (float*)(c.grad + t.goff); }
+inline float* grad_f32(const Ctx& c, const Tn& t) { if (g_plan_check) grad_access_check(t); return (float*)(c.grad + t.goff); }
 
 }  // namespace ddi
 
@@ -371,6 +374,7 @@ void build_guide(dd_engine* E);
 void build_guide_mbv2(dd_engine* E);
 void build_guide_vit(dd_engine* E);
 // engine_exec.cpp
-void run_fwd(const Program& P, const Ctx& c, int op_begin = 0, int op_end = -1);
+void resolve_fusions(Program& P, const Ctx& c);   // finalize: which statistics fusions the forward run takes (Op::gn_fused, Op::row_spans)
+void run_fwd(const Program& P, const Ctx& c);
 void run_bwd(const Program& P, const Ctx& c);
 }  // namespace ddi

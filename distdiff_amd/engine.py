@@ -96,6 +96,7 @@ def _declare(l):
     l.dd_profile_read.argtypes = [vp, vp]
     l.dd_debug_tensor.argtypes = [vp, i, i, i, vp, vp]
     l.dd_debug_num_tensors.argtypes = [vp, i]
+    l.dd_debug_fusion_plan.argtypes = [vp, i, vp, i]
     l.dd_debug_set_image.argtypes = [vp, vp]
     l.dd_debug_set_images.argtypes = [vp, vp, i]
     l.dd_workspace_bytes.argtypes = [vp]
@@ -513,6 +514,16 @@ class Engine:
 
     def debug_num_tensors(self, prog):
         return int(self.L.dd_debug_num_tensors(self._h, prog))
+
+    def fusion_plan(self, prog):
+        """The statistics fusions fixed at finalize (dd_debug_fusion_plan): int32 [nops, 4] = (op kind, GroupNorm statistics, LayerNorm
+        row spans, 0) per op of program 0 unet / 1 vae / 2 guide / 3 vae encoder."""
+        n = int(self.L.dd_debug_fusion_plan(self._h, prog, None, 0))
+        if n < 0:
+            self._chk(n, "dd_debug_fusion_plan")
+        out = torch.zeros(n, 4, dtype=torch.int32)
+        self.L.dd_debug_fusion_plan(self._h, prog, vp(out.data_ptr()), n)
+        return out
 
     def workspace_bytes(self):
         return int(self.L.dd_workspace_bytes(self._h))

@@ -175,6 +175,15 @@ int dd_op_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int H, in
 struct dd_engine;
 int dd_debug_tensor(struct dd_engine* e, int prog, int idx, int want_grad, float* host_out, int* info4);
 int dd_debug_num_tensors(struct dd_engine* e, int prog);
+/* the statistics fusions of program prog = 0 unet / 1 vae / 2 guide / 3 vae encoder, fixed by dd_finalize_weights and read-only from
+ * then on: writes min(cap, ops) records of four ints, one per op in program order, and returns the op count (< 0: dd_status).
+ *   [0] op kind: 0 convolution / linear, 1 GroupNorm, 2 LayerNorm, > 2 anything else
+ *   [1] GroupNorm statistics.  Convolution: 1 emits per-channel partials from its epilogue (CF_STATS), 0 a candidate that does not,
+ *       -1 no candidate.  GroupNorm: 1 merges its producers' partials, 0 has partial buffers but runs its own pass, -1 has none
+ *   [2] LayerNorm row partials.  Linear: column spans it emits (CF_ROWSTATS), 0 a candidate that does not, -1 no candidate.
+ *       LayerNorm: spans it reads from the linear in front of it, 0 folded with its own statistics pass, -1 not folded
+ *   [3] reserved, 0 */
+int dd_debug_fusion_plan(struct dd_engine* e, int prog, int* out, int cap);
 /* parity-test hook: evaluate the guide network of every later guided forward AT these images (DEVICE fp32 [count][B,3,8L,8L], the
  * decoder's output range, caller-owned; chained guided step k reads image min(k, count-1)) instead of the decoder's own output;
  * gradients still flow through the decoder.  The input-gradient of the ReLU / max-pool guide is piecewise constant in the image, so

@@ -463,3 +463,87 @@ def test_gradient_slab_by_liveness_is_bitwise_identical(hip_lib, which):
         assert torch.equal(x, y)                          # run 2 == run 1
     assert sizes[0] < sizes[1], sizes
     print("%s: workspace %.3f GB with liveness-packed gradients, %.3f GB with one range per tensor" % (which, sizes[0] / 1e9, sizes[1] / 1e9))
+
+
+def test_fusion_plan_is_fixed_at_finalize(hip_lib):
+    """resolve_fusions (engine_exec.cpp): which convolutions emit GroupNorm partials (CF_STATS) / LayerNorm row partials (CF_ROWSTATS), and
+    which norms consume them, is decided once by dd_finalize_weights and only read by the forward runs.  The smallest engine in which the
+    decision goes both ways: 128-wide UNet levels at a 64x64 latent and batch 4 -- the level-0 3x3 convs behind the CFG split (M = 32768)
+    emit, the shared prefix (M = 16384) and levels 1-3 do not; level-0 to_out / ff.net.2 / proj_in emit row partials, level 1 does not --
+    and the tiny decoder, whose 64-channel convs emit at 128x128 and 256x256 but not at 64x64 (with every other tiny config nothing fuses).
+    Checked: the plan is self-consistent, reaches every outcome, does not change over schedule / prompt / guided and plain steps, and the
+    guided results are finite and repeat bitwise.  The suite's DD_GRAD_CHECK=1 makes every one of these forwards compare the stored decision
+    with what the launcher's planner grants the launch (a difference raises "fusion plan violated" out of the call)."""
+    from distdiff_amd.config import UNetConfig, tiny_config
+    from distdiff_amd.engine import Engine
+    from distdiff_amd.scheduler import DDIMSchedule
+    from distdiff_amd.weights import synthetic_weights
+    CONV, GN, LN = 0, 1, 2
+    B = 4
+    cfg = tiny_config(latent_size=64, max_batch=B)
+    cfg.unet = UNetConfig(block_out_channels=(128, 128, 128, 128), layers_per_block=1, num_heads=2, cross_attention_dim=64, norm_num_groups=8)
+    w = synthetic_weights(cfg, seed=0, num_classes=5)
+    eng = Engine(cfg, w, enable_grad=True, max_guidance_period=2)
+
+    def plans():
+        return [eng.fusion_plan(p) for p in (0, 1, 2)]
+
+    try:
+        at_finalize = plans()
+        g = torch.Generator().manual_seed(3)
+        L, D = cfg.latent_size, cfg.guide.feature_dim
+        sched = DDIMSchedule(cfg.scheduler)
+        ts = sched.set_timesteps(10)
+        eng.set_schedule(ts, sched.alphas_cumprod, sched.final_alpha_cumprod, guidance_period=2)
+        eng.set_prototypes(F.normalize(torch.randn(5, D, generator=g), dim=-1), F.normalize(torch.randn(5, 3, D, generator=g), dim=-1))
+        eng.set_prompt(torch.randn(2 * B, cfg.text_len, cfg.unet.cross_attention_dim, generator=g).cuda())
+        after_setup = plans()
+        z = torch.randn(B, 4, L, L, generator=g)
+        e, b = torch.rand(B, 4, 1, 1, generator=g), torch.randn(B, 4, 1, 1, generator=g) * 0.3
+        tg = torch.tensor([1, 3, 0, 4])
+        first = [t.cpu() for t in eng.transform_guidance(z, tg, e, b, 5, 2)]
+        direct = [t.cpu() for t in eng.direct_guidance(z, tg, 7)]
+        plain = [t.cpu() for t in eng.denoise_step(z, 8)]
+        after_runs = plans()
+        second = [t.cpu() for t in eng.transform_guidance(z, tg, e, b, 5, 2)]
+    finally:
+        eng.close()
+
+    # 3. read-only
+    for later in (after_setup, after_runs):
+        assert all(torch.equal(a, b_) for a, b_ in zip(at_finalize, later))
+    # 4. finite, and the same bits twice
+    assert all(torch.isfinite(t).all() for t in first + direct + plain)
+    assert all(torch.equal(a, b_) for a, b_ in zip(first, second))
+
+    # 1. consistency.  A record carries no producer list, so the GroupNorm side is checked on the producer every graph here has right in
+    # front of the norm: the convolution nearest before a merging GroupNorm writes its input and must emit.
+    seen = set()
+    for plan in at_finalize[:2]:
+        rec = plan.tolist()
+        assert all(r[3] == 0 for r in rec)
+        for i, (kind, stats, spans, _) in enumerate(rec):
+            prev_conv = next((rec[j] for j in range(i - 1, -1, -1) if rec[j][0] == CONV), None)
+            if kind == CONV:
+                assert stats in (-1, 0, 1) and spans >= -1 and not (stats == 1 and spans > 0)     # one statistics epilogue per launch
+                seen.add(("conv stats", stats))
+            elif kind == GN:
+                assert spans == -1
+                if stats == 1:
+                    assert prev_conv is not None and prev_conv[1] == 1, (i, prev_conv)
+                seen.add(("gn", stats))
+            elif kind == LN:
+                assert stats == -1
+                if spans > 0:
+                    assert rec[i - 1][0] == CONV and rec[i - 1][2] == spans, (i, rec[i - 1])
+                    seen.add("ln reads row partials")
+                elif spans == 0:
+                    assert not (rec[i - 1][0] == CONV and rec[i - 1][2] > 0), (i, rec[i - 1])         # nothing is emitted for nobody
+                    seen.add("ln folded, own pass")
+            else:
+                assert stats == -1 and spans == -1
+    # 2. not vacuous
+    assert ("conv stats", 1) in seen and ("conv stats", 0) in seen and ("gn", 1) in seen, seen
+    assert ("gn", 0) in seen or ("gn", -1) in seen, seen
+    assert "ln reads row partials" in seen and "ln folded, own pass" in seen, seen
+    print("fusion plan: %s" % sorted(map(str, seen)))
