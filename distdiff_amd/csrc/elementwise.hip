@@ -384,6 +384,47 @@ __global__ __launch_bounds__(STEP_THREADS) void sampler_step_kernel(const float*
   }
 }
 
+// ---- DPM-Solver++(2M) step (Lu et al. 2022; diffusers DPMSolverMultistepScheduler: dpmsolver++, order 2, midpoint) ----
+// z' = [the step above: B_z z + B_m m^] + c (x0 - x0_prev), x0 = A_z z + A_m m^, c formed in double on the host (sampler_step_coef_2m)
+// and passed by value.  Same thread map and loads as sampler_step_kernel; x0 is always written and may alias x0_prev (each thread reads
+// its own element before it writes it).  EPS: (epsilon, no rescale) forms x0 and the first-order part as cfg_ddim_kernel does, so x0 --
+// what direct guidance differentiates -- has the bits of the first-order step for every prediction type.
+template <bool EPS>
+__global__ __launch_bounds__(STEP_THREADS) void sampler_step_2m_kernel(const float* m2, int ld, const float* z, const float* x0_prev,
+                                                                       float* z_prev, float* x0, int B, int C, int HW,
+                                                                       const float* coef, const float* lin, const float* stats,
+                                                                       float c2m) {
+  const int b = blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
+  if (pix >= HW) return;
+  const float s = coef[0];
+  float Az = 0.f, Am = 0.f, Bz = 0.f, Bm = 0.f, sa = 1.f, s1m = 0.f, sap = 0.f, s1mp = 0.f;
+  if (EPS) { sa = coef[1]; s1m = coef[2]; sap = coef[3]; s1mp = coef[4]; }
+  else { Az = lin[0]; Am = lin[1]; Bz = lin[2]; Bm = lin[3]; }
+  const float k = stats ? stats[b * 8] : 1.f;
+  float u[8], c[8];
+  load_row8(m2 + ((size_t)b * HW + pix) * ld, C, u);
+  load_row8(m2 + ((size_t)(B + b) * HW + pix) * ld, C, c);
+#pragma unroll
+  for (int ch = 0; ch < 8; ++ch) {
+    if (ch < C) {
+      const size_t zi = ((size_t)b * C + ch) * HW + pix;
+      const float zz = z[zi], xp = x0_prev[zi];
+      float x, zp;
+      if (EPS) {
+        const float eps = u[ch] + s * (c[ch] - u[ch]);
+        x = (zz - s1m * eps) / sa;
+        zp = sap * x + s1mp * eps;
+      } else {
+        const float m = k * (u[ch] + s * (c[ch] - u[ch]));
+        x = Az * zz + Am * m;
+        zp = Bz * zz + Bm * m;
+      }
+      x0[zi] = x;
+      z_prev[zi] = zp + c2m * (x - xp);
+    }
+  }
+}
+
 // CFG rescale statistics, stage 1: per (image, 256-pixel block) the count, mean and centred second moment of c and of m over the C real
 // columns.  part[(b * nblk + blk) * 8] = {n, mean_c, M2_c, mean_m, M2_m}.  Fixed reduction order: bitwise deterministic.
 __global__ __launch_bounds__(STEP_THREADS) void cfg_stats_part_kernel(const float* m2, int ld, int B, int C, int HW, const float* coef,
@@ -869,6 +910,43 @@ hipError_t launch_sampler_step(const float* m2, int ld, const float* z, float* z
   }
   hipLaunchKernelGGL(sampler_step_kernel, grid, dim3(STEP_THREADS), 0, s, m2, ld, z, z_prev, x0, B, C, HW, coef_dev, lin_dev,
                      phi != 0.f ? (const float*)stats : (const float*)nullptr);
+  return hipGetLastError();
+}
+// c_i of the second-order step i of an n-step schedule, from alphas_cumprod at step i - 1, at step i and at its previous timestep.
+// With lambda(a) = ln(a / (1 - a)) / 2, h = lambda(a') - lambda(a) and r = (lambda(a) - lambda(a_before)) / h:
+//   c = sqrt(a') (1 - e^-h) / (2 r)
+// Exactly 0 -- the step is then the first-order one -- for the first and the last step of the schedule and wherever a lambda is not
+// finite (a = 0 of a zero-terminal-SNR table, a' = 1) or c itself is not: never NaN or inf.
+float sampler_step_coef_2m(int i, int n, double a_before, double a, double ap) {
+  if (i <= 0 || i >= n - 1) return 0.f;
+  const double l0 = 0.5 * log(a_before / (1 - a_before)), l1 = 0.5 * log(a / (1 - a)), l2 = 0.5 * log(ap / (1 - ap));
+  if (!std::isfinite(l0) || !std::isfinite(l1) || !std::isfinite(l2)) return 0.f;
+  const double h = l2 - l1, r = (l1 - l0) / h;
+  const double c = sqrt(ap) * -expm1(-h) / (2 * r);
+  return std::isfinite(c) && std::isfinite((float)c) ? (float)c : 0.f;
+}
+
+// x0_prev == nullptr or c2m == 0: the first-order step, launch_sampler_step unchanged (x0_prev is then not read)
+hipError_t launch_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c2m, float* z_prev, float* x0,
+                                  int B, int C, int HW, const float* coef_dev, const float* lin_dev, int prediction_type, float phi,
+                                  float* stats, float* part, hipStream_t s) {
+  if (!x0_prev || c2m == 0.f)
+    return launch_sampler_step(m2, ld, z, z_prev, x0, B, C, HW, coef_dev, lin_dev, prediction_type, phi, stats, part, s);
+  const bool eps = prediction_type == 0 && phi == 0.f;
+  if (!step_shape_ok(ld, B, C, HW) || prediction_type < 0 || prediction_type > 2 || (!eps && !lin_dev) || !x0 || !std::isfinite(c2m) ||
+      (phi != 0.f && (!stats || !part)))
+    return hipErrorInvalidValue;
+  const dim3 grid((HW + STEP_THREADS - 1) / STEP_THREADS, B);
+  if (phi != 0.f) {
+    hipLaunchKernelGGL(cfg_stats_part_kernel, grid, dim3(STEP_THREADS), 0, s, m2, ld, B, C, HW, coef_dev, part);
+    hipLaunchKernelGGL(cfg_stats_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const float*)part, (int)grid.x, B, phi, stats);
+  }
+  if (eps)
+    hipLaunchKernelGGL(sampler_step_2m_kernel<true>, grid, dim3(STEP_THREADS), 0, s, m2, ld, z, x0_prev, z_prev, x0, B, C, HW, coef_dev,
+                       lin_dev, (const float*)nullptr, c2m);
+  else
+    hipLaunchKernelGGL(sampler_step_2m_kernel<false>, grid, dim3(STEP_THREADS), 0, s, m2, ld, z, x0_prev, z_prev, x0, B, C, HW, coef_dev,
+                       lin_dev, phi != 0.f ? (const float*)stats : (const float*)nullptr, c2m);
   return hipGetLastError();
 }
 hipError_t launch_sampler_step_bwd(const float* g_x0, const float* g_zprev, bf16_t* g_m2, int ld, float* g_z, int B, int C, int HW,

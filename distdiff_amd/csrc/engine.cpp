@@ -123,6 +123,16 @@ void sampler_step(dd_engine* E, int k, const float* z, int step_index, float* z_
                              c.latent_size * c.latent_size, E->coef_table + (size_t)step_index * 8, E->step_table + (size_t)step_index * 4,
                              E->sp.prediction_type, E->sp.guidance_rescale, E->inst[k].rs_stats, E->rs_part, s));
 }
+// the same under DPM-Solver++(2M) with x0_prev = x0 of step_index - 1: no history, or c = 0 at this step, IS sampler_step
+void sampler_step_2m(dd_engine* E, int k, const float* z, int step_index, const float* x0_prev, float* z_prev, float* x0, hipStream_t s) {
+  const dd_config& c = E->cfg;
+  const Tn& out = E->unet.t[E->unet_out];
+  const float c2m = x0_prev ? E->c2m[step_index] : 0.f;
+  HIPCHK(launch_sampler_step_2m((const float*)(E->inst[k].unet + out.off), out.ld, z, x0_prev, c2m, z_prev, x0 || c2m == 0.f ? x0 : E->inst[k].x0,
+                                c.max_batch, c.unet_out_channels, c.latent_size * c.latent_size, E->coef_table + (size_t)step_index * 8,
+                                E->step_table + (size_t)step_index * 4, E->sp.prediction_type, E->sp.guidance_rescale,
+                                E->inst[k].rs_stats, E->rs_part, s));
+}
 void sampler_step_bwd(dd_engine* E, int k, const Ctx& uc, int step_index, const float* g_x0, const float* g_znext, float* g_z, hipStream_t s) {
   const dd_config& c = E->cfg;
   const Tn& out = E->unet.t[E->unet_out];
@@ -132,13 +142,15 @@ void sampler_step_bwd(dd_engine* E, int k, const Ctx& uc, int step_index, const 
                                  (const float*)(E->inst[k].unet + out.off), E->inst[k].rs_stats, E->rs_part, s));
 }
 
-// one guided forward step on instance k: z_in -> (z_next, x0, feat) ; energy accumulates into score, writes gfeat
+// one guided forward step on instance k: z_in -> (z_next, x0, feat) ; energy accumulates into score, writes gfeat.  x0_prev: the
+// history of a DPM-Solver++(2M) step (direct guidance); it changes z_next alone, which the reverse pass does not differentiate there
 void guided_forward(dd_engine* E, int k, const float* z_in, int step_index, const int* targets, int normalize, float weight,
-                    float* score, hipStream_t s) {
+                    float* score, hipStream_t s, const float* x0_prev = nullptr) {
   const dd_config& c = E->cfg;
   auto& I = E->inst[k];
   unet_fwd(E, k, z_in, step_index, s);
-  sampler_step(E, k, z_in, step_index, I.z_next, I.x0, s);
+  if (x0_prev) sampler_step_2m(E, k, z_in, step_index, x0_prev, I.z_next, I.x0, s);
+  else sampler_step(E, k, z_in, step_index, I.z_next, I.x0, s);
   vae_fwd(E, k, I.x0, s);
   guide_fwd_from_image(E, k, s);
   HIPCHK(launch_energy(I.feat, E->Pc, E->Pg, targets, c.max_batch, E->pD, E->pK, E->sp.gs, E->sp.ls, E->sp.use_global, E->sp.use_local,
@@ -363,18 +375,25 @@ int dd_finalize_weights(dd_engine* E) {
 
 int dd_set_schedule(dd_engine* E, const int* timesteps, int n, const float* alphas_cumprod, int num_train, float final_alpha,
                     const dd_sampler_params* sp) {
+  return dd_set_schedule_s(E, timesteps, n, alphas_cumprod, num_train, final_alpha, sp, 0);
+}
+
+int dd_set_schedule_s(dd_engine* E, const int* timesteps, int n, const float* alphas_cumprod, int num_train, float final_alpha,
+                      const dd_sampler_params* sp, int solver) {
   if (!E || !timesteps || n < 1 || !alphas_cumprod || !sp) return DD_ERR_ARG;
   if (!E->finalized) { E->err = "finalize first"; return DD_ERR_STATE; }
   DD_TRY(E, {
     const dd_config& c = E->cfg;
     if (sp->prediction_type < 0 || sp->prediction_type > 2) throw std::runtime_error("prediction_type must be 0 (epsilon), 1 (v_prediction) or 2 (sample)");
     if (!(sp->guidance_rescale >= 0.f && sp->guidance_rescale <= 1.f)) throw std::runtime_error("guidance_rescale must be in [0, 1]");
-    std::vector<float> coef((size_t)n * 8, 0.f), lin((size_t)n * 4, 0.f);
+    if (solver < 0 || solver > 1) throw std::runtime_error("solver must be 0 (DDIM) or 1 (DPM-Solver++(2M))");
+    std::vector<float> coef((size_t)n * 8, 0.f), lin((size_t)n * 4, 0.f), c2m;
     const int ratio = num_train / n;
     for (int i = 0; i < n; ++i) {
       const int t = timesteps[i], prev = t - ratio;
       if (t < 0 || t >= num_train) throw std::runtime_error("timestep out of range");
       const double a = alphas_cumprod[t], ap = prev >= 0 ? alphas_cumprod[prev] : final_alpha;
+      if (solver == 1) c2m.push_back(sampler_step_coef_2m(i, n, i > 0 ? alphas_cumprod[timesteps[i - 1]] : 0.0, a, ap));
       float* q = &coef[(size_t)i * 8];
       q[0] = sp->guidance_scale; q[1] = (float)sqrt(a); q[2] = (float)sqrt(1 - a); q[3] = (float)sqrt(ap); q[4] = (float)sqrt(1 - ap);
       if (sampler_step_coefs(sp->prediction_type, a, ap, &lin[(size_t)i * 4]))      // the cfg_ddim kernels divide by sqrt(a) as well
@@ -384,9 +403,17 @@ int dd_set_schedule(dd_engine* E, const int* timesteps, int n, const float* alph
     // every refusal is above: from here on the engine's schedule is replaced
     E->timesteps.assign(timesteps, timesteps + n);
     E->sp = *sp;
+    E->solver = solver;
     HIPCHK(hipDeviceSynchronize());
     for (void* q : E->sched_allocs) E->dfree(q);
     E->sched_allocs.clear();
+    E->c2m = c2m;
+    E->x0_hist = nullptr;
+    if (solver == 1) {
+      E->x0_hist = (float*)E->dmalloc((size_t)c.max_batch * std::max({c.unet_in_channels, c.unet_out_channels, c.vae_latent_channels}) *
+                                      c.latent_size * c.latent_size * 4);
+      E->sched_allocs.push_back(E->x0_hist);
+    }
     E->step_table = (float*)E->dmalloc(lin.size() * 4, false);
     E->sched_allocs.push_back(E->step_table);
     HIPCHK(hipMemcpy(E->step_table, lin.data(), lin.size() * 4, hipMemcpyHostToDevice));
@@ -522,18 +549,26 @@ int dd_unet_forward(dd_engine* E, const float* z, int step_index, float* eps2_ou
   });
 }
 
-// the launch sequence of one plain step: UNet forward (no stash) + CFG + DDIM
-static void denoise_step_enqueue(dd_engine* E, const float* z, int step_index, float* z_prev_out, float* x0_out, hipStream_t s) {
+// the launch sequence of one plain step: UNet forward (no stash) + CFG + scheduler step (x0_prev: the history of a DPM-Solver++(2M) step)
+static void denoise_step_enqueue(dd_engine* E, const float* z, int step_index, const float* x0_prev, float* z_prev_out, float* x0_out,
+                                 hipStream_t s) {
   unet_fwd(E, 0, z, step_index, s, /*stash=*/false);
-  sampler_step(E, 0, z, step_index, z_prev_out, x0_out, s);
+  if (x0_prev) sampler_step_2m(E, 0, z, step_index, x0_prev, z_prev_out, x0_out, s);
+  else sampler_step(E, 0, z, step_index, z_prev_out, x0_out, s);
 }
 
 int dd_denoise_step(dd_engine* E, const float* z, int step_index, float* z_prev_out, float* x0_out, int B, void* stream) {
+  return dd_denoise_step_h(E, z, step_index, nullptr, z_prev_out, x0_out, B, stream);
+}
+
+int dd_denoise_step_h(dd_engine* E, const float* z, int step_index, const float* x0_prev, float* z_prev_out, float* x0_out, int B,
+                      void* stream) {
   if (!E || !z || !z_prev_out) return DD_ERR_ARG;
+  if (x0_prev && E->solver != 1) { E->err = "x0_prev is the history of DPM-Solver++(2M): this schedule was set with solver 0 (DDIM)"; return DD_ERR_STATE; }
   DD_TRY(E, {
     check_batch(E, B);
     if (step_index < 0 || step_index >= (int)E->timesteps.size()) throw std::runtime_error("step_index out of range");
-    denoise_step_enqueue(E, z, step_index, z_prev_out, x0_out, (hipStream_t)stream);
+    denoise_step_enqueue(E, z, step_index, x0_prev, z_prev_out, x0_out, (hipStream_t)stream);
   });
 }
 
@@ -665,7 +700,13 @@ int dd_transform_guidance(dd_engine* E, const float* z, const int* targets, cons
 
 int dd_direct_guidance(dd_engine* E, const float* z, const int* targets, int step_index, float* z_next_out, float* x0_out,
                        float* score_out, float* grad_z_out, int B, void* stream) {
+  return dd_direct_guidance_h(E, z, targets, step_index, nullptr, z_next_out, x0_out, score_out, grad_z_out, B, stream);
+}
+
+int dd_direct_guidance_h(dd_engine* E, const float* z, const int* targets, int step_index, const float* x0_prev, float* z_next_out,
+                         float* x0_out, float* score_out, float* grad_z_out, int B, void* stream) {
   if (!E || !z || !targets || !z_next_out) return DD_ERR_ARG;
+  if (x0_prev && E->solver != 1) { E->err = "x0_prev is the history of DPM-Solver++(2M): this schedule was set with solver 0 (DDIM)"; return DD_ERR_STATE; }
   DD_TRY(E, {
     check_batch(E, B);
     const dd_config& c = E->cfg;
@@ -678,7 +719,7 @@ int dd_direct_guidance(dd_engine* E, const float* z, const int* targets, int ste
     HIPCHK(hipMemsetAsync(score, 0, sizeof(float), s));
     HIPCHK(hipMemsetAsync(E->image_scores, 0, (size_t)B * sizeof(float), s));
     HIPCHK(hipMemcpyAsync(E->inst[0].z_in, z, n * 4, hipMemcpyDeviceToDevice, s));
-    guided_forward(E, 0, E->inst[0].z_in, step_index, targets, 1, 1.f, score, s);
+    guided_forward(E, 0, E->inst[0].z_in, step_index, targets, 1, 1.f, score, s, x0_prev);
     float* g_z = E->f32_tmp[0];
     guided_backward(E, 0, step_index, nullptr, g_z, E->f32_tmp[2], s);
     if (grad_z_out) HIPCHK(hipMemcpyAsync(grad_z_out, g_z, n * 4, hipMemcpyDeviceToDevice, s));
@@ -755,19 +796,26 @@ int dd_expand(dd_engine* E, const dd_expand_args* a, void* stream) {
   if (rc) return rc;
   float* cur = E->f32_tmp[3];
   float* nxt = E->f32_tmp[4];
+  // DPM-Solver++(2M): every step leaves its x0 in the one history buffer (read and written in place); `hist` is that buffer once it
+  // holds x0 of step i - 1 on the trajectory `cur` is on.  Under DDIM both stay null and the calls are those of version 8.
+  float* const keep = E->solver == 1 ? E->x0_hist : nullptr;
+  const float* hist = nullptr;
   for (int i = a->start_index; i < n; ++i) {
+    const float* h = i == n - 1 ? nullptr : hist;          // the final step is first-order
     if (a->guidance_type == 1 && a->guide_count > 0 && i == a->guide_first) {
-      // transform guidance at t == guide_timesteps[0], then the step is executed again from the corrected latent (:1203-1207)
+      // transform guidance at t == guide_timesteps[0], then the step is executed again from the corrected latent (:1203-1207): the
+      // correction moved the latent off the trajectory the history belongs to, so that step runs without one
       rc = dd_transform_guidance(E, cur, a->targets, ch_e, ch_b, a->guide_first, a->guide_count, nxt, a->score_out, nullptr, a->B, stream);
       if (rc) return rc;
       std::swap(cur, nxt);
-      rc = dd_denoise_step(E, cur, i, nxt, nullptr, a->B, stream);
+      rc = dd_denoise_step_h(E, cur, i, nullptr, nxt, keep, a->B, stream);
     } else if (a->guidance_type == 2 && i >= a->guide_first && i < a->guide_first + a->guide_count) {
-      rc = dd_direct_guidance(E, cur, a->targets, i, nxt, nullptr, a->score_out, nullptr, a->B, stream);
+      rc = dd_direct_guidance_h(E, cur, a->targets, i, h, nxt, keep, a->score_out, nullptr, a->B, stream);
     } else {
-      rc = dd_denoise_step(E, cur, i, nxt, nullptr, a->B, stream);
+      rc = dd_denoise_step_h(E, cur, i, h, nxt, keep, a->B, stream);
     }
     if (rc) return rc;
+    hist = keep;
     std::swap(cur, nxt);
   }
   try {

@@ -271,8 +271,11 @@ struct dd_engine {
   std::vector<int> timesteps;
   float* coef_table = nullptr;   // [n][8]: guidance_scale, sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev), -, -, -
   float* step_table = nullptr;   // [n][4]: A_z, A_m, B_z, B_m of the linear step form (v_prediction / sample models, CFG rescale)
+  std::vector<float> c2m;        // DPM-Solver++(2M) only: c_i of every step (host; the kernel takes it by value), empty under DDIM
+  float* x0_hist = nullptr;      // DPM-Solver++(2M) only: dd_expand's history, x0 of the previous step [B,C,L,L] (in sched_allocs)
   float* rs_part = nullptr;      // CFG rescale: block partials of the per-image reductions (scratch, consumed by the next kernel)
   dd_sampler_params sp{};
+  int solver = 0;                // dd_set_schedule_s: 0 DDIM, 1 DPM-Solver++(2M)
   // prototypes
   float* Pc = nullptr; float* Pg = nullptr; int pC = 0, pK = 0, pD = 0;
 

@@ -210,6 +210,14 @@ hipError_t launch_sampler_step(const float* m2, int ld, const float* z, float* z
 hipError_t launch_sampler_step_bwd(const float* g_x0, const float* g_zprev, bf16_t* g_m2, int ld, float* g_z, int B, int C, int HW,
                                    const float* coef_dev, const float* lin_dev, int prediction_type, float phi, const float* m2,
                                    const float* stats, float* part, hipStream_t s);
+// DPM-Solver++(2M): z' = [the step above] + c (x0 - x0_prev), forward only (the guidance calls differentiate x0, which does not depend
+// on the history).  c = sampler_step_coef_2m(i, n, a at step i - 1, a at step i, a at its previous timestep), host, double; exactly 0
+// for the first and the last step and wherever it is undefined.  x0_prev == nullptr or c == 0 IS launch_sampler_step; otherwise x0
+// is always written (required) and may alias x0_prev.
+float sampler_step_coef_2m(int i, int n, double a_before, double a, double a_prev);
+hipError_t launch_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c2m, float* z_prev, float* x0,
+                                  int B, int C, int HW, const float* coef_dev, const float* lin_dev, int prediction_type, float phi,
+                                  float* stats, float* part, hipStream_t s);
 // backward of cat[z, z] + NCHW->NHWC: g_z[b,c,pix] (+)= gin[b*HW+pix, c] + gin[(B+b)*HW+pix, c]   (halves = 2), or of the plain
 // layout change when the UNet input itself is not duplicated (halves = 1: the two CFG halves share their prefix, engine.cpp)
 hipError_t launch_dup_bwd(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, hipStream_t s);

@@ -105,6 +105,15 @@ int dd_op_sampler_step_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_
   return (int)launch_sampler_step_bwd(g_x0, g_zprev, g_m2, ld, g_z, B, C, HW, coef, lin, prediction_type, guidance_rescale, m2, stats, part,
                                       S(st));
 }
+float dd_op_step_coef_2m(int step_index, int n_steps, double a_before, double a, double a_prev) {
+  return sampler_step_coef_2m(step_index, n_steps, a_before, a, a_prev);
+}
+int dd_op_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c2m, float* z_prev, float* x0, int B, int C,
+                          int HW, const float* coef, const float* lin, int prediction_type, float guidance_rescale, float* stats,
+                          float* part, void* st) {
+  return (int)launch_sampler_step_2m(m2, ld, z, x0_prev, c2m, z_prev, x0, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part,
+                                     S(st));
+}
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int acc, void* st) {
   return (int)launch_sumpool2x2(src, src_ld, dst, dst_ld, B, H, W, C, acc, S(st));
 }

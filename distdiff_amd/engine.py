@@ -45,6 +45,7 @@ class DDSamplerParams(C.Structure):
 
 
 PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1, "sample": 2}       # dd_sampler_params.prediction_type
+SOLVERS = {"ddim": 0, "dpmsolver++": 1}                                  # the solver argument of dd_set_schedule_s; dpmsolver++ = DPM-Solver++(2M)
 
 
 class DDExpandArgs(C.Structure):
@@ -70,11 +71,14 @@ def _declare(l):
     l.dd_export_packed.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     l.dd_import_packed.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     l.dd_set_schedule.argtypes = [vp, vp, i, vp, i, f, C.POINTER(DDSamplerParams)]
+    l.dd_set_schedule_s.argtypes = [vp, vp, i, vp, i, f, C.POINTER(DDSamplerParams), i]
     l.dd_set_prototypes.argtypes = [vp, vp, vp, i, i, i]
     l.dd_set_prompt.argtypes = [vp, vp, i, vp]
     l.dd_add_noise.argtypes = [vp, vp, vp, vp, i, i, vp]
     l.dd_set_added_cond.argtypes = [vp, vp, vp, i, vp]
     l.dd_denoise_step.argtypes = [vp, vp, i, vp, vp, i, vp]
+    l.dd_denoise_step_h.argtypes = [vp, vp, i, vp, vp, vp, i, vp]
+    l.dd_direct_guidance_h.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, i, vp]
     l.dd_transform_guidance.argtypes = [vp, vp, vp, vp, vp, i, i, vp, vp, vp, i, vp]
     l.dd_direct_guidance.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, i, vp]
     l.dd_decode.argtypes = [vp, vp, vp, i, i, vp]
@@ -265,17 +269,21 @@ class Engine:
     # ---- setup -------------------------------------------------------------------------------
     def set_schedule(self, timesteps, alphas_cumprod, final_alpha_cumprod, guidance_scale=7.5, gs=1.0, ls=1.0, rho=10.0,
                      constraint_value=0.2, use_global=True, use_local=True, guidance_period=2, prediction_type="epsilon",
-                     guidance_rescale=0.0):
+                     guidance_rescale=0.0, solver="ddim"):
         """prediction_type: what the UNet predicts, 'epsilon' | 'v_prediction' | 'sample' (scheduler_config.json); guidance_rescale: the
-        CFG rescale factor phi in [0, 1] (diffusers rescale_noise_cfg).  The defaults are the SD-1.x sampler."""
+        CFG rescale factor phi in [0, 1] (diffusers rescale_noise_cfg); solver: 'ddim' | 'dpmsolver++' (DPM-Solver++(2M) on the same
+        timestep list: `expand` keeps its history itself, the step-level calls take it as `x0_prev`).  The defaults are the SD-1.x
+        sampler."""
         if prediction_type not in PREDICTION_TYPES:
             raise NotImplementedError("prediction_type=%r (built: %s)" % (prediction_type, ", ".join(PREDICTION_TYPES)))
+        if solver not in SOLVERS:
+            raise NotImplementedError("solver=%r (built: %s)" % (solver, ", ".join(SOLVERS)))
         ts = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int32))
         ac = np.ascontiguousarray(np.asarray(alphas_cumprod, dtype=np.float32))
         sp = DDSamplerParams(guidance_scale, gs, ls, rho, constraint_value, int(use_global), int(use_local), int(guidance_period),
                              PREDICTION_TYPES[prediction_type], float(guidance_rescale))
-        self._chk(self.L.dd_set_schedule(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
-                                         float(final_alpha_cumprod), C.byref(sp)), "dd_set_schedule")
+        self._chk(self.L.dd_set_schedule_s(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
+                                           float(final_alpha_cumprod), C.byref(sp), SOLVERS[solver]), "dd_set_schedule")
         self.n_steps = len(ts)
         self.timesteps = [int(t) for t in ts]
 
@@ -371,10 +379,13 @@ class Engine:
         self._chk(self.L.dd_unet_forward(self._h, _p(z), step_index, _p(out), z.shape[0], _stream()), "dd_unet_forward")
         return out
 
-    def denoise_step(self, z, step_index):
+    def denoise_step(self, z, step_index, x0_prev=None):
+        """-> (z', x0).  x0_prev: under solver 'dpmsolver++' the x0 this call returned for step_index - 1 on the same trajectory (the
+        second-order step); None is the first-order step."""
         z = self._f(z)
+        h = self._f(x0_prev) if x0_prev is not None else None
         zp, x0 = torch.empty_like(z), torch.empty_like(z)
-        self._chk(self.L.dd_denoise_step(self._h, _p(z), step_index, _p(zp), _p(x0), z.shape[0], _stream()), "dd_denoise_step")
+        self._chk(self.L.dd_denoise_step_h(self._h, _p(z), step_index, _p(h), _p(zp), _p(x0), z.shape[0], _stream()), "dd_denoise_step")
         return zp, x0
 
     def transform_guidance(self, z, targets, e, b, first_step_index, P):
@@ -387,13 +398,15 @@ class Engine:
                                                _p(gz0), z.shape[0], _stream()), "dd_transform_guidance")
         return out, score, gz0
 
-    def direct_guidance(self, z, targets, step_index):
+    def direct_guidance(self, z, targets, step_index, x0_prev=None):
+        """-> (z_next, x0, score, g_z).  x0_prev: as in `denoise_step`; it changes z_next alone (the gradient flows through x0)."""
         z = self._f(z)
+        h = self._f(x0_prev) if x0_prev is not None else None
         tg = targets.to(self.device, torch.int32).contiguous()
         zn, x0, gz = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
         score = torch.zeros(1, device=self.device)
-        self._chk(self.L.dd_direct_guidance(self._h, _p(z), _p(tg), step_index, _p(zn), _p(x0), _p(score), _p(gz), z.shape[0],
-                                            _stream()), "dd_direct_guidance")
+        self._chk(self.L.dd_direct_guidance_h(self._h, _p(z), _p(tg), step_index, _p(h), _p(zn), _p(x0), _p(score), _p(gz), z.shape[0],
+                                              _stream()), "dd_direct_guidance")
         return zn, x0, score, gz
 
     def decode(self, z, denormalize=True):

@@ -2,7 +2,11 @@
 
 A maintainer of the reference can swap these in for the three functions: `unet` / `vae` / `image_encoder` /
 `noise_scheduler` are replaced by one `Engine` (passed as `unet`); the other model arguments are accepted and ignored.
-Random draws follow the reference: e ~ U[0,1) and b ~ N(0,1) from the CPU global generator (:692-695)."""
+Random draws follow the reference: e ~ U[0,1) and b ~ N(0,1) from the CPU global generator (:692-695).
+
+The shims are stateless, as the reference's functions are: each call is one first-order step, also on an engine whose schedule was
+set with solver="dpmsolver++".  The second-order step needs the previous step's x0, which these signatures have no place for: pass
+it to `Engine.denoise_step` / `Engine.direct_guidance` as `x0_prev`, or let `Engine.expand` keep it."""
 import torch
 
 

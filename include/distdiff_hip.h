@@ -14,7 +14,8 @@
  *   dd_set_prompt          prompt_embeds = cat[negative, prompt]                generate_data.py:1147-1148, 1184
  *   dd_add_noise           noise_scheduler.add_noise                            generate_data.py:1176
  *   dd_denoise_step        denoise_one_step (noise_scheduler.step for epsilon /   generate_data.py:109-121
- *                          v_prediction / sample models: dd_sampler_params)
+ *                          v_prediction / sample models: dd_sampler_params;
+ *                          dd_denoise_step_h: the DPM-Solver++(2M) step with its history)
  *   dd_transform_guidance  transform_guidance (+ linfball_proj)                 generate_data.py:687-732, 124-137
  *   dd_direct_guidance     direct_guidance                                      generate_data.py:735-767
  *   dd_decode              vae.decode + image_processor.postprocess             generate_data.py:1221-1228
@@ -47,11 +48,12 @@ enum dd_status { DD_OK = 0, DD_ERR_ARG = -1, DD_ERR_HIP = -2, DD_ERR_STATE = -3,
 /* Layout version of the structs and argument lists of this header and distdiff_hip_ops.h.  A caller sets dd_config.abi_version =
  * DD_ABI_VERSION (after zero-initialising the struct: every struct of this ABI must be zero-initialised, new fields are appended and
  * mean "off" at 0); dd_create refuses another value with DD_ERR_ARG, and dd_abi_version() tells what the loaded library was built
- * as.  8: dd_sampler_params gained prediction_type / guidance_rescale (0 = the sampler of version 7), the dd_op_sampler_step* entry
- * points are new; 7: dd_expand_args gained seed / unit_ids / noise_mode / offset_noise / text_to_img (all 0 = the call of version 6), dd_randn_units
+ * as.  9: dd_set_schedule_s (the schedule with a solver: 0 = DDIM, the sampler of version 8; 1 = DPM-Solver++(2M)), dd_denoise_step_h /
+ * dd_direct_guidance_h / dd_op_step_coef_2m / dd_op_sampler_step_2m are new, no struct changed; 8: dd_sampler_params gained prediction_type /
+ * guidance_rescale (0 = the sampler of version 7), the dd_op_sampler_step* entry points are new; 7: dd_expand_args gained seed / unit_ids / noise_mode / offset_noise / text_to_img (all 0 = the call of version 6), dd_randn_units
  * is new; 6: dd_config gained unet_attn_fp8 + abi_version, AttnParams gained no_shortk; 5 (unversioned): workspace_bytes in the dd_op_attention_gemm_* lists,
  * ConvGemmParams.wgroup_rows / wgroup_elems, AttnParams.pv_fp8. */
-#define DD_ABI_VERSION 8
+#define DD_ABI_VERSION 9
 
 typedef struct dd_config {
   /* UNet2DConditionModel (unet/config.json) */
@@ -176,6 +178,19 @@ int dd_import_packed(dd_engine* e, const void* src, size_t offset, size_t bytes,
 /* timesteps: host int32[n] (descending, e.g. 981..1); alphas_cumprod: host float[num_train]; */
 int dd_set_schedule(dd_engine* e, const int* timesteps, int n, const float* alphas_cumprod, int num_train_timesteps,
                     float final_alpha_cumprod, const dd_sampler_params* sp);
+/* dd_set_schedule with a solver (version 9); solver 0 = DDIM IS dd_set_schedule.  1 = DPM-Solver++(2M) (Lu et al. 2022; diffusers
+ * DPMSolverMultistepScheduler with algorithm_type dpmsolver++, solver_order 2, solver_type midpoint, lower_order_final; beyond the
+ * reference, which always builds a DDIMScheduler), on the same timestep list and the same previous-timestep rule.  With
+ * lambda(a) = ln(a / (1 - a)) / 2, h_i = lambda(a'_i) - lambda(a_i), r_i = (lambda(a_i) - lambda(a_{i-1})) / h_i and x0_i as in
+ * dd_sampler_params:
+ *   z' = [the DDIM step, eta = 0] + c_i (x0_i - x0_{i-1}),   c_i = sqrt(a'_i) (1 - e^-h_i) / (2 r_i)
+ * c_i is exactly 0 -- the step is then the DDIM step, run by the same kernels -- without a history (the caller passes none: the first
+ * executed step, the step executed again after transform guidance), for i = 0 and i = n - 1, and wherever a lambda is not finite
+ * (a = 0 of a zero-terminal-SNR table, a' = 1).  The history is explicit: the x0_prev argument of dd_denoise_step_h /
+ * dd_direct_guidance_h; dd_expand keeps it itself.  dd_transform_guidance's chained steps are a look-ahead and stay first-order.
+ * Any other solver is refused.  The solver travels as an argument and not in dd_sampler_params, whose layout stays version 8's. */
+int dd_set_schedule_s(dd_engine* e, const int* timesteps, int n, const float* alphas_cumprod, int num_train_timesteps,
+                      float final_alpha_cumprod, const dd_sampler_params* sp, int solver);
 /* Pc [C,D], Pg [C,K,D] HOST fp32, already L2-normalised by the caller as the reference does */
 int dd_set_prototypes(dd_engine* e, const float* Pc, const float* Pg, int C, int K, int D);
 /* embeds: DEVICE fp32 [2B, text_len, cross_dim], negative half first */
@@ -193,7 +208,18 @@ int dd_transform_guidance(dd_engine* e, const float* z, const int* targets, cons
                           void* stream);
 int dd_direct_guidance(dd_engine* e, const float* z, const int* targets, int step_index, float* z_next_out, float* x0_out,
                        float* score_out, float* grad_z_out, int B, void* stream);
+/* The two calls above with an explicit history (solver 1): x0_prev DEVICE [B,4,L,L] = x0 of step_index - 1 on the same trajectory.
+ * x0_prev == NULL makes them dd_denoise_step / dd_direct_guidance; a non-NULL x0_prev under solver 0 returns DD_ERR_STATE.  x0_out may
+ * be x0_prev itself (a single history buffer, updated in place).  In direct guidance z_next = the second-order step - rho g with g as
+ * in dd_direct_guidance: the gradient flows through x0 alone, which does not depend on the history. */
+int dd_denoise_step_h(dd_engine* e, const float* z, int step_index, const float* x0_prev, float* z_prev_out, float* x0_out, int B,
+                      void* stream);
+int dd_direct_guidance_h(dd_engine* e, const float* z, const int* targets, int step_index, const float* x0_prev, float* z_next_out,
+                         float* x0_out, float* score_out, float* grad_z_out, int B, void* stream);
 int dd_decode(dd_engine* e, const float* z, float* image_out, int denormalize, int B, void* stream);
+/* Under solver 1 the loop keeps the history itself, in one buffer of the engine, for every input mode: plain and direct-guidance steps
+ * read it and leave their x0 in it; the first executed step, the step executed again after transform guidance and the last step run
+ * without one (first-order). */
 int dd_expand(dd_engine* e, const dd_expand_args* a, void* stream);
 /* The counter-based generator of dd_expand's noise_mode 1 on its own: out DEVICE fp32 [B, n_per_unit].  Philox4x32-10 (Salmon et al.,
  * Random123), key = (seed lo, seed hi), counter = (j / 4, rng_stream, unit id lo, unit id hi) for element j of a unit: one 128-bit

@@ -13,6 +13,7 @@
  *   dd_op_attention_*    scaled-dot-product attention (self, cross, VAE mid block) (:112, :701)
  *   dd_op_cfg_ddim*      classifier-free guidance + DDIMScheduler.step (:116-119)
  *   dd_op_sampler_step*  the same for v_prediction / sample models and with CFG rescale
+ *   dd_op_sampler_step_2m  the step of DPM-Solver++(2M) (beyond the reference, which builds a DDIMScheduler)
  *   dd_op_bicubic*       F.interpolate(..., (224,224), 'bicubic') (:704, :745)
  *   dd_op_conv_f32       timm conv+BN(+ReLU) of image_encoder.encode_image and its input-gradient in exact fp32
  *                        (model_utils.py:29-41; generate_data.py:705, :721, :746, :761): v_mfma_f32_32x32x2_f32
@@ -114,6 +115,16 @@ int dd_op_sampler_step(const float* m2, int ld, const float* z, float* z_prev, f
 int dd_op_sampler_step_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_m2, int ld, float* g_z, int B, int C, int HW,
                            const float* coef_dev, const float* lin_dev, int prediction_type, float guidance_rescale, const float* m2,
                            const float* stats, float* part, void* stream);
+/* DPM-Solver++(2M) (dd_set_schedule_s, solver 1), forward only: z' = [z' of dd_op_sampler_step] + c (x0 - x0_prev), x0 as there.
+ * c = dd_op_step_coef_2m(i, n, a_before, a, a_prev) (host, double arithmetic, rounded once) from alphas_cumprod at step i - 1, at step
+ * i and at step i's previous timestep: with lambda(a) = ln(a / (1 - a)) / 2, h = lambda(a_prev) - lambda(a), r = (lambda(a) -
+ * lambda(a_before)) / h, c = sqrt(a_prev) (1 - e^-h) / (2 r).  Exactly 0.0f for i = 0, i = n - 1 and wherever a lambda or c is not
+ * finite.  x0_prev NULL or c == 0 IS dd_op_sampler_step, bit for bit (x0_prev is not read); otherwise x0 is required, is always
+ * written and may be x0_prev itself.  The other arguments are those of dd_op_sampler_step. */
+float dd_op_step_coef_2m(int step_index, int n_steps, double a_before, double a, double a_prev);
+int dd_op_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c, float* z_prev, float* x0, int B, int C,
+                          int HW, const float* coef_dev, const float* lin_dev, int prediction_type, float guidance_rescale, float* stats,
+                          float* part, void* stream);
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int accumulate,
                      void* stream);
 int dd_op_geglu_bwd(const uint16_t* raw, int ld_raw, const uint16_t* dout, int ld_dout, uint16_t* draw, int ld_draw, int M,
