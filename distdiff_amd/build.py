@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 # DD_BUILD_OBJ / DD_BUILD_LIB: a variant build beside the product one (A/B of compile-time switches: DD_EXTRA_CFLAGS=-D... ; run with DD_LIB=)
 OBJ = os.environ.get("DD_BUILD_OBJ") or os.path.join(HERE, "csrc", "_obj")
 LIB = os.environ.get("DD_BUILD_LIB") or os.path.join(HERE, "libdistdiff_hip.so")
-SOURCES = ["conv_gemm.hip", "conv_gemm2.hip", "conv_halo.hip", "gemm_pps.hip", "gemm_ws.hip", "norm.hip", "attention.hip", "attention_shortk.hip", "attention_gemm.hip", "elementwise.hip", "rng.hip", "guide_f32.hip", "weights.cpp", "ops_abi.cpp",
+SOURCES = ["conv_gemm.hip", "conv_gemm2.hip", "conv_halo.hip", "gemm_pps.hip", "gemm_ws.hip", "norm.hip", "attention.hip", "attention_shortk.hip", "attention_gemm.hip", "elementwise.hip", "sampler_step.hip", "rng.hip", "guide_f32.hip", "weights.cpp", "ops_abi.cpp",
            "engine_weights.cpp", "engine_graph.cpp", "engine_exec.cpp", "engine.cpp"]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs. With the default heuristic the attention kernels put them in AccVGPRs
 # and paid 144 v_accvgpr_read/write per KV tile to run the softmax on them (found in the ISA; attention family 475 -> see DESIGN.md)

@@ -1,5 +1,5 @@
 // K6/K7/K9/K10/K12 — the HBM-bound side kernels of the guided DDIM loop (gfx950):
-// layout conversion, CFG + DDIM update and its VJP (generate_data.py:116-119), add_noise (:1176),
+// layout conversion, add_noise (generate_data.py:1176),
 // affine perturbation / SGD / L-inf projection of transform_guidance (:696, :721-728, :124-137),
 // direct-guidance update (:762), nearest-2x transpose (2x2 sum pool), GEGLU backward,
 // max-pool, bicubic 224 resize (A=-0.75, align_corners=False) and its transpose, GAP,
@@ -42,47 +42,6 @@ __global__ void nhwc_to_nchw_kernel(const void* src, int src_f32, float* dst, in
     v = v * scale + shift;
     if (clamp) v = fminf(fmaxf(v, lo), hi);
     dst[i] = v;
-  }
-}
-
-__global__ void cfg_ddim_kernel(const float* eps2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW,
-                                const float* coef) {
-  const float s = coef[0], sa = coef[1], s1m = coef[2], sap = coef[3], s1mp = coef[4];
-  const size_t total = (size_t)B * C * HW;
-  GRID_STRIDE(i, total) {
-    const int pix = (int)(i % HW);
-    const int c = (int)((i / HW) % C);
-    const int b = (int)(i / ((size_t)HW * C));
-    const float eu = eps2[((size_t)b * HW + pix) * ld + c];
-    const float ec = eps2[((size_t)(B + b) * HW + pix) * ld + c];
-    const float eps = eu + s * (ec - eu);
-    const float x = (z[i] - s1m * eps) / sa;
-    if (x0) x0[i] = x;
-    z_prev[i] = sap * x + s1mp * eps;
-  }
-}
-
-__global__ void cfg_ddim_bwd_kernel(const float* g_x0, const float* g_zprev, bf16_t* g_eps2, int ld, float* g_z, int B, int C,
-                                    int HW, int Cpad, const float* coef) {
-  const float s = coef[0], sa = coef[1], s1m = coef[2], sap = coef[3], s1mp = coef[4];
-  const size_t total = (size_t)B * HW * Cpad;
-  GRID_STRIDE(i, total) {
-    const int c = (int)(i % Cpad);
-    const size_t row = i / Cpad;
-    const int pix = (int)(row % HW);
-    const int b = (int)(row / HW);
-    float gu = 0.f, gc = 0.f;
-    if (c < C) {
-      const size_t zi = ((size_t)b * C + c) * HW + pix;
-      const float gx = g_x0 ? g_x0[zi] : 0.f;
-      const float gp = g_zprev ? g_zprev[zi] : 0.f;
-      const float h = gx + sap * gp;
-      const float ge = -s1m / sa * h + s1mp * gp;
-      g_z[zi] = h / sa;
-      gu = (1.f - s) * ge; gc = s * ge;
-    }
-    g_eps2[((size_t)b * HW + pix) * ld + c] = f2bf(gu);
-    g_eps2[((size_t)(B + b) * HW + pix) * ld + c] = f2bf(gc);
   }
 }
 
@@ -348,211 +307,6 @@ __device__ float block_sum(float v, float* red) {
   float t = 0.f;
   for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
   return t;
-}
-
-// ---- sampler step for every prediction type, with optional CFG rescale (diffusers DDIMScheduler.step, eta = 0; rescale_noise_cfg) ----
-// x0 = A_z z + A_m m^, z' = B_z z + B_m m^ with m = u + s (c - u) and m^ = k_b m (k_b = 1 without rescale); lin = {A_z, A_m, B_z, B_m}
-// formed in double on the host (sampler_step_coefs).  One thread per pixel: both CFG halves of the 8-wide fp32 NHWC row come in as
-// 16-byte loads, the NCHW reads and writes are coalesced along the pixels.  grid = (ceil(HW / 256), B).
-#define STEP_THREADS 256
-__device__ __forceinline__ void load_row8(const float* p, int C, float* v) {
-  const float4 a = *(const float4*)p;
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = v[5] = v[6] = v[7] = 0.f;
-  if (C > 4) { const float4 b = *(const float4*)(p + 4); v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w; }
-}
-
-__global__ __launch_bounds__(STEP_THREADS) void sampler_step_kernel(const float* m2, int ld, const float* z, float* z_prev, float* x0,
-                                                                    int B, int C, int HW, const float* coef, const float* lin,
-                                                                    const float* stats) {
-  const int b = blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
-  if (pix >= HW) return;
-  const float s = coef[0], Az = lin[0], Am = lin[1], Bz = lin[2], Bm = lin[3];
-  const float k = stats ? stats[b * 8] : 1.f;
-  float u[8], c[8];
-  load_row8(m2 + ((size_t)b * HW + pix) * ld, C, u);
-  load_row8(m2 + ((size_t)(B + b) * HW + pix) * ld, C, c);
-#pragma unroll
-  for (int ch = 0; ch < 8; ++ch) {
-    if (ch < C) {
-      const size_t zi = ((size_t)b * C + ch) * HW + pix;
-      const float m = k * (u[ch] + s * (c[ch] - u[ch]));
-      const float zz = z[zi];
-      if (x0) x0[zi] = Az * zz + Am * m;
-      z_prev[zi] = Bz * zz + Bm * m;
-    }
-  }
-}
-
-// ---- DPM-Solver++(2M) step (Lu et al. 2022; diffusers DPMSolverMultistepScheduler: dpmsolver++, order 2, midpoint) ----
-// z' = [the step above: B_z z + B_m m^] + c (x0 - x0_prev), x0 = A_z z + A_m m^, c formed in double on the host (sampler_step_coef_2m)
-// and passed by value.  Same thread map and loads as sampler_step_kernel; x0 is always written and may alias x0_prev (each thread reads
-// its own element before it writes it).  EPS: (epsilon, no rescale) forms x0 and the first-order part as cfg_ddim_kernel does, so x0 --
-// what direct guidance differentiates -- has the bits of the first-order step for every prediction type.
-template <bool EPS>
-__global__ __launch_bounds__(STEP_THREADS) void sampler_step_2m_kernel(const float* m2, int ld, const float* z, const float* x0_prev,
-                                                                       float* z_prev, float* x0, int B, int C, int HW,
-                                                                       const float* coef, const float* lin, const float* stats,
-                                                                       float c2m) {
-  const int b = blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
-  if (pix >= HW) return;
-  const float s = coef[0];
-  float Az = 0.f, Am = 0.f, Bz = 0.f, Bm = 0.f, sa = 1.f, s1m = 0.f, sap = 0.f, s1mp = 0.f;
-  if (EPS) { sa = coef[1]; s1m = coef[2]; sap = coef[3]; s1mp = coef[4]; }
-  else { Az = lin[0]; Am = lin[1]; Bz = lin[2]; Bm = lin[3]; }
-  const float k = stats ? stats[b * 8] : 1.f;
-  float u[8], c[8];
-  load_row8(m2 + ((size_t)b * HW + pix) * ld, C, u);
-  load_row8(m2 + ((size_t)(B + b) * HW + pix) * ld, C, c);
-#pragma unroll
-  for (int ch = 0; ch < 8; ++ch) {
-    if (ch < C) {
-      const size_t zi = ((size_t)b * C + ch) * HW + pix;
-      const float zz = z[zi], xp = x0_prev[zi];
-      float x, zp;
-      if (EPS) {
-        const float eps = u[ch] + s * (c[ch] - u[ch]);
-        x = (zz - s1m * eps) / sa;
-        zp = sap * x + s1mp * eps;
-      } else {
-        const float m = k * (u[ch] + s * (c[ch] - u[ch]));
-        x = Az * zz + Am * m;
-        zp = Bz * zz + Bm * m;
-      }
-      x0[zi] = x;
-      z_prev[zi] = zp + c2m * (x - xp);
-    }
-  }
-}
-
-// CFG rescale statistics, stage 1: per (image, 256-pixel block) the count, mean and centred second moment of c and of m over the C real
-// columns.  part[(b * nblk + blk) * 8] = {n, mean_c, M2_c, mean_m, M2_m}.  Fixed reduction order: bitwise deterministic.
-__global__ __launch_bounds__(STEP_THREADS) void cfg_stats_part_kernel(const float* m2, int ld, int B, int C, int HW, const float* coef,
-                                                                      float* part) {
-  __shared__ float red[8];
-  const int b = blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
-  const bool valid = pix < HW;
-  const float s = coef[0];
-  float c[8], m[8];
-  float sc = 0.f, sm = 0.f;
-  if (valid) {
-    float u[8];
-    load_row8(m2 + ((size_t)b * HW + pix) * ld, C, u);
-    load_row8(m2 + ((size_t)(B + b) * HW + pix) * ld, C, c);
-#pragma unroll
-    for (int ch = 0; ch < 8; ++ch)
-      if (ch < C) { m[ch] = u[ch] + s * (c[ch] - u[ch]); sc += c[ch]; sm += m[ch]; }
-  }
-  const float n = (float)(min(STEP_THREADS, HW - (int)blockIdx.x * STEP_THREADS) * C);
-  const float mean_c = block_sum(sc, red) / n, mean_m = block_sum(sm, red) / n;
-  float qc = 0.f, qm = 0.f;
-  if (valid) {
-#pragma unroll
-    for (int ch = 0; ch < 8; ++ch)
-      if (ch < C) { const float dc = c[ch] - mean_c, dm = m[ch] - mean_m; qc += dc * dc; qm += dm * dm; }
-  }
-  const float M2c = block_sum(qc, red), M2m = block_sum(qm, red);
-  if (threadIdx.x == 0) {
-    float* o = part + ((size_t)b * gridDim.x + blockIdx.x) * 8;
-    o[0] = n; o[1] = mean_c; o[2] = M2c; o[3] = mean_m; o[4] = M2m;
-  }
-}
-
-// stage 2: one thread per image merges the block partials in block order (counts, means, M2: Chan et al., as gn_finalize_chan_kernel
-// does) and writes stats[b * 8] = {k, sigma_c, sigma_m, mean_c, mean_m, N, phi}: sigma unbiased (N - 1), k = phi sigma_c / sigma_m + 1 - phi
-__global__ void cfg_stats_final_kernel(const float* part, int nblk, int B, float phi, float* stats) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  double n = 0, mc = 0, Mc = 0, mm = 0, Mm = 0;
-  for (int i = 0; i < nblk; ++i) {
-    const float* p = part + ((size_t)b * nblk + i) * 8;
-    const double nb = p[0], t = n + nb, dc = (double)p[1] - mc, dm = (double)p[3] - mm;
-    Mc += (double)p[2] + dc * dc * n * nb / t; mc += dc * nb / t;
-    Mm += (double)p[4] + dm * dm * n * nb / t; mm += dm * nb / t;
-    n = t;
-  }
-  const double sig_c = sqrt(Mc / (n - 1)), sig_m = sqrt(Mm / (n - 1));
-  float* o = stats + (size_t)b * 8;
-  o[0] = (float)((double)phi * sig_c / sig_m + 1.0 - (double)phi);
-  o[1] = (float)sig_c; o[2] = (float)sig_m; o[3] = (float)mc; o[4] = (float)mm; o[5] = (float)n; o[6] = phi; o[7] = 0.f;
-}
-
-// backward, rescale only: per-block partial of sum(g^ m) with g^ = A_m g_x0 + B_m g_z' the gradient on m^
-__global__ __launch_bounds__(STEP_THREADS) void sampler_step_bwd_dot_kernel(const float* g_x0, const float* g_zprev, const float* m2, int ld,
-                                                                            int B, int C, int HW, const float* coef, const float* lin,
-                                                                            float* dpart) {
-  __shared__ float red[8];
-  const int b = blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
-  const float s = coef[0], Am = lin[1], Bm = lin[3];
-  float acc = 0.f;
-  if (pix < HW) {
-    float u[8], c[8];
-    load_row8(m2 + ((size_t)b * HW + pix) * ld, C, u);
-    load_row8(m2 + ((size_t)(B + b) * HW + pix) * ld, C, c);
-#pragma unroll
-    for (int ch = 0; ch < 8; ++ch)
-      if (ch < C) {
-        const size_t zi = ((size_t)b * C + ch) * HW + pix;
-        const float gh = Am * (g_x0 ? g_x0[zi] : 0.f) + Bm * (g_zprev ? g_zprev[zi] : 0.f);
-        acc += gh * (u[ch] + s * (c[ch] - u[ch]));
-      }
-  }
-  acc = block_sum(acc, red);
-  if (threadIdx.x == 0) dpart[(size_t)b * gridDim.x + blockIdx.x] = acc;
-}
-
-// VJP of sampler_step_kernel: g_z = A_z g_x0 + B_z g_z' (NCHW fp32), g_m2 bf16 NHWC rows (all ld columns written, padding = 0) with
-// g_m split (1 - s, s) onto the CFG halves.  With rescale (stats != null; m2 = the UNet output of that step, dpart from the kernel above):
-//   g_m = k g^ - phi sigma_c / sigma_m^2 . S (m - mean_m) / ((N - 1) sigma_m),  g_c += phi / sigma_m . S (c - mean_c) / ((N - 1) sigma_c)
-__global__ __launch_bounds__(STEP_THREADS) void sampler_step_bwd_kernel(const float* g_x0, const float* g_zprev, bf16_t* g_m2, int ld,
-                                                                        float* g_z, int B, int C, int HW, const float* coef,
-                                                                        const float* lin, const float* m2, const float* stats,
-                                                                        const float* dpart) {
-  __shared__ float S_sh;
-  const int b = blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
-  float k = 1.f, tm = 0.f, tc = 0.f, mean_c = 0.f, mean_m = 0.f;
-  if (stats) {
-    if (threadIdx.x == 0) {
-      double S = 0;
-      for (int i = 0; i < (int)gridDim.x; ++i) S += (double)dpart[(size_t)b * gridDim.x + i];     // block order: deterministic
-      S_sh = (float)S;
-    }
-    __syncthreads();
-    const float* st = stats + (size_t)b * 8;
-    const float sig_c = st[1], sig_m = st[2], N1 = st[5] - 1.f, phi = st[6];
-    k = st[0]; mean_c = st[3]; mean_m = st[4];
-    tm = phi * sig_c / (sig_m * sig_m) * S_sh / (N1 * sig_m);
-    tc = phi / sig_m * S_sh / (N1 * sig_c);
-  }
-  if (pix >= HW) return;
-  const float s = coef[0], Az = lin[0], Am = lin[1], Bz = lin[2], Bm = lin[3];
-  float u[8], c[8];
-  if (stats) {
-    load_row8(m2 + ((size_t)b * HW + pix) * ld, C, u);
-    load_row8(m2 + ((size_t)(B + b) * HW + pix) * ld, C, c);
-  }
-  float gu[8], gc[8];
-#pragma unroll
-  for (int ch = 0; ch < 8; ++ch) {
-    gu[ch] = 0.f; gc[ch] = 0.f;
-    if (ch < C) {
-      const size_t zi = ((size_t)b * C + ch) * HW + pix;
-      const float gx = g_x0 ? g_x0[zi] : 0.f, gp = g_zprev ? g_zprev[zi] : 0.f;
-      g_z[zi] = Az * gx + Bz * gp;
-      float gm = Am * gx + Bm * gp, extra = 0.f;
-      if (stats) {
-        const float m = u[ch] + s * (c[ch] - u[ch]);
-        gm = k * gm - tm * (m - mean_m);
-        extra = tc * (c[ch] - mean_c);
-      }
-      gu[ch] = (1.f - s) * gm; gc[ch] = s * gm + extra;
-    }
-  }
-  bf16_t* ru = g_m2 + ((size_t)b * HW + pix) * ld;
-  bf16_t* rc = g_m2 + ((size_t)(B + b) * HW + pix) * ld;
-  *(uint4*)ru = pack8(gu); *(uint4*)rc = pack8(gc);
-  const uint4 zero = make_uint4(0, 0, 0, 0);
-  for (int c0 = 8; c0 < ld; c0 += 8) { *(uint4*)(ru + c0) = zero; *(uint4*)(rc + c0) = zero; }
 }
 
 // single block: loops over the batch so that the score accumulation order is fixed (deterministic)
@@ -865,102 +619,6 @@ hipError_t launch_nchw_f32_to_nhwc_bf16(const float* src, bf16_t* dst, int B, in
 hipError_t launch_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int B, int C, int H, int W, int ld, float scale,
                                    float shift, int clamp, float lo, float hi, hipStream_t s) {
   LAUNCH(nhwc_to_nchw_kernel, (size_t)B * C * H * W, src, src_f32, dst, B, C, H * W, ld, scale, shift, clamp, lo, hi);
-}
-hipError_t launch_cfg_ddim(const float* eps2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW,
-                           const float* coef_dev, hipStream_t s) {
-  LAUNCH(cfg_ddim_kernel, (size_t)B * C * HW, eps2, ld, z, z_prev, x0, B, C, HW, coef_dev);
-}
-hipError_t launch_cfg_ddim_bwd(const float* g_x0, const float* g_zprev, bf16_t* g_eps2, int ld, float* g_z, int B, int C, int HW,
-                               const float* coef_dev, hipStream_t s) {
-  LAUNCH(cfg_ddim_bwd_kernel, (size_t)B * HW * ld, g_x0, g_zprev, g_eps2, ld, g_z, B, C, HW, ld, coef_dev);
-}
-// the four step coefficients in double (B_m = sqrt(1-a') sqrt(a) - sqrt(a') sqrt(1-a) cancels here and not in fp32); the v-prediction
-// form never divides by sqrt(a): a zero-terminal-SNR table has a = 0 exactly at its first trailing step
-int sampler_step_coefs(int prediction_type, double a, double ap, float* out4) {
-  const double sa = sqrt(a), sb = sqrt(1 - a), sap = sqrt(ap), sbp = sqrt(1 - ap);
-  double Az, Am, Bz, Bm;
-  if (prediction_type == 0) {
-    if (!(a > 0)) return -1;
-    Az = 1 / sa; Am = -sb / sa; Bz = sap / sa; Bm = sbp - sap * sb / sa;
-  } else if (prediction_type == 1) {
-    Az = sa; Am = -sb; Bz = sap * sa + sbp * sb; Bm = sbp * sa - sap * sb;
-  } else if (prediction_type == 2) {
-    if (!(a < 1)) return -1;
-    Az = 0; Am = 1; Bz = sbp / sb; Bm = sap - sbp * sa / sb;
-  } else {
-    return -1;
-  }
-  out4[0] = (float)Az; out4[1] = (float)Am; out4[2] = (float)Bz; out4[3] = (float)Bm;
-  return 0;
-}
-size_t sampler_step_scratch_floats(int B, int HW) { return (size_t)B * ((HW + STEP_THREADS - 1) / STEP_THREADS) * 8; }
-
-static bool step_shape_ok(int ld, int B, int C, int HW) { return B >= 1 && B <= 65535 && C >= 1 && C <= 8 && HW >= 1 && ld >= 8 && !(ld & 7); }
-
-hipError_t launch_sampler_step(const float* m2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW,
-                               const float* coef_dev, const float* lin_dev, int prediction_type, float phi, float* stats, float* part,
-                               hipStream_t s) {
-  if (prediction_type == 0 && phi == 0.f) return launch_cfg_ddim(m2, ld, z, z_prev, x0, B, C, HW, coef_dev, s);
-  if (!step_shape_ok(ld, B, C, HW) || prediction_type < 0 || prediction_type > 2 || !lin_dev || (phi != 0.f && (!stats || !part)))
-    return hipErrorInvalidValue;
-  const dim3 grid((HW + STEP_THREADS - 1) / STEP_THREADS, B);
-  if (phi != 0.f) {
-    hipLaunchKernelGGL(cfg_stats_part_kernel, grid, dim3(STEP_THREADS), 0, s, m2, ld, B, C, HW, coef_dev, part);
-    hipLaunchKernelGGL(cfg_stats_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const float*)part, (int)grid.x, B, phi, stats);
-  }
-  hipLaunchKernelGGL(sampler_step_kernel, grid, dim3(STEP_THREADS), 0, s, m2, ld, z, z_prev, x0, B, C, HW, coef_dev, lin_dev,
-                     phi != 0.f ? (const float*)stats : (const float*)nullptr);
-  return hipGetLastError();
-}
-// c_i of the second-order step i of an n-step schedule, from alphas_cumprod at step i - 1, at step i and at its previous timestep.
-// With lambda(a) = ln(a / (1 - a)) / 2, h = lambda(a') - lambda(a) and r = (lambda(a) - lambda(a_before)) / h:
-//   c = sqrt(a') (1 - e^-h) / (2 r)
-// Exactly 0 -- the step is then the first-order one -- for the first and the last step of the schedule and wherever a lambda is not
-// finite (a = 0 of a zero-terminal-SNR table, a' = 1) or c itself is not: never NaN or inf.
-float sampler_step_coef_2m(int i, int n, double a_before, double a, double ap) {
-  if (i <= 0 || i >= n - 1) return 0.f;
-  const double l0 = 0.5 * log(a_before / (1 - a_before)), l1 = 0.5 * log(a / (1 - a)), l2 = 0.5 * log(ap / (1 - ap));
-  if (!std::isfinite(l0) || !std::isfinite(l1) || !std::isfinite(l2)) return 0.f;
-  const double h = l2 - l1, r = (l1 - l0) / h;
-  const double c = sqrt(ap) * -expm1(-h) / (2 * r);
-  return std::isfinite(c) && std::isfinite((float)c) ? (float)c : 0.f;
-}
-
-// x0_prev == nullptr or c2m == 0: the first-order step, launch_sampler_step unchanged (x0_prev is then not read)
-hipError_t launch_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c2m, float* z_prev, float* x0,
-                                  int B, int C, int HW, const float* coef_dev, const float* lin_dev, int prediction_type, float phi,
-                                  float* stats, float* part, hipStream_t s) {
-  if (!x0_prev || c2m == 0.f)
-    return launch_sampler_step(m2, ld, z, z_prev, x0, B, C, HW, coef_dev, lin_dev, prediction_type, phi, stats, part, s);
-  const bool eps = prediction_type == 0 && phi == 0.f;
-  if (!step_shape_ok(ld, B, C, HW) || prediction_type < 0 || prediction_type > 2 || (!eps && !lin_dev) || !x0 || !std::isfinite(c2m) ||
-      (phi != 0.f && (!stats || !part)))
-    return hipErrorInvalidValue;
-  const dim3 grid((HW + STEP_THREADS - 1) / STEP_THREADS, B);
-  if (phi != 0.f) {
-    hipLaunchKernelGGL(cfg_stats_part_kernel, grid, dim3(STEP_THREADS), 0, s, m2, ld, B, C, HW, coef_dev, part);
-    hipLaunchKernelGGL(cfg_stats_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const float*)part, (int)grid.x, B, phi, stats);
-  }
-  if (eps)
-    hipLaunchKernelGGL(sampler_step_2m_kernel<true>, grid, dim3(STEP_THREADS), 0, s, m2, ld, z, x0_prev, z_prev, x0, B, C, HW, coef_dev,
-                       lin_dev, (const float*)nullptr, c2m);
-  else
-    hipLaunchKernelGGL(sampler_step_2m_kernel<false>, grid, dim3(STEP_THREADS), 0, s, m2, ld, z, x0_prev, z_prev, x0, B, C, HW, coef_dev,
-                       lin_dev, phi != 0.f ? (const float*)stats : (const float*)nullptr, c2m);
-  return hipGetLastError();
-}
-hipError_t launch_sampler_step_bwd(const float* g_x0, const float* g_zprev, bf16_t* g_m2, int ld, float* g_z, int B, int C, int HW,
-                                   const float* coef_dev, const float* lin_dev, int prediction_type, float phi, const float* m2,
-                                   const float* stats, float* part, hipStream_t s) {
-  if (prediction_type == 0 && phi == 0.f) return launch_cfg_ddim_bwd(g_x0, g_zprev, g_m2, ld, g_z, B, C, HW, coef_dev, s);
-  if (!step_shape_ok(ld, B, C, HW) || prediction_type < 0 || prediction_type > 2 || !lin_dev || (phi != 0.f && (!stats || !part || !m2)))
-    return hipErrorInvalidValue;
-  const dim3 grid((HW + STEP_THREADS - 1) / STEP_THREADS, B);
-  if (phi != 0.f)
-    hipLaunchKernelGGL(sampler_step_bwd_dot_kernel, grid, dim3(STEP_THREADS), 0, s, g_x0, g_zprev, m2, ld, B, C, HW, coef_dev, lin_dev, part);
-  hipLaunchKernelGGL(sampler_step_bwd_kernel, grid, dim3(STEP_THREADS), 0, s, g_x0, g_zprev, g_m2, ld, g_z, B, C, HW, coef_dev, lin_dev,
-                     m2, phi != 0.f ? stats : (const float*)nullptr, (const float*)part);
-  return hipGetLastError();
 }
 hipError_t launch_dup_bwd(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, hipStream_t s) {
   LAUNCH(dup_bwd_kernel, (size_t)B * C * HW, gin, ld, g_z, B, C, HW, accumulate, halves);

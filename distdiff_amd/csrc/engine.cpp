@@ -114,32 +114,35 @@ void guide_vae_bwd(dd_engine* E, int k, float* g_x0, hipStream_t s) {
                                  1.f / c.vae_scaling_factor, 0.f, 0, 0.f, 0.f, s));
 }
 
-// CFG + scheduler step on the UNet output of instance k, and its VJP: today's cfg_ddim pair for (epsilon, no rescale), the linear-form
-// kernels for every other (prediction_type, guidance_rescale) -- the choice is made inside the launchers
-void sampler_step(dd_engine* E, int k, const float* z, int step_index, float* z_prev, float* x0, hipStream_t s) {
+// The sampler step on the UNet output of instance k (kernels.h: StepParams lists its modes), and its VJP
+StepParams step_params(dd_engine* E, int k, int step_index) {
   const dd_config& c = E->cfg;
   const Tn& out = E->unet.t[E->unet_out];
-  HIPCHK(launch_sampler_step((const float*)(E->inst[k].unet + out.off), out.ld, z, z_prev, x0, c.max_batch, c.unet_out_channels,
-                             c.latent_size * c.latent_size, E->coef_table + (size_t)step_index * 8, E->step_table + (size_t)step_index * 4,
-                             E->sp.prediction_type, E->sp.guidance_rescale, E->inst[k].rs_stats, E->rs_part, s));
+  StepParams p{};
+  p.m2 = (const float*)(E->inst[k].unet + out.off); p.ld = out.ld;
+  p.B = c.max_batch; p.C = c.unet_out_channels; p.HW = c.latent_size * c.latent_size;
+  p.coef = E->coef_table + (size_t)step_index * 8; p.lin = E->step_table + (size_t)step_index * 4;
+  p.prediction_type = E->sp.prediction_type; p.phi = E->sp.guidance_rescale;
+  p.stats = E->inst[k].rs_stats; p.part = E->rs_part;
+  return p;
 }
-// the same under DPM-Solver++(2M) with x0_prev = x0 of step_index - 1: no history, or c = 0 at this step, IS sampler_step
-void sampler_step_2m(dd_engine* E, int k, const float* z, int step_index, const float* x0_prev, float* z_prev, float* x0, hipStream_t s) {
-  const dd_config& c = E->cfg;
-  const Tn& out = E->unet.t[E->unet_out];
-  const float c2m = x0_prev ? E->c2m[step_index] : 0.f;
-  HIPCHK(launch_sampler_step_2m((const float*)(E->inst[k].unet + out.off), out.ld, z, x0_prev, c2m, z_prev, x0 || c2m == 0.f ? x0 : E->inst[k].x0,
-                                c.max_batch, c.unet_out_channels, c.latent_size * c.latent_size, E->coef_table + (size_t)step_index * 8,
-                                E->step_table + (size_t)step_index * 4, E->sp.prediction_type, E->sp.guidance_rescale,
-                                E->inst[k].rs_stats, E->rs_part, s));
+// x0_prev: x0 of step_index - 1 under DPM-Solver++(2M), or null; x0 may be null
+void sampler_step(dd_engine* E, int k, const float* z, int step_index, const float* x0_prev, float* z_prev, float* x0, hipStream_t s) {
+  StepParams p = step_params(E, k, step_index);
+  p.z = z; p.z_prev = z_prev; p.x0_prev = x0_prev;
+  p.c2m = x0_prev ? E->c2m[step_index] : 0.f;
+  // the second-order term needs x0 of this step: a caller that does not ask for it has it written to the instance's own buffer
+  const bool second_order = x0_prev && p.c2m != 0.f;
+  p.x0 = !x0 && second_order ? E->inst[k].x0 : x0;
+  HIPCHK(launch_sampler_step(p, s));
 }
 void sampler_step_bwd(dd_engine* E, int k, const Ctx& uc, int step_index, const float* g_x0, const float* g_znext, float* g_z, hipStream_t s) {
-  const dd_config& c = E->cfg;
-  const Tn& out = E->unet.t[E->unet_out];
-  HIPCHK(launch_sampler_step_bwd(g_x0, g_znext, grad_ptr(uc, out), out.ld, g_z, c.max_batch, c.unet_out_channels,
-                                 c.latent_size * c.latent_size, E->coef_table + (size_t)step_index * 8,
-                                 E->step_table + (size_t)step_index * 4, E->sp.prediction_type, E->sp.guidance_rescale,
-                                 (const float*)(E->inst[k].unet + out.off), E->inst[k].rs_stats, E->rs_part, s));
+  HIPCHK(launch_sampler_step_bwd(step_params(E, k, step_index), g_x0, g_znext, grad_ptr(uc, E->unet.t[E->unet_out]), g_z, s));
+}
+// a history is the input of DPM-Solver++(2M) alone: the step-level entry points refuse it under another solver
+bool history_refused(dd_engine* E, const float* x0_prev) {
+  if (x0_prev && E->solver != 1) E->err = "x0_prev is the history of DPM-Solver++(2M): this schedule was set with solver 0 (DDIM)";
+  return x0_prev && E->solver != 1;
 }
 
 // one guided forward step on instance k: z_in -> (z_next, x0, feat) ; energy accumulates into score, writes gfeat.  x0_prev: the
@@ -149,8 +152,7 @@ void guided_forward(dd_engine* E, int k, const float* z_in, int step_index, cons
   const dd_config& c = E->cfg;
   auto& I = E->inst[k];
   unet_fwd(E, k, z_in, step_index, s);
-  if (x0_prev) sampler_step_2m(E, k, z_in, step_index, x0_prev, I.z_next, I.x0, s);
-  else sampler_step(E, k, z_in, step_index, I.z_next, I.x0, s);
+  sampler_step(E, k, z_in, step_index, x0_prev, I.z_next, I.x0, s);
   vae_fwd(E, k, I.x0, s);
   guide_fwd_from_image(E, k, s);
   HIPCHK(launch_energy(I.feat, E->Pc, E->Pg, targets, c.max_batch, E->pD, E->pK, E->sp.gs, E->sp.ls, E->sp.use_global, E->sp.use_local,
@@ -275,6 +277,8 @@ int dd_finalize_weights(dd_engine* E) {
   E->shape_only = E->declared > 0;
   DD_TRY(E, {
     const dd_config& c = E->cfg;
+    // the sampler step reads the UNet output as one 8-wide fp32 row per pixel (kernels.h: StepParams)
+    if (c.unet_out_channels > 8) throw std::runtime_error("unet_out_channels " + std::to_string(c.unet_out_channels) + " > 8: the sampler step takes at most 8");
     build_unet(E);
     build_vae(E);
     if (c.guide_kind == 1) build_guide_vit(E);
@@ -396,7 +400,7 @@ int dd_set_schedule_s(dd_engine* E, const int* timesteps, int n, const float* al
       if (solver == 1) c2m.push_back(sampler_step_coef_2m(i, n, i > 0 ? alphas_cumprod[timesteps[i - 1]] : 0.0, a, ap));
       float* q = &coef[(size_t)i * 8];
       q[0] = sp->guidance_scale; q[1] = (float)sqrt(a); q[2] = (float)sqrt(1 - a); q[3] = (float)sqrt(ap); q[4] = (float)sqrt(1 - ap);
-      if (sampler_step_coefs(sp->prediction_type, a, ap, &lin[(size_t)i * 4]))      // the cfg_ddim kernels divide by sqrt(a) as well
+      if (sampler_step_coefs(sp->prediction_type, a, ap, &lin[(size_t)i * 4]))      // the division form of the step divides by sqrt(a) as well
         throw std::runtime_error(sp->prediction_type == 0 ? "epsilon-prediction with alphas_cumprod = 0 at timestep " + std::to_string(t) +
                                  " (zero terminal SNR): x0 is undefined there" : "sample-prediction with alphas_cumprod = 1 at timestep " + std::to_string(t));
     }
@@ -553,8 +557,7 @@ int dd_unet_forward(dd_engine* E, const float* z, int step_index, float* eps2_ou
 static void denoise_step_enqueue(dd_engine* E, const float* z, int step_index, const float* x0_prev, float* z_prev_out, float* x0_out,
                                  hipStream_t s) {
   unet_fwd(E, 0, z, step_index, s, /*stash=*/false);
-  if (x0_prev) sampler_step_2m(E, 0, z, step_index, x0_prev, z_prev_out, x0_out, s);
-  else sampler_step(E, 0, z, step_index, z_prev_out, x0_out, s);
+  sampler_step(E, 0, z, step_index, x0_prev, z_prev_out, x0_out, s);
 }
 
 int dd_denoise_step(dd_engine* E, const float* z, int step_index, float* z_prev_out, float* x0_out, int B, void* stream) {
@@ -564,7 +567,7 @@ int dd_denoise_step(dd_engine* E, const float* z, int step_index, float* z_prev_
 int dd_denoise_step_h(dd_engine* E, const float* z, int step_index, const float* x0_prev, float* z_prev_out, float* x0_out, int B,
                       void* stream) {
   if (!E || !z || !z_prev_out) return DD_ERR_ARG;
-  if (x0_prev && E->solver != 1) { E->err = "x0_prev is the history of DPM-Solver++(2M): this schedule was set with solver 0 (DDIM)"; return DD_ERR_STATE; }
+  if (history_refused(E, x0_prev)) return DD_ERR_STATE;
   DD_TRY(E, {
     check_batch(E, B);
     if (step_index < 0 || step_index >= (int)E->timesteps.size()) throw std::runtime_error("step_index out of range");
@@ -706,7 +709,7 @@ int dd_direct_guidance(dd_engine* E, const float* z, const int* targets, int ste
 int dd_direct_guidance_h(dd_engine* E, const float* z, const int* targets, int step_index, const float* x0_prev, float* z_next_out,
                          float* x0_out, float* score_out, float* grad_z_out, int B, void* stream) {
   if (!E || !z || !targets || !z_next_out) return DD_ERR_ARG;
-  if (x0_prev && E->solver != 1) { E->err = "x0_prev is the history of DPM-Solver++(2M): this schedule was set with solver 0 (DDIM)"; return DD_ERR_STATE; }
+  if (history_refused(E, x0_prev)) return DD_ERR_STATE;
   DD_TRY(E, {
     check_batch(E, B);
     const dd_config& c = E->cfg;

@@ -187,37 +187,38 @@ hipError_t launch_nchw_f32_to_nhwc_bf16(const float* src, bf16_t* dst, int B, in
 // NHWC (bf16 or fp32) [B*H*W, ld] -> NCHW fp32 [B,C,H,W];  out = in * scale + shift, optional clamp to [lo, hi]
 hipError_t launch_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int B, int C, int H, int W, int ld,
                                    float scale, float shift, int clamp, float lo, float hi, hipStream_t s);
-// CFG + DDIM step (generate_data.py:116-119): eps2 NHWC fp32 [2B*HW, ld] (uncond first), z NCHW fp32
-//   coef = {guidance_scale, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev}
-hipError_t launch_cfg_ddim(const float* eps2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW,
-                           const float* coef_dev, hipStream_t s);
-// backward of cfg_ddim wrt (z via direct path) and eps2: see DESIGN.md / SURVEY appendix A
-//   g_x0, g_zprev NCHW fp32 (either may be null) -> g_eps2 NHWC bf16 [2B*HW, ld] and g_z_direct NCHW fp32
-hipError_t launch_cfg_ddim_bwd(const float* g_x0, const float* g_zprev, bf16_t* g_eps2, int ld, float* g_z, int B, int C,
-                               int HW, const float* coef_dev, hipStream_t s);
-// The step for every prediction type (0 epsilon, 1 v_prediction, 2 sample) with optional CFG rescale phi (Lin et al. 2023; diffusers
-// rescale_noise_cfg): x0 = A_z z + A_m m^, z' = B_z z + B_m m^, m = u + s (c - u), m^ = m (phi sigma_c / sigma_m + 1 - phi) per image.
-//   coef_dev = the cfg_ddim row ([0] = guidance scale), lin_dev = {A_z, A_m, B_z, B_m} (sampler_step_coefs)
-//   (prediction_type 0, phi 0) IS launch_cfg_ddim / launch_cfg_ddim_bwd on coef_dev: lin_dev, stats and part are not read
-//   phi != 0: stats [B][8] receives {k, sigma_c, sigma_m, mean_c, mean_m, N, phi} (kept for the backward), part is scratch of
-//   sampler_step_scratch_floats(B, HW) floats.  The backward re-reads m2, the model output of that step, when phi != 0.
-//   ld: a multiple of 8; C <= 8.  No atomics: bitwise deterministic.
+// The sampler step (sampler_step.hip; generate_data.py:116-119 is its epsilon / DDIM mode): CFG mix, optional CFG rescale phi (Lin et al.
+// 2023; diffusers rescale_noise_cfg), the scheduler update, and its VJP.
+//   m = u + s (c - u),  m^ = m (phi sigma_c / sigma_m + 1 - phi) per image,  x0 = A_z z + A_m m^,  z' = B_z z + B_m m^ + c2m (x0 - x0_prev)
+// Modes, chosen by the launchers from the fields below and from nothing else:
+//   (prediction_type 0, phi 0)   the division form x0 = (z - sqrt(1-a) m) / sqrt a, z' = sqrt a' x0 + sqrt(1-a') m on coef; lin, stats and
+//                                part are not read
+//   every other (type, phi)      the linear form on lin
+//   phi != 0                     stats [B][8] receives {k, sigma_c, sigma_m, mean_c, mean_m, N, phi} (kept for the backward), part is
+//                                scratch of sampler_step_scratch_floats(B, HW) floats; the backward re-reads m2 of that step
+//   x0_prev != null and c2m != 0 DPM-Solver++(2M), forward only (the guidance calls differentiate x0, which does not depend on the
+//                                history): x0 is required and always written, and may alias x0_prev.  Otherwise x0_prev is not read
+// ld: a multiple of 8; C <= 8; B <= 65535; anything else is hipErrorInvalidValue in front of any launch.  No atomics: bitwise deterministic.
+struct StepParams {
+  const float* m2; int ld;             // model output, fp32 NHWC rows [2B*HW, ld], unconditional half first
+  const float* z;                      // NCHW fp32 [B, C, HW], as x0_prev, z_prev and x0
+  const float* x0_prev; float c2m;     // history and c of this step (sampler_step_coef_2m)
+  float* z_prev; float* x0;            // x0 may be null in a first-order step
+  int B, C, HW;
+  const float* coef;                   // device: {guidance_scale, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev}
+  const float* lin;                    // device: {A_z, A_m, B_z, B_m} (sampler_step_coefs)
+  int prediction_type; float phi;      // 0 epsilon, 1 v_prediction, 2 sample; CFG rescale
+  float* stats; float* part;
+};
 int sampler_step_coefs(int prediction_type, double a, double a_prev, float* out4);      // host; -1: unknown type or a singular step
 size_t sampler_step_scratch_floats(int B, int HW);
-hipError_t launch_sampler_step(const float* m2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW,
-                               const float* coef_dev, const float* lin_dev, int prediction_type, float phi, float* stats, float* part,
-                               hipStream_t s);
-hipError_t launch_sampler_step_bwd(const float* g_x0, const float* g_zprev, bf16_t* g_m2, int ld, float* g_z, int B, int C, int HW,
-                                   const float* coef_dev, const float* lin_dev, int prediction_type, float phi, const float* m2,
-                                   const float* stats, float* part, hipStream_t s);
-// DPM-Solver++(2M): z' = [the step above] + c (x0 - x0_prev), forward only (the guidance calls differentiate x0, which does not depend
-// on the history).  c = sampler_step_coef_2m(i, n, a at step i - 1, a at step i, a at its previous timestep), host, double; exactly 0
-// for the first and the last step and wherever it is undefined.  x0_prev == nullptr or c == 0 IS launch_sampler_step; otherwise x0
-// is always written (required) and may alias x0_prev.
+// c = sampler_step_coef_2m(i, n, a at step i - 1, a at step i, a at its previous timestep), host, double; exactly 0 for the first and
+// the last step and wherever it is undefined
 float sampler_step_coef_2m(int i, int n, double a_before, double a, double a_prev);
-hipError_t launch_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c2m, float* z_prev, float* x0,
-                                  int B, int C, int HW, const float* coef_dev, const float* lin_dev, int prediction_type, float phi,
-                                  float* stats, float* part, hipStream_t s);
+hipError_t launch_sampler_step(const StepParams& p, hipStream_t s);
+// VJP of step p in (x0, z'): g_x0, g_zprev NCHW fp32 (either may be null) -> g_z NCHW fp32 (the direct path) and g_m2, bf16 NHWC rows
+// [2B*HW, ld] with every column written (padding = 0).  p.z, p.x0_prev, p.z_prev and p.x0 are not used.  See DESIGN.md / SURVEY appendix A
+hipError_t launch_sampler_step_bwd(const StepParams& p, const float* g_x0, const float* g_zprev, bf16_t* g_m2, float* g_z, hipStream_t s);
 // backward of cat[z, z] + NCHW->NHWC: g_z[b,c,pix] (+)= gin[b*HW+pix, c] + gin[(B+b)*HW+pix, c]   (halves = 2), or of the plain
 // layout change when the UNet input itself is not duplicated (halves = 1: the two CFG halves share their prefix, engine.cpp)
 hipError_t launch_dup_bwd(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, hipStream_t s);

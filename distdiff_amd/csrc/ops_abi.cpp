@@ -82,13 +82,21 @@ int dd_op_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int B, int 
                            int clamp, float lo, float hi, void* st) {
   return (int)launch_nhwc_to_nchw_f32(src, src_f32, dst, B, C, H, W, ld, scale, shift, clamp, lo, hi, S(st));
 }
+// the sampler-step ops: each fills one StepParams (kernels.h lists the modes) for one of the two launchers
+static StepParams step_params(const float* m2, int ld, int B, int C, int HW, const float* coef, const float* lin, int prediction_type,
+                              float guidance_rescale, const float* stats, float* part) {
+  StepParams p{};
+  p.m2 = m2; p.ld = ld; p.B = B; p.C = C; p.HW = HW; p.coef = coef; p.lin = lin; p.prediction_type = prediction_type;
+  p.phi = guidance_rescale; p.stats = const_cast<float*>(stats); p.part = part;
+  return p;
+}
 int dd_op_cfg_ddim(const float* eps2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW, const float* coef,
                    void* st) {
-  return (int)launch_cfg_ddim(eps2, ld, z, z_prev, x0, B, C, HW, coef, S(st));
+  return dd_op_sampler_step(eps2, ld, z, z_prev, x0, B, C, HW, coef, nullptr, 0, 0.f, nullptr, nullptr, st);
 }
 int dd_op_cfg_ddim_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_eps2, int ld, float* g_z, int B, int C, int HW,
                        const float* coef, void* st) {
-  return (int)launch_cfg_ddim_bwd(g_x0, g_zprev, g_eps2, ld, g_z, B, C, HW, coef, S(st));
+  return dd_op_sampler_step_bwd(g_x0, g_zprev, g_eps2, ld, g_z, B, C, HW, coef, nullptr, 0, 0.f, nullptr, nullptr, nullptr, st);
 }
 int dd_op_step_coefs(int prediction_type, double a, double a_prev, float* out4) {
   if (!out4) return -1;
@@ -97,13 +105,13 @@ int dd_op_step_coefs(int prediction_type, double a, double a_prev, float* out4) 
 size_t dd_op_sampler_step_scratch_floats(int B, int HW) { return sampler_step_scratch_floats(B, HW); }
 int dd_op_sampler_step(const float* m2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW, const float* coef,
                        const float* lin, int prediction_type, float guidance_rescale, float* stats, float* part, void* st) {
-  return (int)launch_sampler_step(m2, ld, z, z_prev, x0, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part, S(st));
+  return dd_op_sampler_step_2m(m2, ld, z, nullptr, 0.f, z_prev, x0, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part, st);
 }
 int dd_op_sampler_step_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_m2, int ld, float* g_z, int B, int C, int HW,
                            const float* coef, const float* lin, int prediction_type, float guidance_rescale, const float* m2,
                            const float* stats, float* part, void* st) {
-  return (int)launch_sampler_step_bwd(g_x0, g_zprev, g_m2, ld, g_z, B, C, HW, coef, lin, prediction_type, guidance_rescale, m2, stats, part,
-                                      S(st));
+  return (int)launch_sampler_step_bwd(step_params(m2, ld, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part), g_x0, g_zprev,
+                                      g_m2, g_z, S(st));
 }
 float dd_op_step_coef_2m(int step_index, int n_steps, double a_before, double a, double a_prev) {
   return sampler_step_coef_2m(step_index, n_steps, a_before, a, a_prev);
@@ -111,8 +119,9 @@ float dd_op_step_coef_2m(int step_index, int n_steps, double a_before, double a,
 int dd_op_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c2m, float* z_prev, float* x0, int B, int C,
                           int HW, const float* coef, const float* lin, int prediction_type, float guidance_rescale, float* stats,
                           float* part, void* st) {
-  return (int)launch_sampler_step_2m(m2, ld, z, x0_prev, c2m, z_prev, x0, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part,
-                                     S(st));
+  StepParams p = step_params(m2, ld, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part);
+  p.z = z; p.x0_prev = x0_prev; p.c2m = c2m; p.z_prev = z_prev; p.x0 = x0;
+  return (int)launch_sampler_step(p, S(st));
 }
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int acc, void* st) {
   return (int)launch_sumpool2x2(src, src_ld, dst, dst_ld, B, H, W, C, acc, S(st));

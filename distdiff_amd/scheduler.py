@@ -1,6 +1,6 @@
 """Host-side DDIM schedule tables (what the reference gets from diffusers' DDIMScheduler.from_pretrained +
 retrieve_timesteps, generate_data.py:863, 1043-1044). Only tables live here; the per-element update runs in the
-cfg_ddim / sampler_step HIP kernels (elementwise.hip).  Same fp32 torch / float64 numpy arithmetic as diffusers 0.28:
+sampler-step HIP kernel (csrc/sampler_step.hip).  Same fp32 torch / float64 numpy arithmetic as diffusers 0.28:
 `beta_schedule` scaled_linear | linear, `rescale_betas_zero_snr`, `timestep_spacing` leading | trailing | linspace."""
 import numpy as np
 

@@ -11,9 +11,9 @@
  *   dd_op_groupnorm_*    GroupNorm(+SiLU) in ResnetBlock2D / Transformer2D / VAE decoder (:112, :701)
  *   dd_op_layernorm_*    LayerNorm in BasicTransformerBlock (:112)
  *   dd_op_attention_*    scaled-dot-product attention (self, cross, VAE mid block) (:112, :701)
- *   dd_op_cfg_ddim*      classifier-free guidance + DDIMScheduler.step (:116-119)
- *   dd_op_sampler_step*  the same for v_prediction / sample models and with CFG rescale
- *   dd_op_sampler_step_2m  the step of DPM-Solver++(2M) (beyond the reference, which builds a DDIMScheduler)
+ *   dd_op_sampler_step*  classifier-free guidance + DDIMScheduler.step (:116-119) for every prediction type, with optional CFG rescale
+ *                        and, as dd_op_sampler_step_2m, the step of DPM-Solver++(2M) (both beyond the reference, which builds an
+ *                        epsilon DDIMScheduler); dd_op_cfg_ddim* are its (epsilon, no rescale) mode under their first names
  *   dd_op_bicubic*       F.interpolate(..., (224,224), 'bicubic') (:704, :745)
  *   dd_op_conv_f32       timm conv+BN(+ReLU) of image_encoder.encode_image and its input-gradient in exact fp32
  *                        (model_utils.py:29-41; generate_data.py:705, :721, :746, :761): v_mfma_f32_32x32x2_f32
@@ -93,21 +93,37 @@ int dd_op_nchw_f32_to_nhwc_bf16(const float* src, uint16_t* dst, int B, int C, i
                                 float scale, void* stream);
 int dd_op_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int B, int C, int H, int W, int ld, float scale,
                            float shift, int clamp, float lo, float hi, void* stream);
+/* The sampler step: ONE operation (one forward kernel, one backward kernel; distdiff_amd/csrc/sampler_step.hip) behind the five entry
+ * points below, for every prediction_type (0 epsilon, 1 v_prediction, 2 sample; diffusers DDIMScheduler.step, eta = 0) with optional
+ * classifier-free-guidance rescale (guidance_rescale = phi of Lin et al. 2023, diffusers rescale_noise_cfg) and optional second-order
+ * term of DPM-Solver++(2M) (dd_set_schedule_s, solver 1; forward only):
+ *   m = u + s (c - u),  m^ = m (phi std(c) / std(m) + 1 - phi) per image (unbiased std over the C*HW real elements),
+ *   x0 = A_z z + A_m m^,  z' = B_z z + B_m m^ + c2m (x0 - x0_prev).
+ * Modes, chosen from the arguments alone:
+ *   (prediction_type 0, guidance_rescale 0)  evaluates x0 = (z - sqrt(1-a) m) / sqrt a, z' = sqrt a' x0 + sqrt(1-a') m on coef_dev =
+ *       {s, sqrt a, sqrt(1-a), sqrt a', sqrt(1-a')}; lin_dev, stats and part may be NULL.  dd_op_cfg_ddim / dd_op_cfg_ddim_bwd are
+ *       this mode and take only what it reads.
+ *   every other (type, rescale)  evaluates the linear form on lin_dev = {A_z, A_m, B_z, B_m}, filled by dd_op_step_coefs (host, double
+ *       arithmetic; -1 for an unknown type or a singular step: epsilon at a = 0, sample at a = 1) from alphas_cumprod at t and at the
+ *       previous timestep; coef_dev[0] = s.
+ *   guidance_rescale != 0  stats DEVICE [B][8] receives {k, std_c, std_m, mean_c, mean_m, N, phi} and is read again by the backward,
+ *       part is DEVICE scratch of dd_op_sampler_step_scratch_floats(B, HW) floats, and the backward re-reads m2 (the forward's model
+ *       output); all three may be NULL otherwise.
+ *   x0_prev != NULL and c != 0 (dd_op_sampler_step_2m)  adds c (x0 - x0_prev); x0 is then required, is always written and may be x0_prev
+ *       itself.  c = dd_op_step_coef_2m(i, n, a_before, a, a_prev) (host, double arithmetic, rounded once) from alphas_cumprod at step
+ *       i - 1, at step i and at step i's previous timestep: with lambda(a) = ln(a / (1 - a)) / 2, h = lambda(a_prev) - lambda(a),
+ *       r = (lambda(a) - lambda(a_before)) / h, c = sqrt(a_prev) (1 - e^-h) / (2 r); exactly 0.0f for i = 0, i = n - 1 and wherever a
+ *       lambda or c is not finite.  With x0_prev NULL or c == 0 the history is not read and x0 may be NULL: dd_op_sampler_step is that call.
+ * m2 fp32 rows [2B*HW, ld], unconditional half first; z, x0_prev, z', x0 and the cotangents NCHW fp32; g_m2 bf16 rows (every column
+ * written, padding 0); g_x0 or g_zprev may be NULL.
+ * Shapes: ld a multiple of 8, C <= 8, B <= 65535, for EVERY entry point; anything else returns hipErrorInvalidValue and launches
+ * nothing.  (Up to ABI 9's first builds dd_op_cfg_ddim* ran a scalar kernel of their own that took any ld and C; no caller used one.)
+ * Two-stage reductions in a fixed order, no atomics: the same call gives the same bits.  Which results are rounded once and which
+ * twice is written out in the kernels' source and pinned by tests/test_sampler_step_bits_gpu.py. */
 int dd_op_cfg_ddim(const float* eps2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW,
                    const float* coef_dev, void* stream);
 int dd_op_cfg_ddim_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_eps2, int ld, float* g_z, int B, int C, int HW,
                        const float* coef_dev, void* stream);
-/* The step for every prediction_type (0 epsilon, 1 v_prediction, 2 sample; diffusers DDIMScheduler.step, eta = 0) with optional
- * classifier-free-guidance rescale (guidance_rescale = phi of Lin et al. 2023, diffusers rescale_noise_cfg):
- *   m = u + s (c - u),  m^ = m (phi std(c) / std(m) + 1 - phi) per image (unbiased std over the C*HW real elements),
- *   x0 = A_z z + A_m m^,  z' = B_z z + B_m m^.
- * coef_dev: the 5-float row of dd_op_cfg_ddim ([0] = s); lin_dev = {A_z, A_m, B_z, B_m}, filled by dd_op_step_coefs (host, double
- * arithmetic; -1 for an unknown type or a singular step: epsilon at a = 0, sample at a = 1) from alphas_cumprod at t and at the
- * previous timestep.  (prediction_type 0, guidance_rescale 0) runs dd_op_cfg_ddim / dd_op_cfg_ddim_bwd on coef_dev, bit for bit.
- * guidance_rescale != 0: stats DEVICE [B][8] receives {k, std_c, std_m, mean_c, mean_m, N, phi} and is read again by the backward,
- * part is DEVICE scratch of dd_op_sampler_step_scratch_floats(B, HW) floats, and the backward re-reads m2 (the forward's model
- * output); all three may be NULL otherwise.  m2 fp32 rows [2B*HW, ld], g_m2 bf16 rows (every column written, padding 0); ld a
- * multiple of 8, C <= 8.  Two-stage reductions in a fixed order, no atomics: the same call gives the same bits. */
 int dd_op_step_coefs(int prediction_type, double a, double a_prev, float* out4);
 size_t dd_op_sampler_step_scratch_floats(int B, int HW);
 int dd_op_sampler_step(const float* m2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW, const float* coef_dev,
@@ -115,12 +131,6 @@ int dd_op_sampler_step(const float* m2, int ld, const float* z, float* z_prev, f
 int dd_op_sampler_step_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_m2, int ld, float* g_z, int B, int C, int HW,
                            const float* coef_dev, const float* lin_dev, int prediction_type, float guidance_rescale, const float* m2,
                            const float* stats, float* part, void* stream);
-/* DPM-Solver++(2M) (dd_set_schedule_s, solver 1), forward only: z' = [z' of dd_op_sampler_step] + c (x0 - x0_prev), x0 as there.
- * c = dd_op_step_coef_2m(i, n, a_before, a, a_prev) (host, double arithmetic, rounded once) from alphas_cumprod at step i - 1, at step
- * i and at step i's previous timestep: with lambda(a) = ln(a / (1 - a)) / 2, h = lambda(a_prev) - lambda(a), r = (lambda(a) -
- * lambda(a_before)) / h, c = sqrt(a_prev) (1 - e^-h) / (2 r).  Exactly 0.0f for i = 0, i = n - 1 and wherever a lambda or c is not
- * finite.  x0_prev NULL or c == 0 IS dd_op_sampler_step, bit for bit (x0_prev is not read); otherwise x0 is required, is always
- * written and may be x0_prev itself.  The other arguments are those of dd_op_sampler_step. */
 float dd_op_step_coef_2m(int step_index, int n_steps, double a_before, double a, double a_prev);
 int dd_op_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c, float* z_prev, float* x0, int B, int C,
                           int HW, const float* coef_dev, const float* lin_dev, int prediction_type, float guidance_rescale, float* stats,

@@ -1,6 +1,7 @@
 """Times the sampler-step kernels at the bench shape (B = 32: 64 images' worth of UNet output rows, 64 x 64 latents, C = 4) through the
-op-level ABI: today's cfg_ddim pair, the linear-form pair (v-prediction) and the linear-form pair with CFG rescale (which adds the
-two-stage statistics pass in front of the forward and the dot-product pass in front of the backward).
+op-level ABI, forward and backward: the division form of (epsilon, no rescale) -- the `cfg_ddim_*` variants, named after the entry points
+that are this mode --, the linear form (v-prediction) and the linear form with CFG rescale (which adds the two-stage statistics pass in
+front of the forward and the dot-product pass in front of the backward).
 
     python tools/bench_sampler_step.py [--out FILE.json] [--launches 2000] [--rounds 5]
 
