@@ -31,6 +31,26 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   uint4 v; v.x = pack2bf(f[0], f[1]); v.y = pack2bf(f[2], f[3]); v.z = pack2bf(f[4], f[5]); v.w = pack2bf(f[6], f[7]);
   return v;
 }
+// A row of T (bf16_t or float) as the side kernels see it: one 16-byte vector holds V = 1 << SH elements, which are fp32 between
+// ld and st; get / put move one element.  bf16 rounds in st / put (RNE), fp32 is stored as it is.
+template <typename T> struct Row;
+template <> struct Row<bf16_t> {
+  static constexpr int SH = 3, V = 8;
+  static __device__ __forceinline__ void ld(const bf16_t* p, float* f) { unpack8(*(const uint4*)p, f); }
+  static __device__ __forceinline__ void st(bf16_t* p, const float* f) { *(uint4*)p = pack8(f); }
+  static __device__ __forceinline__ float get(const bf16_t* p) { return bf2f(*p); }
+  static __device__ __forceinline__ void put(bf16_t* p, float v) { *p = f2bf(v); }
+};
+template <> struct Row<float> {
+  static constexpr int SH = 2, V = 4;
+  static __device__ __forceinline__ void ld(const float* p, float* f) {
+    const float4 v = *(const float4*)p;
+    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+  }
+  static __device__ __forceinline__ void st(float* p, const float* f) { *(float4*)p = make_float4(f[0], f[1], f[2], f[3]); }
+  static __device__ __forceinline__ float get(const float* p) { return *p; }
+  static __device__ __forceinline__ void put(float* p, float v) { *p = v; }
+};
 // v_rcp_f32 (1 ulp) instead of the IEEE division sequence (~10 VALU per element: GroupNorm+SiLU touches every activation)
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float dsilu_f(float x) { float s = __builtin_amdgcn_rcpf(1.f + __expf(-x)); return s * (1.f + x * (1.f - s)); }

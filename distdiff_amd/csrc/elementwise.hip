@@ -18,15 +18,18 @@ inline int nblocks(size_t n, int threads = 256, int cap = 8192) {
   return (int)b;
 }
 
-__global__ void nchw_to_nhwc_kernel(const float* src, bf16_t* dst, int B, int C, int HW, int Cpad, int ld, int dup, float scale) {
-  const size_t total = (size_t)(dup ? 2 * B : B) * HW * Cpad;
+// DUP: the form that can write the batch twice (dup) and scale it; without it dup and scale are not read, and the instance is the
+// plain re-layout it was before the two formats shared this kernel (same registers, same instructions)
+template <typename T, bool DUP>
+__global__ void nchw_to_nhwc_kernel(const float* src, T* dst, int B, int C, int HW, int Cpad, int ld, int dup, float scale) {
+  const size_t total = (size_t)(DUP && dup ? 2 * B : B) * HW * Cpad;
   GRID_STRIDE(i, total) {
     const int c = (int)(i % Cpad);
     const size_t row = i / Cpad;
     const int pix = (int)(row % HW);
-    const int b = (int)((row / HW) % B);
-    const float v = c < C ? src[((size_t)b * C + c) * HW + pix] * scale : 0.f;
-    dst[row * ld + c] = f2bf(v);
+    const int b = DUP ? (int)((row / HW) % B) : (int)(row / HW);
+    const float v = c < C ? src[((size_t)b * C + c) * HW + pix] * (DUP ? scale : 1.f) : 0.f;
+    Row<T>::put(dst + row * ld + c, v);
   }
 }
 
@@ -91,34 +94,41 @@ __global__ void sumpool_kernel(const bf16_t* src, int src_ld, bf16_t* dst, int d
   }
 }
 
-__global__ void add_kernel(const bf16_t* a, int lda, const bf16_t* b, int ldb, bf16_t* y, int ldy, int M, int C) {
-  const int VC = C >> 3;
+// y = a (+ b)
+template <typename T>
+__global__ void add_kernel(const T* a, int lda, const T* b, int ldb, T* y, int ldy, int M, int C) {
+  constexpr int V = Row<T>::V;
+  const int VC = C >> Row<T>::SH;
   GRID_STRIDE(i, (size_t)M * VC) {
     const int vc = (int)(i % VC);
     const size_t m = i / VC;
-    float x[8], z[8];
-    unpack8(*(const uint4*)(a + m * lda + vc * 8), x);
+    float x[V], z[V];
+    Row<T>::ld(a + m * lda + vc * V, x);
     if (b) {
-      unpack8(*(const uint4*)(b + m * ldb + vc * 8), z);
+      Row<T>::ld(b + m * ldb + vc * V, z);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] += z[e];
+      for (int e = 0; e < V; ++e) x[e] += z[e];
     }
-    *(uint4*)(y + m * ldy + vc * 8) = pack8(x);
+    Row<T>::st(y + m * ldy + vc * V, x);
   }
 }
 
-// y = dy * (mask > 0)
-__global__ void mask_kernel(const bf16_t* dy, int ldd, const bf16_t* mask, int ldm, bf16_t* y, int ldy, int M, int C) {
-  const int VC = C >> 3;
+// y = dy * (mask > 0), the ReLU backward from the stored forward output; HI: y = dy * (mask > 0 && mask < hi), where hi = +inf is
+// again ReLU (but blocks a mask of +inf, which the plain form passes) and 6 is ReLU6 = hardtanh(0, 6), whose gradient is 1 strictly
+// inside the interval
+template <typename T, bool HI>
+__global__ void mask_kernel(const T* dy, int ldd, const T* mask, int ldm, T* y, int ldy, int M, int C, float hi) {
+  constexpr int V = Row<T>::V;
+  const int VC = C >> Row<T>::SH;
   GRID_STRIDE(i, (size_t)M * VC) {
     const int vc = (int)(i % VC);
     const size_t m = i / VC;
-    float x[8], z[8];
-    unpack8(*(const uint4*)(dy + m * ldd + vc * 8), x);
-    unpack8(*(const uint4*)(mask + m * ldm + vc * 8), z);
+    float x[V], z[V];
+    Row<T>::ld(dy + m * ldd + vc * V, x);
+    Row<T>::ld(mask + m * ldm + vc * V, z);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) x[e] = z[e] > 0.f ? x[e] : 0.f;
-    *(uint4*)(y + m * ldy + vc * 8) = pack8(x);
+    for (int e = 0; e < V; ++e) x[e] = (z[e] > 0.f && (!HI || z[e] < hi)) ? x[e] : 0.f;
+    Row<T>::st(y + m * ldy + vc * V, x);
   }
 }
 
@@ -145,62 +155,66 @@ __global__ void geglu_bwd_kernel(const bf16_t* raw, int ld_raw, const bf16_t* do
   }
 }
 
-__global__ void maxpool_kernel(const bf16_t* x, bf16_t* y, int B, int H, int W, int C) {
-  const int Ho = H / 2, Wo = W / 2, VC = C >> 3;
+template <typename T>
+__global__ void maxpool_kernel(const T* x, T* y, int B, int H, int W, int C) {
+  constexpr int V = Row<T>::V;
+  const int Ho = H / 2, Wo = W / 2, VC = C >> Row<T>::SH;
   GRID_STRIDE(i, (size_t)B * Ho * Wo * VC) {
     const int vc = (int)(i % VC);
     const size_t pix = i / VC;
     const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho), b = (int)(pix / ((size_t)Wo * Ho));
-    float m[8];
+    float m[V];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
+    for (int e = 0; e < V; ++e) m[e] = -INFINITY;
     for (int ky = 0; ky < 3; ++ky)
       for (int kx = 0; kx < 3; ++kx) {
         const int iy = oy * 2 + ky - 1, ix = ox * 2 + kx - 1;
         if (iy < 0 || ix < 0 || iy >= H || ix >= W) continue;
-        float v[8];
-        unpack8(*(const uint4*)(x + (((size_t)b * H + iy) * W + ix) * C + vc * 8), v);
+        float v[V];
+        Row<T>::ld(x + (((size_t)b * H + iy) * W + ix) * C + vc * V, v);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], v[e]);
+        for (int e = 0; e < V; ++e) m[e] = fmaxf(m[e], v[e]);
       }
-    *(uint4*)(y + pix * C + vc * 8) = pack8(m);
+    Row<T>::st(y + pix * C + vc * V, m);
   }
 }
 
-// gradient goes to the first maximum of each window in (ky, kx) scan order (PyTorch CPU/CUDA max_pool2d).
-__global__ void maxpool_bwd_kernel(const bf16_t* x, const bf16_t* dy, bf16_t* dx, int B, int H, int W, int C) {
-  const int Ho = H / 2, Wo = W / 2, VC = C >> 3;
+// gradient goes to the first maximum of each window in (ky, kx) scan order (PyTorch CPU/CUDA max_pool2d); gather form, no atomics
+template <typename T>
+__global__ void maxpool_bwd_kernel(const T* x, const T* dy, T* dx, int B, int H, int W, int C) {
+  constexpr int V = Row<T>::V;
+  const int Ho = H / 2, Wo = W / 2, VC = C >> Row<T>::SH;
   GRID_STRIDE(i, (size_t)B * H * W * VC) {
     const int vc = (int)(i % VC);
     const size_t pix = i / VC;
     const int ix = (int)(pix % W), iy = (int)((pix / W) % H), b = (int)(pix / ((size_t)W * H));
-    float g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float g[V] = {};
     // windows (oy, ox) that contain (iy, ix): oy*2-1 <= iy <= oy*2+1
     for (int oy = (iy) / 2; oy <= (iy + 1) / 2; ++oy) {
       if (oy < 0 || oy >= Ho) continue;
       for (int ox = (ix) / 2; ox <= (ix + 1) / 2; ++ox) {
         if (ox < 0 || ox >= Wo) continue;
-        float m[8]; int am[8];
+        float m[V]; int am[V];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; am[e] = -1; }
+        for (int e = 0; e < V; ++e) { m[e] = -INFINITY; am[e] = -1; }
         for (int ky = 0; ky < 3; ++ky)
           for (int kx = 0; kx < 3; ++kx) {
             const int yy = oy * 2 + ky - 1, xx = ox * 2 + kx - 1;
             if (yy < 0 || xx < 0 || yy >= H || xx >= W) continue;
-            float v[8];
-            unpack8(*(const uint4*)(x + (((size_t)b * H + yy) * W + xx) * C + vc * 8), v);
+            float v[V];
+            Row<T>::ld(x + (((size_t)b * H + yy) * W + xx) * C + vc * V, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e)
+            for (int e = 0; e < V; ++e)
               if (v[e] > m[e]) { m[e] = v[e]; am[e] = yy * W + xx; }
           }
-        float d[8];
-        unpack8(*(const uint4*)(dy + (((size_t)b * Ho + oy) * Wo + ox) * C + vc * 8), d);
+        float d[V];
+        Row<T>::ld(dy + (((size_t)b * Ho + oy) * Wo + ox) * C + vc * V, d);
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
+        for (int e = 0; e < V; ++e)
           if (am[e] == iy * W + ix) g[e] += d[e];
       }
     }
-    *(uint4*)(dx + pix * C + vc * 8) = pack8(g);
+    Row<T>::st(dx + pix * C + vc * V, g);
   }
 }
 
@@ -211,8 +225,10 @@ __device__ __forceinline__ void cubic_coeffs(float t, float* w) {
   w[0] = cc2(t + 1.f, A); w[1] = cc1(t, A); w[2] = cc1(1.f - t, A); w[3] = cc2(2.f - t, A);
 }
 
-__global__ void bicubic_kernel(const bf16_t* src, int ld_s, bf16_t* dst, int ld_d, int B, int Hs, int Ws, int Hd, int Wd, int C,
-                               int Cpad) {
+// F.interpolate(img, (Hd, Wd), mode='bicubic') (generate_data.py:704, :745): A = -0.75, align_corners=False, no antialias,
+// border-clamped taps.  src NHWC [B,Hs,Ws,ld_s] -> dst [B,Hd,Wd,ld_d], channels >= C zero-filled up to Cpad.
+template <typename T>
+__global__ void bicubic_kernel(const T* src, int ld_s, T* dst, int ld_d, int B, int Hs, int Ws, int Hd, int Wd, int C, int Cpad) {
   const float sh = (float)Hs / (float)Hd, sw = (float)Ws / (float)Wd;
   GRID_STRIDE(i, (size_t)B * Hd * Wd) {
     const int ox = (int)(i % Wd), oy = (int)((i / Wd) % Hd), b = (int)(i / ((size_t)Wd * Hd));
@@ -231,20 +247,21 @@ __global__ void bicubic_kernel(const bf16_t* src, int ld_s, bf16_t* dst, int ld_
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int xx = min(max(ix - 1 + q, 0), Ws - 1);
-            r += wx[q] * bf2f(src[(((size_t)b * Hs + yy) * Ws + xx) * ld_s + c]);
+            r += wx[q] * Row<T>::get(src + (((size_t)b * Hs + yy) * Ws + xx) * ld_s + c);
           }
           acc += wy[a] * r;
         }
       }
-      dst[i * ld_d + c] = f2bf(acc);
+      Row<T>::put(dst + i * ld_d + c, acc);
     }
   }
 }
 
 // Transposed bicubic as a gather over destination pixels whose 4x4 footprints (after border clamping) hit this
-// source pixel: deterministic, no atomics. For a down-scale factor s the candidate dst range is small.
-__global__ void bicubic_bwd_kernel(const bf16_t* ddst, int ld_d, bf16_t* dsrc, int ld_s, int B, int Hs, int Ws, int Hd, int Wd,
-                                   int C) {
+// source pixel: deterministic, no atomics. For a down-scale factor s the candidate dst range is small.  The gradient may change
+// format on the way: fp32 ddst -> bf16 dsrc is the guide's input gradient written into the VAE decoder's gradient slab.
+template <typename TI, typename TO>
+__global__ void bicubic_bwd_kernel(const TI* ddst, int ld_d, TO* dsrc, int ld_s, int B, int Hs, int Ws, int Hd, int Wd, int C) {
   const float sh = (float)Hs / (float)Hd, sw = (float)Ws / (float)Wd;
   GRID_STRIDE(i, (size_t)B * Hs * Ws) {
     const int sx = (int)(i % Ws), sy = (int)((i / Ws) % Hs), b = (int)(i / ((size_t)Ws * Hs));
@@ -271,31 +288,45 @@ __global__ void bicubic_bwd_kernel(const bf16_t* ddst, int ld_d, bf16_t* dsrc, i
 #pragma unroll
         for (int q = 0; q < 4; ++q) wxs += (min(max((int)fx - 1 + q, 0), Ws - 1) == sx) ? wx[q] : 0.f;
         if (wxs == 0.f) continue;
-        const bf16_t* d = ddst + (((size_t)b * Hd + oy) * Wd + ox) * ld_d;
-        for (int c = 0; c < C && c < 4; ++c) acc[c] += wys * wxs * bf2f(d[c]);
+        const TI* d = ddst + (((size_t)b * Hd + oy) * Wd + ox) * ld_d;
+        for (int c = 0; c < C && c < 4; ++c) acc[c] += wys * wxs * Row<TI>::get(d + c);
       }
     }
-    for (int c = 0; c < C && c < 4; ++c) dsrc[i * ld_s + c] = f2bf(acc[c]);
+    for (int c = 0; c < C && c < 4; ++c) Row<TO>::put(dsrc + i * ld_s + c, acc[c]);
   }
 }
 
-__global__ void gap_kernel(const bf16_t* x, int ld, float* f, int B, int HW, int C) {
+// encode_image's pooling (model_utils.py:31-37): 'avg' = AdaptiveAvgPool2d(1), 'max' = AdaptiveMaxPool2d(1); the max form also records
+// its argmax pixel for the VJP when arg is given (first maximum in scan order, like torch).  MAX: the instance has the max form at all
+// (the bf16 guides only average: their instance stays the loop it was)
+template <typename T, bool MAX>
+__global__ void gap_kernel(const T* x, int ld, float* f, int* arg, int B, int HW, int C, int use_max) {
   GRID_STRIDE(i, (size_t)B * C) {
     const int c = (int)(i % C), b = (int)(i / C);
-    float s = 0.f;
-    for (int pxl = 0; pxl < HW; ++pxl) s += bf2f(x[((size_t)b * HW + pxl) * ld + c]);
-    f[i] = s / HW;
+    if (MAX && use_max) {
+      float m = -INFINITY; int am = 0;
+      for (int pxl = 0; pxl < HW; ++pxl) { const float v = Row<T>::get(x + ((size_t)b * HW + pxl) * ld + c); if (v > m) { m = v; am = pxl; } }
+      f[i] = m;
+      if (arg) arg[i] = am;
+    } else {
+      float s = 0.f;
+      for (int pxl = 0; pxl < HW; ++pxl) s += Row<T>::get(x + ((size_t)b * HW + pxl) * ld + c);
+      f[i] = s / HW;
+    }
   }
 }
 
-__global__ void gap_bwd_kernel(const float* gf, bf16_t* dx, int ld, int B, int HW, int C, const bf16_t* mask, int mask_ld) {
+// dx = gf / HW on every pixel, or gf on the argmax pixel alone (arg); mask: times (mask > 0), the ReLU in front of the pooling
+template <typename T>
+__global__ void gap_bwd_kernel(const float* gf, T* dx, int ld, int B, int HW, int C, const T* mask, int mask_ld, const int* arg) {
   GRID_STRIDE(i, (size_t)B * HW * C) {
     const int c = (int)(i % C);
     const size_t row = i / C;
-    const int b = (int)(row / HW);
-    float v = gf[(size_t)b * C + c] / HW;
-    if (mask && !(bf2f(mask[row * mask_ld + c]) > 0.f)) v = 0.f;
-    dx[row * ld + c] = f2bf(v);
+    const int b = (int)(row / HW), pxl = (int)(row % HW);
+    const float g = gf[(size_t)b * C + c];
+    float v = arg ? (arg[(size_t)b * C + c] == pxl ? g : 0.f) : g / HW;
+    if (mask && !(Row<T>::get(mask + row * mask_ld + c) > 0.f)) v = 0.f;
+    Row<T>::put(dx + row * ld + c, v);
   }
 }
 
@@ -608,13 +639,47 @@ __global__ void rows_bf16_to_f32_kernel(const bf16_t* x, int ld, float* y, int M
 }  // namespace
 
 #define LAUNCH(kern, n, ...) hipLaunchKernelGGL(kern, dim3(nblocks(n)), dim3(256), 0, s, __VA_ARGS__); return hipGetLastError()
-// The 8-wide bf16 row kernels move whole uint4 vectors: a channel count that is not a multiple of 8 would lose its tail, a row stride
-// that is not would misalign the 16-byte accesses.  Refused on the host, in front of any launch.
-#define VEC8(...) do { const int _v[] = {__VA_ARGS__}; for (int _x : _v) if (_x & 7) return hipErrorInvalidValue; } while (0)
+// The row kernels move whole 16-byte vectors of V elements (Row<T>::V: 8 bf16, 4 fp32): a channel count that is not a multiple of V would
+// lose its tail, a row stride that is not would misalign the accesses.  Refused on the host, in front of any launch.
+#define VEC(V, ...) do { const int _v[] = {__VA_ARGS__}; for (int _x : _v) if (_x & ((V) - 1)) return hipErrorInvalidValue; } while (0)
+
+// the launchers of the kernels that serve both row formats: refusals and grid once, the launch_* surface of kernels.h below them
+namespace {
+template <typename T>
+hipError_t add_rows(const T* a, int lda, const T* b, int ldb, T* y, int ldy, int M, int C, hipStream_t s) {
+  VEC(Row<T>::V, C, lda, b ? ldb : 0, ldy);
+  LAUNCH(add_kernel<T>, (size_t)M * (C / Row<T>::V), a, lda, b, ldb, y, ldy, M, C);
+}
+template <typename T, bool HI>
+hipError_t mask_rows(const T* dy, int ldd, const T* mask, int ldm, T* y, int ldy, int M, int C, float hi, hipStream_t s) {
+  VEC(Row<T>::V, C, ldd, ldm, ldy);
+  LAUNCH((mask_kernel<T, HI>), (size_t)M * (C / Row<T>::V), dy, ldd, mask, ldm, y, ldy, M, C, hi);
+}
+template <typename T>
+hipError_t maxpool_rows(const T* x, T* y, int B, int H, int W, int C, hipStream_t s) {
+  VEC(Row<T>::V, C);
+  if ((H | W) & 1) return hipErrorInvalidValue;      // the kernels pool to H / 2 x W / 2: torch's (H - 1) / 2 + 1 for even sizes only
+  LAUNCH(maxpool_kernel<T>, (size_t)B * (H / 2) * (W / 2) * (C / Row<T>::V), x, y, B, H, W, C);
+}
+template <typename T>
+hipError_t maxpool_bwd_rows(const T* x, const T* dy, T* dx, int B, int H, int W, int C, hipStream_t s) {
+  VEC(Row<T>::V, C);
+  if ((H | W) & 1) return hipErrorInvalidValue;
+  LAUNCH(maxpool_bwd_kernel<T>, (size_t)B * H * W * (C / Row<T>::V), x, dy, dx, B, H, W, C);
+}
+template <typename TI, typename TO>
+hipError_t bicubic_bwd_rows(const TI* ddst, int ld_d, TO* dsrc, int ld_s, int B, int Hs, int Ws, int Hd, int Wd, int C, hipStream_t s) {
+  if (C > 4) return hipErrorInvalidValue;
+  LAUNCH((bicubic_bwd_kernel<TI, TO>), (size_t)B * Hs * Ws, ddst, ld_d, dsrc, ld_s, B, Hs, Ws, Hd, Wd, C);
+}
+}  // namespace
 
 hipError_t launch_nchw_f32_to_nhwc_bf16(const float* src, bf16_t* dst, int B, int C, int H, int W, int Cpad, int ld, int dup,
                                         float scale, hipStream_t s) {
-  LAUNCH(nchw_to_nhwc_kernel, (size_t)(dup ? 2 : 1) * B * H * W * Cpad, src, dst, B, C, H * W, Cpad, ld, dup, scale);
+  LAUNCH((nchw_to_nhwc_kernel<bf16_t, true>), (size_t)(dup ? 2 : 1) * B * H * W * Cpad, src, dst, B, C, H * W, Cpad, ld, dup, scale);
+}
+hipError_t launch_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int H, int W, int Cpad, int ld, hipStream_t s) {
+  LAUNCH((nchw_to_nhwc_kernel<float, false>), (size_t)B * H * W * Cpad, src, dst, B, C, H * W, Cpad, ld, 0, 1.f);
 }
 hipError_t launch_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int B, int C, int H, int W, int ld, float scale,
                                    float shift, int clamp, float lo, float hi, hipStream_t s) {
@@ -628,52 +693,74 @@ hipError_t launch_axpby(const float* x, const float* n, float* out, size_t count
 }
 hipError_t launch_sumpool2x2(const bf16_t* src, int src_ld, bf16_t* dst, int dst_ld, int B, int H, int W, int C, int accumulate,
                              hipStream_t s) {
-  VEC8(C, src_ld, dst_ld);
+  VEC(8, C, src_ld, dst_ld);
   LAUNCH(sumpool_kernel, (size_t)B * H * W * (C / 8), src, src_ld, dst, dst_ld, B, H, W, C, accumulate);
 }
 hipError_t launch_add_bf16(const bf16_t* a, int lda, const bf16_t* b, int ldb, bf16_t* y, int ldy, int M, int C, hipStream_t s) {
-  VEC8(C, lda, b ? ldb : 0, ldy);
-  LAUNCH(add_kernel, (size_t)M * (C / 8), a, lda, b, ldb, y, ldy, M, C);
+  return add_rows(a, lda, b, ldb, y, ldy, M, C, s);
+}
+hipError_t launch_add_f32(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int M, int C, hipStream_t s) {
+  return add_rows(a, lda, b, ldb, y, ldy, M, C, s);
 }
 hipError_t launch_copy_bf16(const bf16_t* a, int lda, bf16_t* y, int ldy, int M, int C, hipStream_t s) {
-  VEC8(C, lda, ldy);
-  LAUNCH(add_kernel, (size_t)M * (C / 8), a, lda, (const bf16_t*)nullptr, 0, y, ldy, M, C);
+  return add_rows(a, lda, (const bf16_t*)nullptr, 0, y, ldy, M, C, s);
+}
+hipError_t launch_copy_f32(const float* a, int lda, float* y, int ldy, int M, int C, hipStream_t s) {
+  return add_rows(a, lda, (const float*)nullptr, 0, y, ldy, M, C, s);
 }
 hipError_t launch_mask_bf16(const bf16_t* dy, int ldd, const bf16_t* mask, int ldm, bf16_t* y, int ldy, int M, int C,
                             hipStream_t s) {
-  VEC8(C, ldd, ldm, ldy);
-  LAUNCH(mask_kernel, (size_t)M * (C / 8), dy, ldd, mask, ldm, y, ldy, M, C);
+  return mask_rows<bf16_t, false>(dy, ldd, mask, ldm, y, ldy, M, C, 0.f, s);
+}
+hipError_t launch_mask_f32(const float* dy, int ldd, const float* mask, int ldm, float* y, int ldy, int M, int C, float hi, hipStream_t s) {
+  return mask_rows<float, true>(dy, ldd, mask, ldm, y, ldy, M, C, hi > 0.f ? hi : INFINITY, s);
 }
 hipError_t launch_geglu_bwd(const bf16_t* raw, int ld_raw, const bf16_t* dout, int ld_dout, bf16_t* draw, int ld_draw, int M,
                             int F, hipStream_t s) {
-  VEC8(F, ld_raw, ld_dout, ld_draw);
+  VEC(8, F, ld_raw, ld_dout, ld_draw);
   LAUNCH(geglu_bwd_kernel, (size_t)M * (F / 8), raw, ld_raw, dout, ld_dout, draw, ld_draw, M, F);
 }
 hipError_t launch_maxpool3x3s2(const bf16_t* x, bf16_t* y, int B, int H, int W, int C, hipStream_t s) {
-  VEC8(C);
-  if ((H | W) & 1) return hipErrorInvalidValue;      // the kernels pool to H / 2 x W / 2: torch's (H - 1) / 2 + 1 for even sizes only
-  LAUNCH(maxpool_kernel, (size_t)B * (H / 2) * (W / 2) * (C / 8), x, y, B, H, W, C);
+  return maxpool_rows(x, y, B, H, W, C, s);
+}
+hipError_t launch_maxpool3x3s2_f32(const float* x, float* y, int B, int H, int W, int C, hipStream_t s) {
+  return maxpool_rows(x, y, B, H, W, C, s);
 }
 hipError_t launch_maxpool3x3s2_bwd(const bf16_t* x, const bf16_t* dy, bf16_t* dx, int B, int H, int W, int C, hipStream_t s) {
-  VEC8(C);
-  if ((H | W) & 1) return hipErrorInvalidValue;
-  LAUNCH(maxpool_bwd_kernel, (size_t)B * H * W * (C / 8), x, dy, dx, B, H, W, C);
+  return maxpool_bwd_rows(x, dy, dx, B, H, W, C, s);
+}
+hipError_t launch_maxpool3x3s2_bwd_f32(const float* x, const float* dy, float* dx, int B, int H, int W, int C, hipStream_t s) {
+  return maxpool_bwd_rows(x, dy, dx, B, H, W, C, s);
 }
 hipError_t launch_bicubic(const bf16_t* src, int ld_s, bf16_t* dst, int ld_d, int B, int Hs, int Ws, int Hd, int Wd, int C,
                           int Cpad, hipStream_t s) {
-  LAUNCH(bicubic_kernel, (size_t)B * Hd * Wd, src, ld_s, dst, ld_d, B, Hs, Ws, Hd, Wd, C, Cpad);
+  LAUNCH(bicubic_kernel<bf16_t>, (size_t)B * Hd * Wd, src, ld_s, dst, ld_d, B, Hs, Ws, Hd, Wd, C, Cpad);
+}
+hipError_t launch_bicubic_f32(const float* src, int ld_s, float* dst, int ld_d, int B, int Hs, int Ws, int Hd, int Wd, int C, int Cpad,
+                              hipStream_t s) {
+  LAUNCH(bicubic_kernel<float>, (size_t)B * Hd * Wd, src, ld_s, dst, ld_d, B, Hs, Ws, Hd, Wd, C, Cpad);
 }
 hipError_t launch_bicubic_bwd(const bf16_t* ddst, int ld_d, bf16_t* dsrc, int ld_s, int B, int Hs, int Ws, int Hd, int Wd, int C,
                               hipStream_t s) {
-  if (C > 4) return hipErrorInvalidValue;
-  LAUNCH(bicubic_bwd_kernel, (size_t)B * Hs * Ws, ddst, ld_d, dsrc, ld_s, B, Hs, Ws, Hd, Wd, C);
+  return bicubic_bwd_rows(ddst, ld_d, dsrc, ld_s, B, Hs, Ws, Hd, Wd, C, s);
+}
+hipError_t launch_bicubic_bwd_f32(const float* ddst, int ld_d, void* dsrc, int dsrc_bf16, int ld_s, int B, int Hs, int Ws, int Hd, int Wd,
+                                  int C, hipStream_t s) {
+  return dsrc_bf16 ? bicubic_bwd_rows(ddst, ld_d, (bf16_t*)dsrc, ld_s, B, Hs, Ws, Hd, Wd, C, s)
+                   : bicubic_bwd_rows(ddst, ld_d, (float*)dsrc, ld_s, B, Hs, Ws, Hd, Wd, C, s);
 }
 hipError_t launch_gap(const bf16_t* x, int ld, float* f, int B, int HW, int C, hipStream_t s) {
-  LAUNCH(gap_kernel, (size_t)B * C, x, ld, f, B, HW, C);
+  LAUNCH((gap_kernel<bf16_t, false>), (size_t)B * C, x, ld, f, (int*)nullptr, B, HW, C, 0);
+}
+hipError_t launch_gap_f32(const float* x, int ld, float* f, int* argmax, int B, int HW, int C, int use_max, hipStream_t s) {
+  LAUNCH((gap_kernel<float, true>), (size_t)B * C, x, ld, f, argmax, B, HW, C, use_max);
 }
 hipError_t launch_gap_bwd(const float* gf, bf16_t* dx, int ld, int B, int HW, int C, const bf16_t* mask, int mask_ld,
                           hipStream_t s) {
-  LAUNCH(gap_bwd_kernel, (size_t)B * HW * C, gf, dx, ld, B, HW, C, mask, mask_ld);
+  LAUNCH(gap_bwd_kernel<bf16_t>, (size_t)B * HW * C, gf, dx, ld, B, HW, C, mask, mask_ld, (const int*)nullptr);
+}
+hipError_t launch_gap_bwd_f32(const float* gf, float* dx, int ld, int B, int HW, int C, const int* argmax, hipStream_t s) {
+  LAUNCH(gap_bwd_kernel<float>, (size_t)B * HW * C, gf, dx, ld, B, HW, C, (const float*)nullptr, 0, argmax);
 }
 hipError_t launch_energy(const float* f, const float* Pc, const float* Pg, const int* targets, int B, int D, int K, float gs,
                          float ls, int use_c, int use_g, int normalize, float weight, const float* sample_w, float* score_out,

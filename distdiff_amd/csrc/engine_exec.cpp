@@ -272,7 +272,6 @@ void run_fwd(const Program& P, const Ctx& c) {
         HIPCHK(launch_copy_bf16(act_ptr(c, x), x.ld, act_ptr(c, y), y.ld, x.rows, rup(x.C, 8), c.s));
         HIPCHK(launch_copy_bf16(act_ptr(c, x), x.ld, act_ptr(c, y) + (size_t)x.rows * y.ld, y.ld, x.rows, rup(x.C, 8), c.s));
       } break;
-      case OP_GAP: break;
     }
     if (c.prof) c.prof->end(c.s);
   }
@@ -423,7 +422,6 @@ void run_bwd(const Program& P, const Ctx& c) {
         if (!x.grad) break;
         HIPCHK(launch_select_rows_bwd(grad_ptr(c, y), y.ld, grad_ptr(c, x), x.ld, x.B, op.sel_stride, x.C, op.x_acc ? 1 : 0, c.s));
       } break;
-      case OP_GAP: break;
     }
   }
 }

@@ -210,7 +210,7 @@ void plan_backward(Program& P) {
         }
         op.x_acc = mark(op.x);
         break;
-      case OP_GN: case OP_LN: case OP_MAXPOOL: case OP_GAP:
+      case OP_GN: case OP_LN: case OP_MAXPOOL:
         op.x_acc = mark(op.x);
         break;
       case OP_ACT: case OP_PATCHIFY: case OP_VITEMBED: case OP_SELECT: case OP_DUP:
@@ -267,7 +267,7 @@ void plan_grad_memory(Program& P) {
     const Op& op = P.ops[i];
     if (op.y >= 0) { has_prod[op.y] = 1; touch(op.y, i); }
     for (int id : {op.x, op.res, op.q, op.k, op.v, op.x2})
-      if (id >= 0) { touch(id, i); if (op.kind != OP_GAP) has_cons[id] = 1; }
+      if (id >= 0) { touch(id, i); has_cons[id] = 1; }
   }
   for (int i = 0; i < nt; ++i) {
     const Tn& t = P.t[i];

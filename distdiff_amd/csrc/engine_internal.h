@@ -91,7 +91,7 @@ struct Tn {              // activation tensor or channel view
   int glo = -(1 << 30), ghi = 1 << 30;
 };
 
-enum OpKind { OP_CONV, OP_GN, OP_LN, OP_ATTN, OP_CONCAT, OP_MAXPOOL, OP_GAP, OP_ACT, OP_PATCHIFY, OP_VITEMBED, OP_SELECT, OP_DUP };
+enum OpKind { OP_CONV, OP_GN, OP_LN, OP_ATTN, OP_CONCAT, OP_MAXPOOL, OP_ACT, OP_PATCHIFY, OP_VITEMBED, OP_SELECT, OP_DUP };
 
 struct Op {
   OpKind kind;

@@ -176,10 +176,11 @@ hipError_t launch_attention_gemm_bwd(const AttnParams& p, void* workspace, size_
 // ----------------------------------------------------------------------------------------------
 // K6/K7/K9/K10/K12: small HBM-bound kernels.
 // ----------------------------------------------------------------------------------------------
-// The vectorised bf16 row kernels (launch_add_bf16 / copy_bf16 / mask_bf16 / sumpool2x2 / geglu_bwd / maxpool3x3s2*) move uint4 vectors:
-// C (F) and every row stride must be multiples of 8, the max pools also need even H and W (they pool to H / 2 x W / 2); anything else is
-// hipErrorInvalidValue and nothing is launched.  Row base pointers must be 16-byte aligned (not checked: a column view has to start at
-// a multiple of 8 channels).
+// The vectorised row kernels (launch_add / copy / mask / maxpool3x3s2* in both formats, sumpool2x2, geglu_bwd) move 16-byte vectors of
+// V elements (8 bf16, 4 fp32: Row<T> in common.h): C (F) and every row stride must be multiples of V, the max pools also need even H and
+// W (they pool to H / 2 x W / 2); anything else is hipErrorInvalidValue and nothing is launched.  Row base pointers must be 16-byte
+// aligned (not checked: a column view has to start at a multiple of V channels).  The *_f32 forms of these kernels are declared with the
+// fp32 guide below; both formats are instances of one kernel each (elementwise.hip).
 // NCHW fp32 [B,C,H,W] -> NHWC bf16 [B*H*W, ld] (channels >= C zero-filled up to Cpad); dup copies
 // the batch twice (CFG: cat[z, z]).  scale multiplies.
 hipError_t launch_nchw_f32_to_nhwc_bf16(const float* src, bf16_t* dst, int B, int C, int H, int W, int Cpad, int ld,
@@ -317,8 +318,8 @@ hipError_t launch_rows_bf16_to_f32(const bf16_t* x, int ld, float* y, int M, int
 hipError_t launch_clip_pool_project(const int* ids, const bf16_t* x, int ld, const float* W, float* out, int n, int T, int C, int Pd, hipStream_t s);
 
 // ----------------------------------------------------------------------------------------------
-// The guide network in exact fp32 (guide_f32.hip): implicit-GEMM convolution on v_mfma_f32_32x32x2_f32 and the fp32
-// forms of the guide's side kernels.  Same tap-table / stride / dilated-gather conventions as ConvGemmParams.
+// The guide network in exact fp32: implicit-GEMM convolution on v_mfma_f32_32x32x2_f32 (guide_f32.hip) and the fp32
+// forms of the guide's side kernels (elementwise.hip).  Same tap-table / stride / dilated-gather conventions as ConvGemmParams.
 // ----------------------------------------------------------------------------------------------
 struct ConvF32Params {
   const float* x;       // input activations, NHWC fp32, row stride x_ld (multiple of 4)
@@ -336,8 +337,6 @@ struct ConvF32Params {
   int flags;            // CF_BIAS | CF_RES | CF_RELU | CF_MASK
 };
 hipError_t launch_conv_f32(const ConvF32Params& p, hipStream_t s);
-// add / copy / mask / maxpool3x3s2* move float4 vectors: C and every row stride multiples of 4, even H and W for the max pools, 16-byte
-// aligned row base pointers (hipErrorInvalidValue otherwise, pointers unchecked)
 hipError_t launch_add_f32(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int M, int C, hipStream_t s);
 hipError_t launch_copy_f32(const float* a, int lda, float* y, int ldy, int M, int C, hipStream_t s);
 // y = dy * (mask > 0 [&& mask < hi when hi > 0])   (ReLU / ReLU6 backward from the stored forward output)
