@@ -137,3 +137,10 @@ inline int persistent_cus() {
   static const int cus = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 8 ? n & ~7 : 8; }();
   return cus;
 }
+// Device: the tiles of the XCD that workgroup `block` runs on.  Workgroups b, b + 8, ... share an XCD, and every XCD owns one contiguous
+// range of the `tiles` (n-tiles fastest inside it, so that its L2 holds the operands they share): first tile and length of that range.
+struct XcdRange { int first, count; };
+__device__ __forceinline__ XcdRange xcd_tile_range(int tiles, int block) {
+  const int q = tiles >> 3, r = tiles & 7, xcd = block & 7;
+  return {xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, q + (xcd < r ? 1 : 0)};
+}

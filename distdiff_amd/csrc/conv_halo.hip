@@ -15,10 +15,15 @@
 //     (cdna_hip_programming.md section 5, "The 256^2 8-phase template"; MI355X_MICROARCH.md "Two waves per SIMD").
 // The 3x3 kernel is not persistent (one workgroup per tile, XCD-aware tile order, n-tiles fastest inside an XCD: a persistent form
 // measured slower); the pointwise GEMM of the same loop (gemm_pps_kernel, gemm_pps.hip) is.
+// Where the loop lives: pp_kloop.h holds the K-step (pp_kstep, also gemm_pps_kernel's), the chunk x tap loop around it with the halo refill
+// (pp_halo_kloop, called by both kernels of this file) and the weight-row map (pp_weight_row); pp_epilogue.h the epilogue; common.h the XCD
+// tile range.  This file keeps what differs between its two kernels: tile selection and the persistent walk, the two halo address schemes,
+// the prologues, the narrow and chunk-split stores.
 #include "common.h"
 #include "conv_dispatch.h"
 #include "conv_epilogue.h"
 #include "pp_epilogue.h"
+#include "pp_kloop.h"
 
 namespace {
 
@@ -64,11 +69,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
 
   // ---- tile of this workgroup (n-tiles fastest; blocks b, b + 8, ... share an XCD)
   const int ntn = (p.N + BN - 1) / BN, tiles = (p.M / BM) * ntn;      // (N < BN: the narrow form TN = 1, one n-tile)
-  int tile;
-  {
-    const int q = tiles >> 3, r = tiles & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int tile = xcd_tile_range(tiles, blockIdx.x).first + (blockIdx.x >> 3);
   const int n0 = (tile % ntn) * BN;
   const int mt = tile / ntn, tpi = geo.tiles_x * geo.tiles_y;
   const int ipt = MI ? geo.ipt : 1;                       // > 1: the tile is ipt whole (8 x 8) images, output rows contiguous
@@ -82,28 +83,25 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
   const int chunks_all = p.cin >> 6;
   const int cper = MI ? (chunks_all + p.ksplit - 1) / (p.ksplit > 0 ? p.ksplit : 1) : chunks_all;
   const int c_begin = MI ? kz * cper : 0, c_end = MI ? min(chunks_all, c_begin + cper) : chunks_all;
-  const int KT = (c_end - c_begin) * 9;
 
   // ---- per-tap offsets: lane t holds tap t ((dy + 32) << 6 | (dx + 32)); read with readlane where needed
   const int v_taps = lane < 9 ? p.taptab[lane] : 0;
   if (tid < BN) bias_s[tid] = ((p.flags & CF_BIAS) && n0 + tid < p.N) ? p.bias[n0 + tid] : 0.f;
 
   // ---- weight staging: wave w moves pieces w, w + 8, ... (8 rows x 128 B) of the BN weight rows of a K-step.  LDS row R of a wave's
-  // TN * 16 span holds output channel chan_of_row(R): tiles are paired so that a lane's 4 + 4 accumulator rows of a pair are 8
-  // consecutive channels (16-byte epilogue stores), exactly as in conv_gemm2.hip.
+  // TN * 16 span holds output channel pp_weight_row(R).
   const int prow = lane >> 3, jw = (lane & 7) ^ prow;
-  constexpr int TNP = TN & ~1;
   unsigned woff[NWP];
 #pragma unroll
   for (int i = 0; i < NWP; ++i) {
-    const int R = (wave + 8 * i) * 8 + prow;
-    const int wv = R / (TN * 16), q = R - wv * (TN * 16), jn = q >> 4, f = q & 15;
-    const int ch = jn < TNP ? wv * (TN * 16) + (jn >> 1) * 32 + (f >> 2) * 8 + (jn & 1) * 4 + (f & 3) : R;
+    const int R = (wave + 8 * i) * 8 + prow, ch = pp_weight_row<TN>(R);
     // (rows behind the last output channel -- the narrow form pads N = 3 / 4 to a 32-row stage -- read as zeros: out of range)
     woff[i] = (((NPC & 7) == 0 || R < BN) && n0 + ch < p.N) ? ((unsigned)(n0 + ch) * (unsigned)p.K + (unsigned)(jw * 8)) * 2u : OOB;
   }
-  auto issue_w = [&](int kt, int i) {
-    if ((NPC & 7) == 0 || wave + 8 * i < NPC) dma16(p.w, smem + (kt & 1) * WB + (wave + 8 * i) * 1024, woff[i], (unsigned)(c_begin * 9 + kt) * 128u);
+  auto issue_w = [&](int kt) {                           // this wave's pieces of K-step kt into its stage
+#pragma unroll
+    for (int i = 0; i < NWP; ++i)
+      if ((NPC & 7) == 0 || wave + 8 * i < NPC) dma16(p.w, smem + (kt & 1) * WB + (wave + 8 * i) * 1024, woff[i], (unsigned)(c_begin * 9 + kt) * 128u);
   };
   // ---- halo staging (row half 0 only): pieces wave, wave + 4, ... of ceil(halo_px / 8); a lane's pixel hp = 8 * piece + (lane >> 3)
   const float inv_w2 = 1.f / (float)W2;
@@ -160,72 +158,11 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(ConvGemmParams p, Hal
   // ---- prologue
   if (use_tab) first_halo(c_begin);
   else if (grp == 0) issue_halo(c_begin);
-#pragma unroll
-  for (int i = 0; i < NWP; ++i) issue_w(0, i);
+  issue_w(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();                                      // also publishes bias_s
   if (grp == 1) __builtin_amdgcn_s_barrier();           // the second group runs one barrier behind
-
-  // Two sections per K-step, one per 32-deep K half: 8 x TN MFMAs between two barriers (the barrier hand-off between the SIMD partners is
-  // not hidden by anything: tools/micro/pingpong_gemm.hip, four 32-row strips per K-step cost 0.5 us of barrier skeleton per K-step,
-  // two K halves 0.35), TN + 8 fragments live instead of 2 TN + 4.
-  bf16x8 wf[TN], xf[8];
-  // (narrow form, TN = 1: the second column wave of a row group only multiplies zero padding, columns 16 .. 31.  Letting it skip its
-  // fragment reads and MFMAs measured SLOWER -- 1206 -> 1504 us on the decoder's conv_out: the form is bound by the exposed halo refill
-  // of its two short chunks, not by LDS reads, and the branch cost the schedule.)
-  int kt = 0;
-  for (int c = c_begin; c < c_end; ++c) {
-    if (c > c_begin) {
-      // every read of the previous chunk's halo has retired (both groups waited lgkmcnt(0) in front of their last X barrier)
-      if (grp == 0) {
-        issue_halo(c);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-    }
-    for (int t = 0; t < 9; ++t, ++kt) {
-      const int e = __builtin_amdgcn_readlane(v_taps, t);
-      const int dy = ((e >> 6) & 63) - 32, dx = (e & 63) - 32;
-      const int tapoff = dy * W2 + dx;
-      const unsigned char* Bb = smem + (kt & 1) * WB;
-      const bool more = kt + 1 < KT;
-      const int xs = (fr + 1 + dx) & 7;                   // 16-pixel row tiles start at multiples of 16 inside an image row (tw >= 16)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        // ---- load section (the SIMD partner is in its MFMA section)
-#pragma unroll
-        for (int jn = 0; jn < TN; ++jn) {
-          const int row = wc * (TN * 16) + jn * 16 + fr;
-          wf[jn] = *(const bf16x8*)(Bb + row * 128 + (((fq + 4 * ks) ^ (row & 7)) << 4));
-        }
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-          const int r = wr * 128 + a * 16 + fr;
-          // halo pixel of output pixel r for this tap (multi-image tiles: + the two border rows of every image in front of r's)
-          const int hp = r + 2 * (r >> lw) + (MI ? 2 * W2 * (r >> 6) : 0) + Wd + 3 + tapoff;
-          xf[a] = *(const bf16x8*)(halo + hp * 128 + (((fq + 4 * ks) ^ xs) << 4));
-        }
-        if (ks == 0 && more) {
-#pragma unroll
-          for (int q = 0; q < NWP; ++q) issue_w(kt + 1, q);
-        }
-        // second half: this wave's weight pieces of K-step kt + 1 have landed and its LDS reads of this stage (and, on tap 8, of the
-        // halo) have retired BEFORE the barrier behind which the other half reads the new stage / the halo is refilled
-        if (ks == 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // ---- MFMA section
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int a = 0; a < 8; ++a)
-#pragma unroll
-          for (int jn = 0; jn < TN; ++jn)
-            acc[a][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[jn], xf[a], acc[a][jn], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_s_barrier();
-      }
-    }
-  }
+  pp_halo_kloop<TN, WB, MI>(acc, smem, halo, c_begin, c_end, 0, v_taps, lw, grp, wr, wc, fr, fq, issue_halo, issue_w);
   if (grp == 0) __builtin_amdgcn_s_barrier();           // balance the barrier count of the two groups
 
   if constexpr (MI) {
@@ -282,8 +219,8 @@ __device__ unsigned long long g_halo_trace[8192 * 6];
 // CU (LDS) nothing overlaps them.  One workgroup per CU walks its tiles: behind the last K-step of a tile the halo buffer and the idle
 // weight stage are free, so the NEXT tile's first halo chunk, first weight stage and bias row are requested BEFORE this tile's epilogue
 // and land while it stores.  Same tile -> XCD map as the one-tile kernel (an XCD's workgroups share a contiguous tile range, n-tiles
-// fastest), same K loop, same epilogue; N % BN == 0.  Results are bitwise those of conv_halo_kernel (same order of
-// operations per tile).
+// fastest), the same K loop (pp_halo_kloop) and epilogue (pp_epilogue); N % BN == 0.  Results are bitwise those of conv_halo_kernel
+// (same order of operations per tile; tests/test_pingpong_bits_gpu.py).
 template <int TN, int WN>
 __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParams p, HaloGeo geo) {
   const int lw = geo.ltw, halo_px = geo.halo_px;
@@ -304,26 +241,17 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
   const int ntn = p.N / BN, tiles = (p.M / BM) * ntn, tpi = geo.tiles_x * geo.tiles_y;
   // tiles of this workgroup: XCD x owns [xs, xs + xc); its gridDim.x / 8 workgroups take xs + idx, xs + idx + per, ...
   const int per = gridDim.x >> 3;
-  int xs, xc;
-  {
-    const int q = tiles >> 3, r = tiles & 7, xcd = blockIdx.x & 7;
-    xs = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    xc = q + (xcd < r ? 1 : 0);
-  }
+  const XcdRange xr = xcd_tile_range(tiles, blockIdx.x);
+  const int xs = xr.first, xc = xr.count;
   int t = blockIdx.x >> 3;
   if (t >= xc) return;
   const int chunks = p.cin >> 6, KT = chunks * 9;
   const int v_taps = lane < 9 ? p.taptab[lane] : 0;
   const int prow = lane >> 3, jw = (lane & 7) ^ prow;
-  constexpr int TNP = TN & ~1;
   unsigned woff[NWP];                                   // lane part of the weight offsets (n0 goes into the scalar offset)
 #pragma unroll
-  for (int i = 0; i < NWP; ++i) {
-    const int R = (wave + 8 * i) * 8 + prow;
-    const int wv = R / (TN * 16), q = R - wv * (TN * 16), jn = q >> 4, f = q & 15;
-    const int ch = jn < TNP ? wv * (TN * 16) + (jn >> 1) * 32 + (f >> 2) * 8 + (jn & 1) * 4 + (f & 3) : R;
-    woff[i] = ((unsigned)ch * (unsigned)p.K + (unsigned)(jw * 8)) * 2u;
-  }
+  for (int i = 0; i < NWP; ++i)
+    woff[i] = ((unsigned)pp_weight_row<TN>((wave + 8 * i) * 8 + prow) * (unsigned)p.K + (unsigned)(jw * 8)) * 2u;
   const float inv_w2 = 1.f / (float)W2;
   // ---- halo address table (LDS, built once per workgroup): the LDS-DMA requests of a halo refill were bound by their ADDRESS ARITHMETIC
   // (~35 instructions and two divergent branches per 1 KB piece: ~210 cycles a piece, 2.5 us per refill with cache-hot data as with cold,
@@ -351,9 +279,11 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
     g.y0 = (tin / geo.tiles_x) * geo.th; g.x0 = (tin % geo.tiles_x) << lw;
     return g;
   };
-  // weight K-step kt of tile g into stage st
-  auto issue_w = [&](const Tile& g, int kt, int st, int i) {
-    dma16(p.w, smem + st * WB + (wave + 8 * i) * 1024, woff[i], (unsigned)g.n0 * (unsigned)p.K * 2u + (unsigned)kt * 128u);
+  // this wave's pieces of weight K-step kt of tile g into stage st
+  auto issue_w = [&](const Tile& g, int kt, int st) {
+#pragma unroll
+    for (int i = 0; i < NWP; ++i)
+      dma16(p.w, smem + st * WB + (wave + 8 * i) * 1024, woff[i], (unsigned)g.n0 * (unsigned)p.K * 2u + (unsigned)kt * 128u);
   };
   auto issue_halo = [&](const Tile& g, int chunk, int nw) {     // nw = 4: waves 0 .. 3 (refill inside the K loop); 8: all waves (between tiles)
     // first stored pixel of the halo (logical (y0 - 1, x0 - 1); may lie in front of the image: those lanes are masked below)
@@ -377,8 +307,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
   };
   auto stage_first = [&](const Tile& g, int st, int slot) {   // everything a tile needs before its first K-step (all waves are between tiles here)
     issue_halo(g, 0, 8);
-#pragma unroll
-    for (int i = 0; i < NWP; ++i) issue_w(g, 0, st, i);
+    issue_w(g, 0, st);
     if (tid < BN) bias_base[slot * BN + tid] = (p.flags & CF_BIAS) ? p.bias[g.n0 + tid] : 0.f;
   };
 
@@ -386,7 +315,6 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
   int kg = 0;                                             // K-steps issued so far: K-step kt of the current tile lives in stage (kg + kt) & 1
   __syncthreads();                                      // the address table is complete
   stage_first(g, 0, 0);
-  bf16x8 wf[TN], xf[8];
   for (int it = 0;; ++it) {
     HP_STAMP(xs + t, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -398,54 +326,8 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
     for (int a = 0; a < 8; ++a)
 #pragma unroll
       for (int b = 0; b < TN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    int kt = 0;
-    for (int c = 0; c < chunks; ++c) {
-      if (c > 0) {
-        if (grp == 0) {
-          issue_halo(g, c, 4);
-          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-      }
-      for (int tp = 0; tp < 9; ++tp, ++kt) {
-        const int e = __builtin_amdgcn_readlane(v_taps, tp);
-        const int dy = ((e >> 6) & 63) - 32, dx = (e & 63) - 32;
-        const int tapoff = dy * W2 + dx;
-        const int st = (kg + kt) & 1;
-        const unsigned char* Bb = smem + st * WB;
-        const bool more = kt + 1 < KT;
-        const int xsw = (fr + 1 + dx) & 7;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-          for (int jn = 0; jn < TN; ++jn) {
-            const int row = wc * (TN * 16) + jn * 16 + fr;
-            wf[jn] = *(const bf16x8*)(Bb + row * 128 + (((fq + 4 * ks) ^ (row & 7)) << 4));
-          }
-#pragma unroll
-          for (int a = 0; a < 8; ++a) {
-            const int r = wr * 128 + a * 16 + fr;
-            const int hp = r + 2 * (r >> lw) + Wd + 3 + tapoff;
-            xf[a] = *(const bf16x8*)(halo + hp * 128 + (((fq + 4 * ks) ^ xsw) << 4));
-          }
-          if (ks == 0 && more) {
-#pragma unroll
-            for (int q = 0; q < NWP; ++q) issue_w(g, kt + 1, st ^ 1, q);
-          }
-          if (ks == 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-          for (int a = 0; a < 8; ++a)
-#pragma unroll
-            for (int jn = 0; jn < TN; ++jn)
-              acc[a][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[jn], xf[a], acc[a][jn], 0, 0, 0);
-          __builtin_amdgcn_s_setprio(0);
-          __builtin_amdgcn_s_barrier();
-        }
-      }
-    }
+    pp_halo_kloop<TN, WB, false>(acc, smem, halo, 0, chunks, kg, v_taps, lw, grp, wr, wc, fr, fq,
+                                 [&](int c) { issue_halo(g, c, 4); }, [&](int kt) { issue_w(g, kt, (kg + kt) & 1); });
     if (grp == 0) __builtin_amdgcn_s_barrier();         // balance the barrier count of the two groups: every LDS read of this tile has retired
     HP_STAMP(xs + t, 2);
     kg += KT;

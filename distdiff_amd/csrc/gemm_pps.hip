@@ -1,10 +1,13 @@
 // K2/K8 (pointwise layers) -- persistent ping-pong GEMM for 1x1 convolutions / linear layers, bf16 MFMA, gfx950: the phase-alternating
-// K loop of conv_halo.hip (its header says why) with both operands streamed, and the epilogue the two share (pp_epilogue.h).  Same packed
+// K loop of conv_halo.hip (its header says why) with both operands streamed: the K-step is pp_kstep of pp_kloop.h, which the halo kernels
+// run too, and the epilogue the one they share (pp_epilogue.h); this file keeps the persistent tile walk, the prefetch of the next tile's
+// first K-step and bias / c1 / statistics rows, and the GEGLU epilogue.  Same packed
 // weights, NHWC row layout and epilogue semantics as conv_gemm2.hip; launch_conv_gemm sends eligible shapes here (gemm_pp_config).
 #include "common.h"
 #include "conv_dispatch.h"
 #include "conv_epilogue.h"
 #include "pp_epilogue.h"
+#include "pp_kloop.h"
 
 namespace {
 
@@ -89,34 +92,18 @@ __global__ __launch_bounds__(512, 1) void gemm_pps_kernel(ConvGemmParams p) {
   const int fr = lane & 15, fq = lane >> 4;
   const int ntn = p.N / BN, tiles = (p.M / BM) * ntn;
   // this workgroup's tiles: first, first + per, ... (count of them) inside its XCD's contiguous range
-  int first, count;
-  const int per = gridDim.x >> 3;
-  {
-    const int q = tiles >> 3, r = tiles & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int xbase = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, xcount = q + (xcd < r ? 1 : 0);
-    first = xbase + slot;
-    count = slot < xcount ? (xcount - slot + per - 1) / per : 0;
-  }
+  const int per = gridDim.x >> 3, slot = blockIdx.x >> 3;
+  const XcdRange xr = xcd_tile_range(tiles, blockIdx.x);
+  const int first = xr.first + slot, count = slot < xr.count ? (xr.count - slot + per - 1) / per : 0;
   if (count == 0) return;
   const int KT = p.K >> 6;
   const int prow = lane >> 3, j = (lane & 7) ^ prow;
-  constexpr int TNP = TN & ~1;
   unsigned aoff[4], woff[TN];
 #pragma unroll
   for (int i = 0; i < 4; ++i) aoff[i] = ((unsigned)((wave + 8 * i) * 8 + prow) * (unsigned)p.x_ld + (unsigned)(j * 8)) * 2u;
 #pragma unroll
-  for (int i = 0; i < TN; ++i) {
-    const int R = (wave + 8 * i) * 8 + prow;             // MFMA-ordered row of the W stage -> weight row of the tile
-    const int wv = R / (TN * 16), q = R - wv * (TN * 16), jn = q >> 4, f = q & 15;
-    int ch;
-    if (GEGLU) {
-      const int c = (f >> 2) * 8 + (jn >> 1) * 4 + (f & 3);          // output column inside the wave's 32
-      ch = wv * 64 + (c >> 4) * 32 + (jn & 1) * 16 + (c & 15);
-    } else {
-      ch = jn < TNP ? wv * (TN * 16) + (jn >> 1) * 32 + (f >> 2) * 8 + (jn & 1) * 4 + (f & 3) : R;
-    }
-    woff[i] = ((unsigned)ch * (unsigned)p.K + (unsigned)(j * 8)) * 2u;
-  }
+  for (int i = 0; i < TN; ++i)                           // MFMA-ordered row of the W stage -> weight row of the tile
+    woff[i] = ((unsigned)pp_weight_row<TN, GEGLU>((wave + 8 * i) * 8 + prow) * (unsigned)p.K + (unsigned)(j * 8)) * 2u;
   // bias / c1 pieces of a tile: waves 0, 1 bring bias[n0 .. n0 + BN), waves 2, 3 c1 (256 floats per piece; absent rows read as zeros)
   const unsigned auxoff = (wave < 4 && (wave & 1) * 256 + lane * 4 < BN && ((wave < 2) ? (p.flags & CF_BIAS) : (p.flags & CF_LNFOLD)))
                               ? (unsigned)((wave & 1) * 256 + lane * 4) * 4u : 0xffffff00u;
@@ -141,7 +128,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pps_kernel(ConvGemmParams p) {
   for (int q = 0; q < NP; ++q) issue(xt, wsoff, 0, 0, q);
   issue_aux(m0, n0, 0);
   f32x4 acc[8][TN];
-  bf16x8 wf[TN], xf[8];
   for (int it = 0; it < count; ++it) {
     PPS_STAMP(tile, 0);
 #pragma unroll
@@ -168,38 +154,19 @@ __global__ __launch_bounds__(512, 1) void gemm_pps_kernel(ConvGemmParams p) {
       const bf16_t* nx = more ? xt : xtn;
       const unsigned nw = more ? wsoff : wsoffn;
       const int nk = more ? kt + 1 : 0;
+      // the last K-step leaves the next tile's first K-step in flight: only its LDS reads have to retire
+      pp_kstep<TN>(acc, Bb, Ab, wc, fr, fq,
+                   [&](int a) {
+                     const int row = wr * 128 + a * 16 + fr;
+                     return PpRow{row, row & 7};
+                   },
+                   [&] {
+                     if (!pre) return;
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {                  // two sections per K-step, one per K half (see conv_halo_kernel)
-#pragma unroll
-        for (int jn = 0; jn < TN; ++jn) {
-          const int row = wc * (TN * 16) + jn * 16 + fr;
-          wf[jn] = *(const bf16x8*)(Bb + row * 128 + (((fq + 4 * ks) ^ (row & 7)) << 4));
-        }
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-          const int row = wr * 128 + a * 16 + fr;
-          xf[a] = *(const bf16x8*)(Ab + row * 128 + (((fq + 4 * ks) ^ (row & 7)) << 4));
-        }
-        if (ks == 0 && pre) {
-#pragma unroll
-          for (int q = 0; q < NP; ++q) issue(nx, nw, nk, cur ^ 1, q);
-          if (!more) issue_aux(m0n, n0n, (it + 1) & 1);
-        }
-        if (ks == 1) {
-          if (more) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-          else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int a = 0; a < 8; ++a)
-#pragma unroll
-          for (int jn = 0; jn < TN; ++jn)
-            acc[a][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[jn], xf[a], acc[a][jn], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_s_barrier();
-      }
+                     for (int q = 0; q < NP; ++q) issue(nx, nw, nk, cur ^ 1, q);
+                     if (!more) issue_aux(m0n, n0n, (it + 1) & 1);
+                   },
+                   more);
       cur ^= 1;
     }
     if (wr == 0) __builtin_amdgcn_s_barrier();
