@@ -104,6 +104,8 @@ struct GroupNormParams {
   bf16_t* dx; int dx_ld;
   int accumulate;      // dx += result
 };
+// Both launchers return hipErrorInvalidValue in front of any launch (and of any division by G) for: G, C, HW or B <= 0, B > 65535 (the
+// images are the grid's y extent), C % 8, C % G, a row stride (x_ld, y_ld / dy_ld, dx_ld) that is no multiple of 8, chan_part with HW % 64.
 size_t groupnorm_scratch_bytes(int B, int G);
 hipError_t launch_groupnorm_fwd(const GroupNormParams& p, hipStream_t stream);
 hipError_t launch_groupnorm_bwd(const GroupNormParams& p, hipStream_t stream);
@@ -123,6 +125,8 @@ struct LayerNormParams {
   bf16_t* dx; int dx_ld;
   int accumulate;
 };
+// hipErrorInvalidValue in front of any launch for: M or C <= 0, C % 8, C > 2048, a row stride that is no multiple of 8 (y_ld only when y
+// is given); forward with neither y nor stats, row partials with spans < 1 or rowpart_ld < spans; backward without stats.
 hipError_t launch_layernorm_fwd(const LayerNormParams& p, hipStream_t stream);
 hipError_t launch_layernorm_bwd(const LayerNormParams& p, hipStream_t stream);
 

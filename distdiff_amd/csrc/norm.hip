@@ -466,7 +466,10 @@ static size_t gn_partial_lds(int C) {
   const int VC = C / 8, VCt = VC < GN_THREADS ? VC : GN_THREADS, R = GN_THREADS / VCt;
   return (size_t)R * 2 * C * sizeof(float);
 }
+// Refused in front of any launch (and of any division by G): empty or negative extents, more images than a grid's y extent holds, a
+// channel count that is no whole number of 8-channel vectors or of groups, a row stride that would misalign the 16-byte accesses.
 static hipError_t gn_check(const GroupNormParams& p) {
+  if (p.G <= 0 || p.C <= 0 || p.HW <= 0 || p.B <= 0 || p.B > 65535) return hipErrorInvalidValue;
   if (p.C % 8 || p.C % p.G || (p.x_ld & 7)) return hipErrorInvalidValue;
   return hipSuccess;
 }
@@ -484,7 +487,6 @@ static hipError_t gn_launch(const GroupNormParams& p, hipStream_t stream) {
   const int S = gn_split(p.HW, p.C);
   float* fin = p.scratch + (size_t)p.B * GN_MAX_SPLIT * p.G * 3;   // [B][G][2] finalize output of the backward sums
   if (!BWD && p.chan_part) {
-    if (p.HW & 63) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gn_finalize_chan_kernel, dim3(p.B * p.G), dim3(GN_THREADS), 0, stream, p);
   } else {
     hipLaunchKernelGGL((gn_partial_kernel<BWD>), dim3(S, p.B), dim3(GN_THREADS), gn_partial_lds(p.C), stream, p);
@@ -497,6 +499,7 @@ static hipError_t gn_launch(const GroupNormParams& p, hipStream_t stream) {
 
 hipError_t launch_groupnorm_fwd(const GroupNormParams& p, hipStream_t stream) {
   if (gn_check(p) != hipSuccess || (p.y_ld & 7)) return hipErrorInvalidValue;
+  if (p.chan_part && (p.HW & 63)) return hipErrorInvalidValue;     // the partials are per 64-row block
   return gn_launch<false>(p, stream);
 }
 
@@ -519,7 +522,7 @@ __global__ __launch_bounds__(256) void ln_rowpart_finalize_kernel(LayerNormParam
 }
 
 hipError_t launch_layernorm_fwd(const LayerNormParams& p, hipStream_t stream) {
-  if (p.C % 8 || p.C > 2048 || (p.x_ld & 7) || (p.y && (p.y_ld & 7))) return hipErrorInvalidValue;
+  if (p.M <= 0 || p.C <= 0 || p.C % 8 || p.C > 2048 || (p.x_ld & 7) || (p.y && (p.y_ld & 7))) return hipErrorInvalidValue;
   if (!p.y) {
     if (!p.stats) return hipErrorInvalidValue;
     if (p.rowpart) {
@@ -544,7 +547,7 @@ hipError_t launch_layernorm_fwd(const LayerNormParams& p, hipStream_t stream) {
 }
 
 hipError_t launch_layernorm_bwd(const LayerNormParams& p, hipStream_t stream) {
-  if (p.C % 8 || p.C > 2048 || (p.x_ld & 7) || (p.dy_ld & 7) || (p.dx_ld & 7) || !p.stats) return hipErrorInvalidValue;
+  if (p.M <= 0 || p.C <= 0 || p.C % 8 || p.C > 2048 || (p.x_ld & 7) || (p.dy_ld & 7) || (p.dx_ld & 7) || !p.stats) return hipErrorInvalidValue;
   hipLaunchKernelGGL((ln_kernel<true>), dim3((p.M + 3) / 4), dim3(256), 0, stream, p);
   return hipGetLastError();
 }

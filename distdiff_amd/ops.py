@@ -219,13 +219,15 @@ def conv_gemm_plan(x, pk, B, H, W, Ho, Wo, *args, **kw):
     return CONV_GEMM_KINDS[kind], form, out4[2]
 
 
-def groupnorm(x, gamma, beta, B, HW, G, eps, silu, dy=None, stats=None, chan_part=None, accumulate_into=None):
+def groupnorm(x, gamma, beta, B, HW, G, eps, silu, dy=None, stats=None, chan_part=None, accumulate_into=None, y=None, dx=None):
     """Forward (y, stats), or with dy the input-gradient dx.  accumulate_into: a dx buffer that already holds a gradient -- the result
-    is added to it in place (GroupNormParams.accumulate) and it is returned."""
+    is added to it in place (GroupNormParams.accumulate) and it is returned.  y / dx: write the forward result / the gradient there (a
+    column view of a wider buffer is fine) instead of into a fresh tensor."""
     Cc = x.shape[1]
     L = _lib.lib()
     p = GroupNormParams()
-    y = torch.empty_like(x)
+    if y is None:
+        y = torch.empty(x.shape, device=x.device, dtype=x.dtype)
     scratch = torch.empty((L.dd_op_groupnorm_scratch_bytes(B, G) // 4,), device=x.device, dtype=torch.float32)
     if stats is None:
         stats = torch.empty((B, G, 2), device=x.device, dtype=torch.float32)
@@ -237,7 +239,10 @@ def groupnorm(x, gamma, beta, B, HW, G, eps, silu, dy=None, stats=None, chan_par
     if dy is None:
         check(L.dd_op_groupnorm_fwd(C.byref(p), _stream()), "gn_fwd")
         return y, stats
-    dx = torch.empty_like(x) if accumulate_into is None else accumulate_into
+    if accumulate_into is not None:
+        dx = accumulate_into
+    elif dx is None:
+        dx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
     p.dy, p.dy_ld, p.dx, p.dx_ld, p.accumulate = _ptr(dy), dy.stride(0), _ptr(dx), dx.stride(0), int(accumulate_into is not None)
     check(L.dd_op_groupnorm_bwd(C.byref(p), _stream()), "gn_bwd")
     return dx
@@ -255,12 +260,13 @@ def layernorm_stats(x, eps, rowpart=None, spans=0):
     return stats
 
 
-def layernorm(x, gamma, beta, eps, dy=None, stats=None, accumulate_into=None):
-    """Forward (y, stats), or with dy the input-gradient dx; accumulate_into as for groupnorm (LayerNormParams.accumulate)."""
+def layernorm(x, gamma, beta, eps, dy=None, stats=None, accumulate_into=None, y=None, dx=None):
+    """Forward (y, stats), or with dy the input-gradient dx; accumulate_into, y and dx as for groupnorm (LayerNormParams.accumulate)."""
     M, Cc = x.shape
     L = _lib.lib()
     p = LayerNormParams()
-    y = torch.empty_like(x)
+    if y is None:
+        y = torch.empty(x.shape, device=x.device, dtype=x.dtype)
     if stats is None:
         stats = torch.empty((M, 2), device=x.device, dtype=torch.float32)
     p.x, p.x_ld, p.y, p.y_ld = _ptr(x), x.stride(0), _ptr(y), y.stride(0)
@@ -268,7 +274,10 @@ def layernorm(x, gamma, beta, eps, dy=None, stats=None, accumulate_into=None):
     if dy is None:
         check(L.dd_op_layernorm_fwd(C.byref(p), _stream()), "ln_fwd")
         return y, stats
-    dx = torch.empty_like(x) if accumulate_into is None else accumulate_into
+    if accumulate_into is not None:
+        dx = accumulate_into
+    elif dx is None:
+        dx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
     p.dy, p.dy_ld, p.dx, p.dx_ld, p.accumulate = _ptr(dy), dy.stride(0), _ptr(dx), dx.stride(0), int(accumulate_into is not None)
     check(L.dd_op_layernorm_bwd(C.byref(p), _stream()), "ln_bwd")
     return dx
