@@ -126,10 +126,24 @@ StepParams step_params(dd_engine* E, int k, int step_index) {
   p.stats = E->inst[k].rs_stats; p.part = E->rs_part;
   return p;
 }
+// the noise of a stochastic step (eta > 0): the caller's tensor [B,C,L,L], or generated inside the step kernel from (seed, unit id of
+// the row, stream 16 + step index) -- what dd_randn_units writes for that stream.  Neither: the eta = 0 step
+struct StepNoise {
+  const float* noise = nullptr; const uint64_t* unit_ids = nullptr; uint64_t seed = 0;
+  bool on() const { return noise || unit_ids; }
+};
 // x0_prev: x0 of step_index - 1 under DPM-Solver++(2M), or null; x0 may be null
-void sampler_step(dd_engine* E, int k, const float* z, int step_index, const float* x0_prev, float* z_prev, float* x0, hipStream_t s) {
+void sampler_step(dd_engine* E, int k, const float* z, int step_index, const float* x0_prev, float* z_prev, float* x0, hipStream_t s,
+                  const StepNoise& sn = StepNoise()) {
   StepParams p = step_params(E, k, step_index);
   p.z = z; p.z_prev = z_prev; p.x0_prev = x0_prev;
+  if (sn.on() && E->eta > 0.f && E->sigma[step_index] != 0.f) {     // sigma = 0 (a' = 1): d = sqrt(1-a'), the eta = 0 rows and kernel
+    p.coef = E->coef_table_eta + (size_t)step_index * 8; p.lin = E->step_table_eta + (size_t)step_index * 4;
+    p.x0 = x0; p.sigma = E->sigma[step_index]; p.noise = sn.noise;
+    p.rng_seed = sn.seed; p.rng_stream = DD_RNG_STEP_STREAM + step_index;
+    HIPCHK(launch_sampler_step_units(p, sn.unit_ids, s));
+    return;
+  }
   p.c2m = x0_prev ? E->c2m[step_index] : 0.f;
   // the second-order term needs x0 of this step: a caller that does not ask for it has it written to the instance's own buffer
   const bool second_order = x0_prev && p.c2m != 0.f;
@@ -144,15 +158,21 @@ bool history_refused(dd_engine* E, const float* x0_prev) {
   if (x0_prev && E->solver != 1) E->err = "x0_prev is the history of DPM-Solver++(2M): this schedule was set with solver 0 (DDIM)";
   return x0_prev && E->solver != 1;
 }
+// step noise is the input of a schedule set with eta > 0 alone
+bool noise_refused(dd_engine* E, const float* step_noise) {
+  if (step_noise && !(E->eta > 0.f)) E->err = "step_noise is the noise of a stochastic DDIM step: this schedule was set with eta = 0";
+  return step_noise && !(E->eta > 0.f);
+}
 
 // one guided forward step on instance k: z_in -> (z_next, x0, feat) ; energy accumulates into score, writes gfeat.  x0_prev: the
-// history of a DPM-Solver++(2M) step (direct guidance); it changes z_next alone, which the reverse pass does not differentiate there
+// history of a DPM-Solver++(2M) step, sn: the noise of a stochastic step (direct guidance); they change z_next alone, which the reverse
+// pass does not differentiate there
 void guided_forward(dd_engine* E, int k, const float* z_in, int step_index, const int* targets, int normalize, float weight,
-                    float* score, hipStream_t s, const float* x0_prev = nullptr) {
+                    float* score, hipStream_t s, const float* x0_prev = nullptr, const StepNoise& sn = StepNoise()) {
   const dd_config& c = E->cfg;
   auto& I = E->inst[k];
   unet_fwd(E, k, z_in, step_index, s);
-  sampler_step(E, k, z_in, step_index, x0_prev, I.z_next, I.x0, s);
+  sampler_step(E, k, z_in, step_index, x0_prev, I.z_next, I.x0, s, sn);
   vae_fwd(E, k, I.x0, s);
   guide_fwd_from_image(E, k, s);
   HIPCHK(launch_energy(I.feat, E->Pc, E->Pg, targets, c.max_batch, E->pD, E->pK, E->sp.gs, E->sp.ls, E->sp.use_global, E->sp.use_local,
@@ -384,6 +404,11 @@ int dd_set_schedule(dd_engine* E, const int* timesteps, int n, const float* alph
 
 int dd_set_schedule_s(dd_engine* E, const int* timesteps, int n, const float* alphas_cumprod, int num_train, float final_alpha,
                       const dd_sampler_params* sp, int solver) {
+  return dd_set_schedule_e(E, timesteps, n, alphas_cumprod, num_train, final_alpha, sp, solver, 0.f);
+}
+
+int dd_set_schedule_e(dd_engine* E, const int* timesteps, int n, const float* alphas_cumprod, int num_train, float final_alpha,
+                      const dd_sampler_params* sp, int solver, float eta) {
   if (!E || !timesteps || n < 1 || !alphas_cumprod || !sp) return DD_ERR_ARG;
   if (!E->finalized) { E->err = "finalize first"; return DD_ERR_STATE; }
   DD_TRY(E, {
@@ -391,7 +416,11 @@ int dd_set_schedule_s(dd_engine* E, const int* timesteps, int n, const float* al
     if (sp->prediction_type < 0 || sp->prediction_type > 2) throw std::runtime_error("prediction_type must be 0 (epsilon), 1 (v_prediction) or 2 (sample)");
     if (!(sp->guidance_rescale >= 0.f && sp->guidance_rescale <= 1.f)) throw std::runtime_error("guidance_rescale must be in [0, 1]");
     if (solver < 0 || solver > 1) throw std::runtime_error("solver must be 0 (DDIM) or 1 (DPM-Solver++(2M))");
+    if (!(eta >= 0.f && eta <= 1.f)) throw std::runtime_error("eta must be in [0, 1]");
+    if (eta > 0.f && solver != 0) throw std::runtime_error("eta > 0 is stochastic DDIM (solver 0): the SDE variant of DPM-Solver++ is another solver");
+    if (eta > 0.f && n > DD_RNG_STEP_STREAMS) throw std::runtime_error("eta > 0: at most " + std::to_string(DD_RNG_STEP_STREAMS) + " steps (one noise stream per step)");
     std::vector<float> coef((size_t)n * 8, 0.f), lin((size_t)n * 4, 0.f), c2m;
+    std::vector<float> coef_eta, lin_eta, sigma;          // eta > 0 only
     const int ratio = num_train / n;
     for (int i = 0; i < n; ++i) {
       const int t = timesteps[i], prev = t - ratio;
@@ -403,6 +432,14 @@ int dd_set_schedule_s(dd_engine* E, const int* timesteps, int n, const float* al
       if (sampler_step_coefs(sp->prediction_type, a, ap, &lin[(size_t)i * 4]))      // the division form of the step divides by sqrt(a) as well
         throw std::runtime_error(sp->prediction_type == 0 ? "epsilon-prediction with alphas_cumprod = 0 at timestep " + std::to_string(t) +
                                  " (zero terminal SNR): x0 is undefined there" : "sample-prediction with alphas_cumprod = 1 at timestep " + std::to_string(t));
+      if (eta > 0.f) {
+        float o[5];
+        if (sampler_step_coefs_eta(sp->prediction_type, a, ap, eta, o)) throw std::runtime_error("eta > 0: the step at timestep " + std::to_string(t) + " has no finite sigma");
+        coef_eta.insert(coef_eta.end(), q, q + 8);
+        coef_eta[(size_t)i * 8 + 4] = sampler_step_eta_d(a, ap, eta);
+        lin_eta.insert(lin_eta.end(), o, o + 4);
+        sigma.push_back(o[4]);
+      }
     }
     // every refusal is above: from here on the engine's schedule is replaced
     E->timesteps.assign(timesteps, timesteps + n);
@@ -412,6 +449,16 @@ int dd_set_schedule_s(dd_engine* E, const int* timesteps, int n, const float* al
     for (void* q : E->sched_allocs) E->dfree(q);
     E->sched_allocs.clear();
     E->c2m = c2m;
+    E->eta = eta; E->sigma = sigma;
+    E->coef_table_eta = nullptr; E->step_table_eta = nullptr;
+    if (eta > 0.f) {
+      E->step_table_eta = (float*)E->dmalloc(lin_eta.size() * 4, false);
+      E->sched_allocs.push_back(E->step_table_eta);
+      HIPCHK(hipMemcpy(E->step_table_eta, lin_eta.data(), lin_eta.size() * 4, hipMemcpyHostToDevice));
+      E->coef_table_eta = (float*)E->dmalloc(coef_eta.size() * 4, false);
+      E->sched_allocs.push_back(E->coef_table_eta);
+      HIPCHK(hipMemcpy(E->coef_table_eta, coef_eta.data(), coef_eta.size() * 4, hipMemcpyHostToDevice));
+    }
     E->x0_hist = nullptr;
     if (solver == 1) {
       E->x0_hist = (float*)E->dmalloc((size_t)c.max_batch * std::max({c.unet_in_channels, c.unet_out_channels, c.vae_latent_channels}) *
@@ -555,24 +602,37 @@ int dd_unet_forward(dd_engine* E, const float* z, int step_index, float* eps2_ou
 
 // the launch sequence of one plain step: UNet forward (no stash) + CFG + scheduler step (x0_prev: the history of a DPM-Solver++(2M) step)
 static void denoise_step_enqueue(dd_engine* E, const float* z, int step_index, const float* x0_prev, float* z_prev_out, float* x0_out,
-                                 hipStream_t s) {
+                                 hipStream_t s, const StepNoise& sn) {
   unet_fwd(E, 0, z, step_index, s, /*stash=*/false);
-  sampler_step(E, 0, z, step_index, x0_prev, z_prev_out, x0_out, s);
+  sampler_step(E, 0, z, step_index, x0_prev, z_prev_out, x0_out, s, sn);
 }
 
 int dd_denoise_step(dd_engine* E, const float* z, int step_index, float* z_prev_out, float* x0_out, int B, void* stream) {
   return dd_denoise_step_h(E, z, step_index, nullptr, z_prev_out, x0_out, B, stream);
 }
 
-int dd_denoise_step_h(dd_engine* E, const float* z, int step_index, const float* x0_prev, float* z_prev_out, float* x0_out, int B,
-                      void* stream) {
+// one plain step with its optional inputs: the history (solver 1) or the noise (eta > 0); the public calls and dd_expand's loop are this
+static int denoise_step_call(dd_engine* E, const float* z, int step_index, const float* x0_prev, const StepNoise& sn, float* z_prev_out,
+                             float* x0_out, int B, void* stream) {
   if (!E || !z || !z_prev_out) return DD_ERR_ARG;
-  if (history_refused(E, x0_prev)) return DD_ERR_STATE;
+  if (history_refused(E, x0_prev) || noise_refused(E, sn.noise)) return DD_ERR_STATE;
   DD_TRY(E, {
     check_batch(E, B);
     if (step_index < 0 || step_index >= (int)E->timesteps.size()) throw std::runtime_error("step_index out of range");
-    denoise_step_enqueue(E, z, step_index, x0_prev, z_prev_out, x0_out, (hipStream_t)stream);
+    denoise_step_enqueue(E, z, step_index, x0_prev, z_prev_out, x0_out, (hipStream_t)stream, sn);
   });
+}
+
+int dd_denoise_step_h(dd_engine* E, const float* z, int step_index, const float* x0_prev, float* z_prev_out, float* x0_out, int B,
+                      void* stream) {
+  return denoise_step_call(E, z, step_index, x0_prev, StepNoise(), z_prev_out, x0_out, B, stream);
+}
+
+int dd_denoise_step_n(dd_engine* E, const float* z, int step_index, const float* step_noise, float* z_prev_out, float* x0_out, int B,
+                      void* stream) {
+  StepNoise sn;
+  sn.noise = step_noise;
+  return denoise_step_call(E, z, step_index, nullptr, sn, z_prev_out, x0_out, B, stream);
 }
 
 int dd_decode(dd_engine* E, const float* z, float* image_out, int denormalize, int B, void* stream) {
@@ -706,10 +766,25 @@ int dd_direct_guidance(dd_engine* E, const float* z, const int* targets, int ste
   return dd_direct_guidance_h(E, z, targets, step_index, nullptr, z_next_out, x0_out, score_out, grad_z_out, B, stream);
 }
 
+static int direct_guidance_call(dd_engine* E, const float* z, const int* targets, int step_index, const float* x0_prev, const StepNoise& sn,
+                                float* z_next_out, float* x0_out, float* score_out, float* grad_z_out, int B, void* stream);
 int dd_direct_guidance_h(dd_engine* E, const float* z, const int* targets, int step_index, const float* x0_prev, float* z_next_out,
                          float* x0_out, float* score_out, float* grad_z_out, int B, void* stream) {
+  return direct_guidance_call(E, z, targets, step_index, x0_prev, StepNoise(), z_next_out, x0_out, score_out, grad_z_out, B, stream);
+}
+
+int dd_direct_guidance_n(dd_engine* E, const float* z, const int* targets, int step_index, const float* step_noise, float* z_next_out,
+                         float* x0_out, float* score_out, float* grad_z_out, int B, void* stream) {
+  StepNoise sn;
+  sn.noise = step_noise;
+  return direct_guidance_call(E, z, targets, step_index, nullptr, sn, z_next_out, x0_out, score_out, grad_z_out, B, stream);
+}
+
+// direct guidance with its optional inputs, as denoise_step_call
+static int direct_guidance_call(dd_engine* E, const float* z, const int* targets, int step_index, const float* x0_prev, const StepNoise& sn,
+                                float* z_next_out, float* x0_out, float* score_out, float* grad_z_out, int B, void* stream) {
   if (!E || !z || !targets || !z_next_out) return DD_ERR_ARG;
-  if (history_refused(E, x0_prev)) return DD_ERR_STATE;
+  if (history_refused(E, x0_prev) || noise_refused(E, sn.noise)) return DD_ERR_STATE;
   DD_TRY(E, {
     check_batch(E, B);
     const dd_config& c = E->cfg;
@@ -722,7 +797,7 @@ int dd_direct_guidance_h(dd_engine* E, const float* z, const int* targets, int s
     HIPCHK(hipMemsetAsync(score, 0, sizeof(float), s));
     HIPCHK(hipMemsetAsync(E->image_scores, 0, (size_t)B * sizeof(float), s));
     HIPCHK(hipMemcpyAsync(E->inst[0].z_in, z, n * 4, hipMemcpyDeviceToDevice, s));
-    guided_forward(E, 0, E->inst[0].z_in, step_index, targets, 1, 1.f, score, s, x0_prev);
+    guided_forward(E, 0, E->inst[0].z_in, step_index, targets, 1, 1.f, score, s, x0_prev, sn);
     float* g_z = E->f32_tmp[0];
     guided_backward(E, 0, step_index, nullptr, g_z, E->f32_tmp[2], s);
     if (grad_z_out) HIPCHK(hipMemcpyAsync(grad_z_out, g_z, n * 4, hipMemcpyDeviceToDevice, s));
@@ -742,7 +817,7 @@ static void philox_units_enqueue(uint64_t seed, int rng_stream, const uint64_t* 
 }
 
 int dd_randn_units(dd_engine* E, uint64_t seed, int rng_stream, const uint64_t* unit_ids, int B, int64_t n_per_unit, float* out, void* stream) {
-  if (!E || !unit_ids || !out || B < 1 || n_per_unit < 1 || rng_stream < 0 || rng_stream > 3) return DD_ERR_ARG;
+  if (!E || !unit_ids || !out || B < 1 || n_per_unit < 1 || !rng_stream_ok(rng_stream)) return DD_ERR_ARG;
   DD_TRY(E, { philox_units_enqueue(seed, rng_stream, unit_ids, B, n_per_unit, out, (hipStream_t)stream); });
 }
 
@@ -778,6 +853,12 @@ int dd_expand(dd_engine* E, const dd_expand_args* a, void* stream) {
   const int n = (int)E->timesteps.size();
   if (a->start_index < 0 || a->start_index >= n) { E->err = "start_index out of range"; return DD_ERR_ARG; }
   if (a->text_to_img && a->start_index != 0) { E->err = "text_to_img runs the whole schedule: start_index must be 0"; return DD_ERR_ARG; }
+  // eta > 0: the noise of step i of row k is generated from (seed, unit_ids[k], stream 16 + i) in either noise_mode
+  StepNoise sn;
+  if (E->eta > 0.f) {
+    if (!a->unit_ids) { E->err = "this schedule was set with eta > 0: dd_expand needs unit_ids (with seed they key the noise of every step)"; return DD_ERR_ARG; }
+    sn.unit_ids = a->unit_ids; sn.seed = a->seed;
+  }
   const float* ch_e = a->e;
   const float* ch_b = a->b;
   int rc;
@@ -811,11 +892,11 @@ int dd_expand(dd_engine* E, const dd_expand_args* a, void* stream) {
       rc = dd_transform_guidance(E, cur, a->targets, ch_e, ch_b, a->guide_first, a->guide_count, nxt, a->score_out, nullptr, a->B, stream);
       if (rc) return rc;
       std::swap(cur, nxt);
-      rc = dd_denoise_step_h(E, cur, i, nullptr, nxt, keep, a->B, stream);
+      rc = denoise_step_call(E, cur, i, nullptr, sn, nxt, keep, a->B, stream);
     } else if (a->guidance_type == 2 && i >= a->guide_first && i < a->guide_first + a->guide_count) {
-      rc = dd_direct_guidance_h(E, cur, a->targets, i, h, nxt, keep, a->score_out, nullptr, a->B, stream);
+      rc = direct_guidance_call(E, cur, a->targets, i, h, sn, nxt, keep, a->score_out, nullptr, a->B, stream);
     } else {
-      rc = dd_denoise_step_h(E, cur, i, h, nxt, keep, a->B, stream);
+      rc = denoise_step_call(E, cur, i, h, sn, nxt, keep, a->B, stream);
     }
     if (rc) return rc;
     hist = keep;

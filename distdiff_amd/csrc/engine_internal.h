@@ -273,6 +273,12 @@ struct dd_engine {
   float* step_table = nullptr;   // [n][4]: A_z, A_m, B_z, B_m of the linear step form (v_prediction / sample models, CFG rescale)
   std::vector<float> c2m;        // DPM-Solver++(2M) only: c_i of every step (host; the kernel takes it by value), empty under DDIM
   float* x0_hist = nullptr;      // DPM-Solver++(2M) only: dd_expand's history, x0 of the previous step [B,C,L,L] (in sched_allocs)
+  // eta > 0 only (dd_set_schedule_e; all empty / null under eta = 0): sigma_i of every step (host; the kernel takes it by value) and the
+  // rows the stochastic steps read in place of coef_table / step_table -- sqrt(1-a_prev) and B_z, B_m with d (sampler_step_coefs_eta).
+  // step_params() keeps pointing at the eta = 0 tables: transform guidance's chained steps and every backward stay deterministic
+  std::vector<float> sigma;
+  float* coef_table_eta = nullptr; float* step_table_eta = nullptr;
+  float eta = 0.f;
   float* rs_part = nullptr;      // CFG rescale: block partials of the per-image reductions (scratch, consumed by the next kernel)
   dd_sampler_params sp{};
   int solver = 0;                // dd_set_schedule_s: 0 DDIM, 1 DPM-Solver++(2M)

@@ -203,7 +203,17 @@ hipError_t launch_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int
 //                                scratch of sampler_step_scratch_floats(B, HW) floats; the backward re-reads m2 of that step
 //   x0_prev != null and c2m != 0 DPM-Solver++(2M), forward only (the guidance calls differentiate x0, which does not depend on the
 //                                history): x0 is required and always written, and may alias x0_prev.  Otherwise x0_prev is not read
+//   sigma != 0 and a noise source stochastic DDIM (eta > 0; forward only): coef / lin are the eta rows (sampler_step_coefs_eta: sqrt(1-a')
+//                                becomes d) and z' gains sigma n, n ~ N(0,1) per element: read from `noise` when it is given, otherwise
+//                                generated in registers when rng_count > 0 -- element j = ch * HW + pix of row b takes lane j & 3 of Philox
+//                                block j >> 2 of (rng_seed, rng_stream, unit id of row b - rng_row0), the bits launch_philox_units writes.
+//                                The generated form steps rows [rng_row0, rng_row0 + rng_count) alone, rng_count <= DD_RNG_UNITS ids per
+//                                launch: a larger batch is several launches over row ranges in order, and the one with rng_row0 == 0
+//                                computes the statistics of phi != 0 for the whole batch.  Not with a history.
+//                                With sigma == 0 or no source: the step above, nothing of this block is read.
 // ld: a multiple of 8; C <= 8; B <= 65535; anything else is hipErrorInvalidValue in front of any launch.  No atomics: bitwise deterministic.
+#define DD_RNG_UNITS 16
+struct RngUnits { unsigned lo[DD_RNG_UNITS], hi[DD_RNG_UNITS]; };
 struct StepParams {
   const float* m2; int ld;             // model output, fp32 NHWC rows [2B*HW, ld], unconditional half first
   const float* z;                      // NCHW fp32 [B, C, HW], as x0_prev, z_prev and x0
@@ -214,13 +224,24 @@ struct StepParams {
   const float* lin;                    // device: {A_z, A_m, B_z, B_m} (sampler_step_coefs)
   int prediction_type; float phi;      // 0 epsilon, 1 v_prediction, 2 sample; CFG rescale
   float* stats; float* part;
+  const float* noise; float sigma;     // eta > 0: explicit step noise NCHW fp32 [B, C, HW] (or null: generated) and sigma of this step
+  uint64_t rng_seed; int rng_stream;   // the generated form: Philox key and stream (16 + step index)
+  RngUnits rng_ids; int rng_count, rng_row0;
 };
 int sampler_step_coefs(int prediction_type, double a, double a_prev, float* out4);      // host; -1: unknown type or a singular step
+// {A_z, A_m, B_z, B_m, sigma} of the DDIM step with eta in [0, 1] (diffusers DDIMScheduler.step): sigma = eta sqrt((1-a')/(1-a) (1-a/a')),
+// d = sqrt(max(0, 1 - a' - sigma^2)) takes the place of sqrt(1-a') in B_z / B_m.  Host, double; -1 as above, for eta outside [0, 1] and
+// for a result that is not finite.  eta = 0: the four floats of sampler_step_coefs bit for bit and sigma = 0.0f.
+int sampler_step_coefs_eta(int prediction_type, double a, double a_prev, double eta, float* out5);
+float sampler_step_eta_d(double a, double a_prev, double eta);      // d of that step, rounded once: coef[4] of the division form
 size_t sampler_step_scratch_floats(int B, int HW);
 // c = sampler_step_coef_2m(i, n, a at step i - 1, a at step i, a at its previous timestep), host, double; exactly 0 for the first and
 // the last step and wherever it is undefined
 float sampler_step_coef_2m(int i, int n, double a_before, double a, double a_prev);
 hipError_t launch_sampler_step(const StepParams& p, hipStream_t s);
+// the generated form for a whole batch: unit_ids HOST [p.B], read before the call returns; DD_RNG_UNITS rows per launch (p.rng_ids,
+// rng_count and rng_row0 are filled here).  With sigma == 0 this is launch_sampler_step(p).
+hipError_t launch_sampler_step_units(const StepParams& p, const uint64_t* unit_ids, hipStream_t s);
 // VJP of step p in (x0, z'): g_x0, g_zprev NCHW fp32 (either may be null) -> g_z NCHW fp32 (the direct path) and g_m2, bf16 NHWC rows
 // [2B*HW, ld] with every column written (padding = 0).  p.z, p.x0_prev, p.z_prev and p.x0 are not used.  See DESIGN.md / SURVEY appendix A
 hipError_t launch_sampler_step_bwd(const StepParams& p, const float* g_x0, const float* g_zprev, bf16_t* g_m2, float* g_z, hipStream_t s);
@@ -234,12 +255,14 @@ hipError_t launch_mask_bf16(const bf16_t* dy, int ldd, const bf16_t* mask, int l
 hipError_t launch_axpby(const float* x, const float* n, float* out, size_t count, const float* coef_dev, hipStream_t s);
 // Counter-based noise (rng.hip): Philox4x32-10, key = seed, counter = (j / 4, rng_stream, unit id lo, unit id hi) for element j of a
 // unit; up to DD_RNG_UNITS unit ids travel in the kernel arguments (nothing of the caller's is referenced after the launch).
-//   launch_philox_units    : out [count, n_per_unit] = the values of `rng_stream` (0, 1, 3: N(0,1) by Box-Muller; 2: U[0,1))
+//   launch_philox_units    : out [count, n_per_unit] = the values of `rng_stream` (0, 1, 3: N(0,1) by Box-Muller; 2: U[0,1);
+//                            DD_RNG_STEP_STREAM + i: N(0,1), the noise of step i under eta > 0; 4-15 reserved and refused)
 //   launch_philox_add_noise: out [count, C, HW] = sa * x + sb * (n + 0.1 * o_c) with n from stream 0 and, when offset_noise, o_c from
 //                            stream 1 at channel c; coef_dev = {sa, sb} as launch_axpby -- bit for bit what launch_axpby gives on the
 //                            tensors of launch_philox_units
-#define DD_RNG_UNITS 16
-struct RngUnits { unsigned lo[DD_RNG_UNITS], hi[DD_RNG_UNITS]; };
+#define DD_RNG_STEP_STREAM 16
+#define DD_RNG_STEP_STREAMS 4096
+inline bool rng_stream_ok(int st) { return (st >= 0 && st <= 3) || (st >= DD_RNG_STEP_STREAM && st < DD_RNG_STEP_STREAM + DD_RNG_STEP_STREAMS); }
 hipError_t launch_philox_units(const RngUnits& ids, int count, uint64_t seed, int rng_stream, int64_t n_per_unit, float* out, hipStream_t s);
 hipError_t launch_philox_add_noise(const RngUnits& ids, int count, uint64_t seed, const float* x, float* out, int C, int HW, int offset_noise,
                                    const float* coef_dev, hipStream_t s);

@@ -2,47 +2,16 @@
 // of a unit (train image, expand index) depends on nothing else -- not on the row of the batch, the batch size, the grid or the call.
 //   key     = (seed lo, seed hi)
 //   counter = (j / 4, stream, unit id lo, unit id hi) for element j of the unit's tensor: one 128-bit block per 4 outputs
-//   streams : 0 initial noise [C,L,L], 1 offset noise [C], 3 b [4] -- N(0,1);  2 e [4] -- U[0,1)
+//   streams : 0 initial noise [C,L,L], 1 offset noise [C], 3 b [4] -- N(0,1);  2 e [4] -- U[0,1);  16 + i the noise of step i of the
+//             schedule under eta > 0 [C,L,L] -- N(0,1) (sampler_step.hip generates the same values in registers); 4-15 reserved
 // Normals by Box-Muller from the word pairs (w0,w1) and (w2,w3); uniforms (w >> 8) * 2^-24.
 // This file is built with -ffp-contract=off (build.py): every product and sum below is rounded on its own, because the fused first op
 // of the loop has to give the bits of the two-kernel path (dd_randn_units, then add_noise) that the parity tests cover.
 #include "common.h"
 #include "kernels.h"
+#include "philox.h"
 
 namespace {
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c.x, p1 = 0xCD9E8D57ull * c.z;
-    c = make_uint4((unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0);
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
-// u1 = (wa + 0.5) 2^-32 in (0,1), u2 = (wb + 0.5) 2^-32.  In the upper half u1 would round to 1 in fp32 and lose the small radii:
-// ln u1 = log1p(-(1 - u1)) there, with 1 - u1 = (~wa + 0.5) 2^-32 exact to one rounding.  Library logf / log1pf / sincospif (a few
-// ulp), not the fast intrinsics: the tails are what this generator is for.
-__device__ __forceinline__ void box_muller(unsigned wa, unsigned wb, float& n0, float& n1) {
-  const float l = (wa & 0x80000000u) ? log1pf(-(((float)(~wa) + 0.5f) * 0x1p-32f)) : logf(((float)wa + 0.5f) * 0x1p-32f);
-  const float r = sqrtf(-2.f * l);
-  float sn, cs;
-  sincospif(((float)wb + 0.5f) * 0x1p-31f, &sn, &cs);
-  n0 = r * cs;
-  n1 = r * sn;
-}
-
-__device__ __forceinline__ void block_values(unsigned q, int rng_stream, unsigned id_lo, unsigned id_hi, unsigned k0, unsigned k1, float v[4]) {
-  const uint4 w = philox4x32_10(make_uint4(q, (unsigned)rng_stream, id_lo, id_hi), k0, k1);
-  if (rng_stream == 2) {
-    v[0] = (float)(w.x >> 8) * 0x1p-24f; v[1] = (float)(w.y >> 8) * 0x1p-24f;
-    v[2] = (float)(w.z >> 8) * 0x1p-24f; v[3] = (float)(w.w >> 8) * 0x1p-24f;
-  } else {
-    box_muller(w.x, w.y, v[0], v[1]);
-    box_muller(w.z, w.w, v[2], v[3]);
-  }
-}
 
 // FUSED = false: out[u, j] = value j of unit u in `rng_stream`.
 // FUSED = true : out[u, j] = sa * x[u, j] + sb * (n_j + 0.1 * o_c), n from stream 0, o_c from stream 1 at channel c = j / HW when
@@ -85,7 +54,7 @@ __global__ void philox_units_kernel(RngUnits ids, unsigned k0, unsigned k1, int 
 
 hipError_t launch(bool fused, const RngUnits& ids, int count, uint64_t seed, int rng_stream, int64_t n, float* out, const float* x,
                   const float* coef, int HW, int offset_noise, hipStream_t s) {
-  if (count < 1 || count > DD_RNG_UNITS || n < 1 || rng_stream < 0 || rng_stream > 3) return hipErrorInvalidValue;
+  if (count < 1 || count > DD_RNG_UNITS || n < 1 || !rng_stream_ok(rng_stream)) return hipErrorInvalidValue;
   const long long nq = (n + 3) / 4;
   const dim3 grid((unsigned)((nq + 255) / 256), (unsigned)count);
   const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);

@@ -1,9 +1,9 @@
 // The sampler step (gfx950): classifier-free-guidance mix, optional CFG rescale (Lin et al. 2023; diffusers rescale_noise_cfg), the
-// scheduler update (diffusers DDIMScheduler.step, eta = 0; DPMSolverMultistepScheduler: dpmsolver++, order 2, midpoint) and its VJP.
+// scheduler update (diffusers DDIMScheduler.step, eta in [0, 1]; DPMSolverMultistepScheduler: dpmsolver++, order 2, midpoint) and its VJP.
 // One forward kernel template, one backward kernel template, one launcher each; the modes are listed at StepParams in kernels.h.
 //
 //   m  = u + s (c - u),  m^ = k_b m  (k_b = phi sigma_c / sigma_m + 1 - phi per image; 1 without rescale)
-//   x0 = A_z z + A_m m^,  z' = B_z z + B_m m^ [+ c2m (x0 - x0_prev)]
+//   x0 = A_z z + A_m m^,  z' = B_z z + B_m m^ [+ c2m (x0 - x0_prev)] [+ sigma n]
 //
 // One thread per pixel: both CFG halves of the 8-wide fp32 NHWC row come in as 16-byte loads, the NCHW reads and writes are coalesced
 // along the pixels.  grid = (ceil(HW / 256), B).  No atomics: bitwise deterministic.
@@ -12,10 +12,13 @@
 // __builtin_fmaf, so which results are rounded once and which twice is a statement of this file.  Each form is the one the kernel
 // that first served that mode happened to compile to (the former kernel is named at the line); tests/test_sampler_step_bits_gpu.py
 // holds their bits.  Do not "simplify" a * b + c * d into an fma or the reverse: it changes the latents of every image.
+// The noise term of eta > 0 is zp = (b0 * t + b1 * m) + sigma * n: the no-history expression on the eta tables, then the product rounded,
+// then the sum rounded, no fma -- what torch gives for z'(noise = 0) + sigma * n in fp32 (tests/test_ddim_eta_gpu.py).
 #include <cmath>
 
 #include "common.h"
 #include "kernels.h"
+#include "philox.h"
 
 namespace {
 
@@ -30,11 +33,14 @@ __device__ __forceinline__ void load_row8(const float* p, int C, float* v) {
 // EPS: (epsilon, no rescale) in the division form on the five-float row coef = {s, sqrt a, sqrt(1-a), sqrt a', sqrt(1-a')}:
 //   x0 = (z - sqrt(1-a) m) / sqrt a,  z' = sqrt a' x0 + sqrt(1-a') m
 // otherwise the linear form on lin = {A_z, A_m, B_z, B_m} (sampler_step_coefs).  HIST adds c2m (x0 - x0_prev) and always writes x0,
-// which may alias x0_prev: each thread reads its own element before it writes it.
-template <bool EPS, bool HIST>
+// which may alias x0_prev: each thread reads its own element before it writes it.  NOISE (never with HIST) adds sigma n on the eta rows
+// of coef / lin and steps rows rng_row0 + blockIdx.y: n is read from p.noise, or is lane j & 3 of Philox block j >> 2 of the row's unit,
+// j = ch * HW + pix -- one thread per pixel as before, so each thread computes the block of each of its elements (and its neighbours
+// compute it again: 4x the Philox work of rng.hip, microseconds against the UNet) and the Box-Muller of the one word pair it needs.
+template <bool EPS, bool HIST, bool NOISE>
 __global__ __launch_bounds__(STEP_THREADS) void sampler_step_kernel(const StepParams p) {
 #pragma clang fp contract(off)
-  const int b = blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
+  const int b = NOISE ? p.rng_row0 + blockIdx.y : blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
   if (pix >= p.HW) return;
   const float s = p.coef[0];
   // EPS: {sqrt a, sqrt(1-a)} and {sqrt a', sqrt(1-a')}, the latter on (x0, m); linear: {A_z, A_m} and {B_z, B_m}, on (z, m^)
@@ -60,6 +66,20 @@ __global__ __launch_bounds__(STEP_THREADS) void sampler_step_kernel(const StepPa
       // both instantiations); without, both products rounded, then added (cfg_ddim_kernel and sampler_step_kernel)
       if (HIST) zp = __builtin_fmaf(b0, t, b1 * m) + p.c2m * (x - xp);
       else zp = b0 * t + b1 * m;
+      if (NOISE) {
+        float n;
+        if (p.noise) {
+          n = p.noise[zi];
+        } else {
+          const unsigned j = (unsigned)ch * (unsigned)p.HW + (unsigned)pix;
+          const uint4 w = philox4x32_10(make_uint4(j >> 2, (unsigned)p.rng_stream, p.rng_ids.lo[blockIdx.y], p.rng_ids.hi[blockIdx.y]),
+                                        (unsigned)p.rng_seed, (unsigned)(p.rng_seed >> 32));
+          float n0, n1;
+          box_muller((j & 2) ? w.z : w.x, (j & 2) ? w.w : w.y, n0, n1);
+          n = (j & 1) ? n1 : n0;
+        }
+        zp = zp + p.sigma * n;
+      }
       if (HIST || p.x0) p.x0[zi] = x;
       p.z_prev[zi] = zp;
     }
@@ -233,8 +253,8 @@ bool step_args_ok(const StepParams& p, bool eps) {
 
 // the four step coefficients in double (B_m = sqrt(1-a') sqrt(a) - sqrt(a') sqrt(1-a) cancels here and not in fp32); the v-prediction
 // form never divides by sqrt(a): a zero-terminal-SNR table has a = 0 exactly at its first trailing step
-int sampler_step_coefs(int prediction_type, double a, double ap, float* out4) {
-  const double sa = sqrt(a), sb = sqrt(1 - a), sap = sqrt(ap), sbp = sqrt(1 - ap);
+static int step_coefs_d(int prediction_type, double a, double ap, double sbp, float* out4) {
+  const double sa = sqrt(a), sb = sqrt(1 - a), sap = sqrt(ap);
   double Az, Am, Bz, Bm;
   if (prediction_type == 0) {
     if (!(a > 0)) return -1;
@@ -249,6 +269,30 @@ int sampler_step_coefs(int prediction_type, double a, double ap, float* out4) {
   }
   out4[0] = (float)Az; out4[1] = (float)Am; out4[2] = (float)Bz; out4[3] = (float)Bm;
   return 0;
+}
+int sampler_step_coefs(int prediction_type, double a, double ap, float* out4) { return step_coefs_d(prediction_type, a, ap, sqrt(1 - ap), out4); }
+// eta in [0, 1]: the direction term keeps d = sqrt(max(0, 1 - a' - sigma^2)) of the noise level 1 - a' and sigma^2 goes to fresh noise.
+// The max is needed: at a = 0 (the first trailing step of a zero-terminal-SNR table) eta = 1 gives 1 - a' - sigma^2 ~ 1e-16 of either
+// sign.  eta = 0 takes sigma = 0 without evaluating the variance: d is then sqrt(1 - a') and the floats are those of sampler_step_coefs.
+static void eta_sigma_d(double a, double ap, double eta, double* sigma, double* d) {
+  *sigma = eta > 0 ? eta * sqrt((1 - ap) / (1 - a) * (1 - a / ap)) : 0.0;
+  const double d2 = 1 - ap - *sigma * *sigma;
+  *d = sqrt(d2 > 0 ? d2 : 0.0);
+}
+int sampler_step_coefs_eta(int prediction_type, double a, double ap, double eta, float* out5) {
+  if (!(eta >= 0 && eta <= 1)) return -1;
+  double sigma, d;
+  eta_sigma_d(a, ap, eta, &sigma, &d);
+  if (step_coefs_d(prediction_type, a, ap, d, out5)) return -1;
+  out5[4] = (float)sigma;
+  for (int k = 0; k < 5; ++k)
+    if (!std::isfinite(out5[k])) return -1;
+  return 0;
+}
+float sampler_step_eta_d(double a, double ap, double eta) {
+  double sigma, d;
+  eta_sigma_d(a, ap, eta, &sigma, &d);
+  return (float)d;
 }
 size_t sampler_step_scratch_floats(int B, int HW) { return (size_t)B * ((HW + STEP_THREADS - 1) / STEP_THREADS) * 8; }
 
@@ -270,15 +314,42 @@ hipError_t launch_sampler_step(const StepParams& p, hipStream_t s) {
   const bool eps = p.prediction_type == 0 && p.phi == 0.f;
   const bool hist = p.x0_prev && p.c2m != 0.f;              // otherwise the first-order step: the history is not read
   if (!step_args_ok(p, eps) || (hist && (!p.x0 || !std::isfinite(p.c2m)))) return hipErrorInvalidValue;
+  // eta > 0: sigma != 0 and a noise source, the tensor or (rng_count > 0) the generator on rows [rng_row0, rng_row0 + rng_count)
+  if (!std::isfinite(p.sigma) || p.rng_count < 0 || p.rng_count > DD_RNG_UNITS) return hipErrorInvalidValue;
+  const bool noise = p.sigma != 0.f && (p.noise || p.rng_count > 0), generated = noise && !p.noise;
+  if (noise && hist) return hipErrorInvalidValue;
+  // the kernel draws normals: stream 2 (e) is uniform in launch_philox_units and would not be its tensor here
+  if (generated && (p.rng_row0 < 0 || p.rng_row0 + p.rng_count > p.B || !rng_stream_ok(p.rng_stream) || p.rng_stream == 2)) return hipErrorInvalidValue;
   const dim3 grid((p.HW + STEP_THREADS - 1) / STEP_THREADS, p.B);
-  if (p.phi != 0.f) {
+  if (p.phi != 0.f && !(generated && p.rng_row0 > 0)) {     // the statistics of the whole batch, once: with the first row range
     hipLaunchKernelGGL(cfg_stats_part_kernel, grid, dim3(STEP_THREADS), 0, s, p.m2, p.ld, p.B, p.C, p.HW, p.coef, p.part);
     hipLaunchKernelGGL(cfg_stats_final_kernel, dim3((p.B + 63) / 64), dim3(64), 0, s, (const float*)p.part, (int)grid.x, p.B, p.phi, p.stats);
   }
-  const auto kernel = eps ? (hist ? sampler_step_kernel<true, true> : sampler_step_kernel<true, false>)
-                          : (hist ? sampler_step_kernel<false, true> : sampler_step_kernel<false, false>);
+  if (noise) {
+    StepParams q = p;
+    if (!generated) q.rng_row0 = 0;
+    const dim3 rows(grid.x, generated ? p.rng_count : p.B);
+    const auto noisy = eps ? sampler_step_kernel<true, false, true> : sampler_step_kernel<false, false, true>;
+    hipLaunchKernelGGL(noisy, rows, dim3(STEP_THREADS), 0, s, q);
+    return hipGetLastError();
+  }
+  const auto kernel = eps ? (hist ? sampler_step_kernel<true, true, false> : sampler_step_kernel<true, false, false>)
+                          : (hist ? sampler_step_kernel<false, true, false> : sampler_step_kernel<false, false, false>);
   hipLaunchKernelGGL(kernel, grid, dim3(STEP_THREADS), 0, s, p);
   return hipGetLastError();
+}
+
+hipError_t launch_sampler_step_units(const StepParams& p, const uint64_t* unit_ids, hipStream_t s) {
+  if (p.sigma == 0.f || p.noise) return launch_sampler_step(p, s);
+  if (!unit_ids) return hipErrorInvalidValue;
+  StepParams q = p;
+  for (int r0 = 0; r0 < p.B; r0 += DD_RNG_UNITS) {
+    q.rng_row0 = r0; q.rng_count = p.B - r0 < DD_RNG_UNITS ? p.B - r0 : DD_RNG_UNITS;
+    for (int k = 0; k < q.rng_count; ++k) { q.rng_ids.lo[k] = (unsigned)unit_ids[r0 + k]; q.rng_ids.hi[k] = (unsigned)(unit_ids[r0 + k] >> 32); }
+    const hipError_t e = launch_sampler_step(q, s);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_sampler_step_bwd(const StepParams& p, const float* g_x0, const float* g_zprev, bf16_t* g_m2, float* g_z, hipStream_t s) {

@@ -72,6 +72,9 @@ def _declare(l):
     l.dd_import_packed.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     l.dd_set_schedule.argtypes = [vp, vp, i, vp, i, f, C.POINTER(DDSamplerParams)]
     l.dd_set_schedule_s.argtypes = [vp, vp, i, vp, i, f, C.POINTER(DDSamplerParams), i]
+    l.dd_set_schedule_e.argtypes = [vp, vp, i, vp, i, f, C.POINTER(DDSamplerParams), i, f]
+    l.dd_denoise_step_n.argtypes = [vp, vp, i, vp, vp, vp, i, vp]
+    l.dd_direct_guidance_n.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, i, vp]
     l.dd_set_prototypes.argtypes = [vp, vp, vp, i, i, i]
     l.dd_set_prompt.argtypes = [vp, vp, i, vp]
     l.dd_add_noise.argtypes = [vp, vp, vp, vp, i, i, vp]
@@ -269,11 +272,13 @@ class Engine:
     # ---- setup -------------------------------------------------------------------------------
     def set_schedule(self, timesteps, alphas_cumprod, final_alpha_cumprod, guidance_scale=7.5, gs=1.0, ls=1.0, rho=10.0,
                      constraint_value=0.2, use_global=True, use_local=True, guidance_period=2, prediction_type="epsilon",
-                     guidance_rescale=0.0, solver="ddim"):
+                     guidance_rescale=0.0, solver="ddim", eta=0.0):
         """prediction_type: what the UNet predicts, 'epsilon' | 'v_prediction' | 'sample' (scheduler_config.json); guidance_rescale: the
         CFG rescale factor phi in [0, 1] (diffusers rescale_noise_cfg); solver: 'ddim' | 'dpmsolver++' (DPM-Solver++(2M) on the same
-        timestep list: `expand` keeps its history itself, the step-level calls take it as `x0_prev`).  The defaults are the SD-1.x
-        sampler."""
+        timestep list: `expand` keeps its history itself, the step-level calls take it as `x0_prev`); eta in [0, 1]: stochastic DDIM
+        (diffusers DDIMScheduler.step(eta=...), 'ddim' only): every plain and direct-guidance step adds sigma_i n -- `expand` generates n
+        from (seed, unit id, step) itself, the step-level calls take it as `step_noise`; transform guidance's look-ahead stays
+        deterministic.  The defaults are the SD-1.x sampler; eta = 0 is the call without it, bit for bit."""
         if prediction_type not in PREDICTION_TYPES:
             raise NotImplementedError("prediction_type=%r (built: %s)" % (prediction_type, ", ".join(PREDICTION_TYPES)))
         if solver not in SOLVERS:
@@ -282,8 +287,8 @@ class Engine:
         ac = np.ascontiguousarray(np.asarray(alphas_cumprod, dtype=np.float32))
         sp = DDSamplerParams(guidance_scale, gs, ls, rho, constraint_value, int(use_global), int(use_local), int(guidance_period),
                              PREDICTION_TYPES[prediction_type], float(guidance_rescale))
-        self._chk(self.L.dd_set_schedule_s(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
-                                           float(final_alpha_cumprod), C.byref(sp), SOLVERS[solver]), "dd_set_schedule")
+        self._chk(self.L.dd_set_schedule_e(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
+                                           float(final_alpha_cumprod), C.byref(sp), SOLVERS[solver], float(eta)), "dd_set_schedule")
         self.n_steps = len(ts)
         self.timesteps = [int(t) for t in ts]
 
@@ -379,12 +384,20 @@ class Engine:
         self._chk(self.L.dd_unet_forward(self._h, _p(z), step_index, _p(out), z.shape[0], _stream()), "dd_unet_forward")
         return out
 
-    def denoise_step(self, z, step_index, x0_prev=None):
+    def denoise_step(self, z, step_index, x0_prev=None, step_noise=None):
         """-> (z', x0).  x0_prev: under solver 'dpmsolver++' the x0 this call returned for step_index - 1 on the same trajectory (the
-        second-order step); None is the first-order step."""
+        second-order step); None is the first-order step.  step_noise: on a schedule set with eta > 0 the N(0,1) tensor [B,C,L,L] of this
+        step, e.g. `randn_units(seed, 16 + step_index, unit_ids, C*L*L)`; None is the eta = 0 step."""
         z = self._f(z)
         h = self._f(x0_prev) if x0_prev is not None else None
         zp, x0 = torch.empty_like(z), torch.empty_like(z)
+        if step_noise is not None:
+            if h is not None:
+                raise ValueError("denoise_step: x0_prev (solver 'dpmsolver++') and step_noise (eta > 0) do not go together")
+            nz = self._f(step_noise)
+            assert nz.numel() == z.numel()
+            self._chk(self.L.dd_denoise_step_n(self._h, _p(z), step_index, _p(nz), _p(zp), _p(x0), z.shape[0], _stream()), "dd_denoise_step")
+            return zp, x0
         self._chk(self.L.dd_denoise_step_h(self._h, _p(z), step_index, _p(h), _p(zp), _p(x0), z.shape[0], _stream()), "dd_denoise_step")
         return zp, x0
 
@@ -398,13 +411,22 @@ class Engine:
                                                _p(gz0), z.shape[0], _stream()), "dd_transform_guidance")
         return out, score, gz0
 
-    def direct_guidance(self, z, targets, step_index, x0_prev=None):
-        """-> (z_next, x0, score, g_z).  x0_prev: as in `denoise_step`; it changes z_next alone (the gradient flows through x0)."""
+    def direct_guidance(self, z, targets, step_index, x0_prev=None, step_noise=None):
+        """-> (z_next, x0, score, g_z).  x0_prev, step_noise: as in `denoise_step`; they change z_next alone (the gradient flows through
+        x0, which depends on neither)."""
         z = self._f(z)
         h = self._f(x0_prev) if x0_prev is not None else None
         tg = targets.to(self.device, torch.int32).contiguous()
         zn, x0, gz = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
         score = torch.zeros(1, device=self.device)
+        if step_noise is not None:
+            if h is not None:
+                raise ValueError("direct_guidance: x0_prev (solver 'dpmsolver++') and step_noise (eta > 0) do not go together")
+            nz = self._f(step_noise)
+            assert nz.numel() == z.numel()
+            self._chk(self.L.dd_direct_guidance_n(self._h, _p(z), _p(tg), step_index, _p(nz), _p(zn), _p(x0), _p(score), _p(gz), z.shape[0],
+                                                  _stream()), "dd_direct_guidance")
+            return zn, x0, score, gz
         self._chk(self.L.dd_direct_guidance_h(self._h, _p(z), _p(tg), step_index, _p(h), _p(zn), _p(x0), _p(score), _p(gz), z.shape[0],
                                               _stream()), "dd_direct_guidance")
         return zn, x0, score, gz
@@ -432,7 +454,9 @@ class Engine:
 
     def randn_units(self, seed, stream, unit_ids, n):
         """The counter-based generator of `expand(seed=...)` on its own (dd_randn_units): device fp32 [len(unit_ids), n], row k a function
-        of (seed, stream, unit_ids[k]) alone.  stream 0 initial noise, 1 offset noise (unscaled), 3 b: N(0,1); 2 e: U[0,1)."""
+        of (seed, stream, unit_ids[k]) alone.  stream 0 initial noise, 1 offset noise (unscaled), 3 b: N(0,1); 2 e: U[0,1); 16 + i: the
+        N(0,1) noise of step index i of a schedule set with eta > 0 (n = C*L*L), what `expand` generates inside its step kernel; 4-15 are
+        reserved and refused."""
         ids = np.ascontiguousarray(np.asarray(unit_ids, dtype=np.uint64).reshape(-1))
         out = torch.empty((len(ids), int(n)), device=self.device, dtype=torch.float32)
         self._chk(self.L.dd_randn_units(self._h, int(seed) & (2 ** 64 - 1), int(stream), ids.ctypes.data_as(vp), len(ids), int(n), _p(out),
@@ -440,11 +464,13 @@ class Engine:
         return out
 
     def expand(self, image_latents, noise, e, b, targets, start_index, guidance_type, guide_first, guide_count, want_image=True,
-               seed=None, unit_ids=None, offset_noise=False, text_to_img=False):
+               seed=None, unit_ids=None, offset_noise=False, text_to_img=False, generate_inputs=True):
         """guidance_type: None | 'transform_guidance' | 'direct_guidance' (generate_data.py:1203-1218).
         seed + unit_ids [B]: the initial noise, the offset noise (offset_noise=True), e and b of row k are generated on the device from
         (seed, unit_ids[k]) alone (`randn_units`); `noise`, `e`, `b` are then not read and may be None.
-        text_to_img: the loop starts from the noise itself and runs the whole schedule (start_index must be 0); image_latents may be None."""
+        text_to_img: the loop starts from the noise itself and runs the whole schedule (start_index must be 0); image_latents may be None.
+        generate_inputs=False (a schedule set with eta > 0): `noise`, `e`, `b` are read as without seed / unit_ids, which then key the
+        noise of the steps alone -- step i of row k from (seed, unit_ids[k], stream 16 + i).  Under eta > 0 seed and unit_ids are required."""
         generated = seed is not None or unit_ids is not None
         if generated and (seed is None or unit_ids is None):
             raise ValueError("expand: seed and unit_ids go together")
@@ -469,8 +495,9 @@ class Engine:
             ids = np.ascontiguousarray(np.asarray(unit_ids, dtype=np.uint64).reshape(-1))
             if len(ids) != B:
                 raise ValueError("expand: %d unit ids for a batch of %d" % (len(ids), B))
-            a.seed, a.unit_ids, a.noise_mode = int(seed) & (2 ** 64 - 1), ids.ctypes.data_as(vp), 1     # host array, read during the call
-            a.offset_noise = int(bool(offset_noise))
+            a.seed, a.unit_ids = int(seed) & (2 ** 64 - 1), ids.ctypes.data_as(vp)     # host array, read during the call
+            a.noise_mode = int(bool(generate_inputs))
+            a.offset_noise = int(bool(offset_noise)) if generate_inputs else 0
         a.text_to_img = int(bool(text_to_img))
         self._chk(self.L.dd_expand(self._h, C.byref(a), _stream()), "dd_expand")
         return z_out, img, score

@@ -37,6 +37,11 @@ v-prediction / zero-SNR checkpoints (Lin et al. 2023; diffusers `rescale_noise_c
 (diffusers `DPMSolverMultistepScheduler`: dpmsolver++, order 2, midpoint, lower_order_final), which needs fewer `--steps` for the same
 quality; the chained steps inside transform guidance, the step executed again after it and the final step stay first-order.  The
 solver is chosen by this flag alone, never by `scheduler_config.json`'s `_class_name`.
+`--eta ETA` in (0, 1] (default 0, the reference's deterministic DDIM) is stochastic DDIM, diffusers `DDIMScheduler.step(eta=...)`: every
+plain and direct-guidance step of the main loop adds sigma_t * N(0,1), so the expansions of one train image differ by more than their
+first latent.  The step noise is counter-based under both --noise_rng settings -- generated inside the step kernel from (--seed, unit
+id, step index) -- so it never depends on how the run is packed; under `stream` the initial noise / e / b still come from the host
+generators.  The look-ahead steps inside transform guidance stay deterministic.  Not with --sampler dpmsolver++.
 The stage before the loop runs on the engine too: image latents come from the reference's cache
 `save/vae_embedding/<dataset>/<model>/image_latents.pt` when it exists and are otherwise produced by the HIP VAE encoder and
 written to that path in the same format (dataloader.py:788-811); class prompts go through the Hugging Face tokenizer of the
@@ -121,6 +126,9 @@ def parse_args(argv=None):
     p.add_argument("--sampler", default="ddim", choices=["ddim", "dpmsolver++"],
                    help="ddim (default): the reference's scheduler.  dpmsolver++: DPM-Solver++(2M), second-order multistep on the same timesteps "
                    "(about 20 --steps for the quality of 50 DDIM steps)")
+    p.add_argument("--eta", type=float, default=0.0,
+                   help="stochastic DDIM, eta in [0, 1] (diffusers DDIMScheduler.step(eta=...)): sigma_t = eta * sqrt((1-a')/(1-a) (1-a/a')) of fresh "
+                   "noise per step, keyed by (--seed, unit, step).  0 (default) = the reference's deterministic DDIM; 1 = DDPM-like.  --sampler ddim only")
     p.add_argument("--prediction_type", default=None, choices=["epsilon", "v_prediction", "sample"],
                    help="override scheduler_config.json's prediction_type (chiefly for --synthetic)")
     p.add_argument("--timestep_spacing", default=None, choices=["leading", "trailing", "linspace"],
@@ -147,6 +155,10 @@ def parse_args(argv=None):
         args.local_rank = env_local_rank
     if not 0.0 <= args.guidance_rescale <= 1.0:
         raise SystemExit("--guidance_rescale must be in [0, 1]")
+    if not 0.0 <= args.eta <= 1.0:                        # also refuses nan
+        raise SystemExit("--eta must be in [0, 1]")
+    if args.eta > 0.0 and args.sampler != "ddim":
+        raise SystemExit("--eta > 0 is stochastic DDIM: it does not go with --sampler %s" % args.sampler)
     if not args.do_classifier_free_guidance:
         raise SystemExit("the engine always runs classifier-free guidance (the reference's type=bool flag cannot be switched off either)")
     return args
@@ -361,6 +373,7 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
     n = len(ts)
     si = start_index(args.strength, n)
     philox, t2i = getattr(args, "noise_rng", "stream") == "philox", bool(getattr(args, "text_to_img", False))
+    eta = float(getattr(args, "eta", 0.0) or 0.0)         # > 0: every unit's counter also keys the noise of its steps, in either noise_rng
     if t2i:
         log.info("--text_to_img: the loop starts from noise at t=%d (start index 0; --strength %s does not apply%s)", ts[0], args.strength,
                  ", nor does --offset_noise" if args.offset_noise else "")
@@ -447,10 +460,12 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
             engine.set_added_cond(pooled.to(dev), torch.tensor([[S, S, 0.0, 0.0, S, S]]).expand(2 * EB, -1).to(dev))
         if args.guidance_type and hasattr(engine, "set_sample_weights"):
             engine.set_sample_weights([1.0 / u[3] for u in chunk] + [0.0] * (EB - nb))
-        if not (philox or t2i):
+        if not (philox or t2i or eta > 0.0):
             z, img, score = engine.expand(lat, noise, e, b, tg, si, args.guidance_type or None, gfirst, gcount, want_image=True)
         else:
             kw = dict(seed=int(seed), unit_ids=[u[8] for u in chunk_p], offset_noise=offset_noise) if philox else {}
+            if eta > 0.0 and not philox:                  # the host's noise / e / b are read; seed and unit ids key the step noise alone
+                kw = dict(seed=int(seed), unit_ids=[u[8] for u in chunk_p], generate_inputs=False)
             if t2i:
                 kw["text_to_img"] = True
             z, img, score = engine.expand(lat, noise, e, b, tg, si, args.guidance_type or None, gfirst, gcount, want_image=True, **kw)
@@ -589,7 +604,7 @@ def build_engine(args, device=None, distributed=False):
                      rho=args.rho, constraint_value=args.constraint_value, use_global="global_prototype" in targets,
                      use_local="local_prototype" in targets, guidance_period=args.guidance_period,
                      prediction_type=cfg.scheduler.prediction_type, guidance_rescale=args.guidance_rescale,
-                     solver=getattr(args, "sampler", "ddim"))
+                     solver=getattr(args, "sampler", "ddim"), **({"eta": args.eta} if getattr(args, "eta", 0.0) else {}))
     return cfg, eng, sched
 
 

@@ -6,7 +6,10 @@ Random draws follow the reference: e ~ U[0,1) and b ~ N(0,1) from the CPU global
 
 The shims are stateless, as the reference's functions are: each call is one first-order step, also on an engine whose schedule was
 set with solver="dpmsolver++".  The second-order step needs the previous step's x0, which these signatures have no place for: pass
-it to `Engine.denoise_step` / `Engine.direct_guidance` as `x0_prev`, or let `Engine.expand` keep it."""
+it to `Engine.denoise_step` / `Engine.direct_guidance` as `x0_prev`, or let `Engine.expand` keep it.  Likewise each call is the
+deterministic (eta = 0) step, also on an engine whose schedule was set with eta > 0: the noise of a stochastic step is an input these
+signatures have no place for either -- pass it to `Engine.denoise_step` / `Engine.direct_guidance` as `step_noise`, or let
+`Engine.expand` generate it."""
 import torch
 
 

@@ -15,7 +15,8 @@
  *   dd_add_noise           noise_scheduler.add_noise                            generate_data.py:1176
  *   dd_denoise_step        denoise_one_step (noise_scheduler.step for epsilon /   generate_data.py:109-121
  *                          v_prediction / sample models: dd_sampler_params;
- *                          dd_denoise_step_h: the DPM-Solver++(2M) step with its history)
+ *                          dd_denoise_step_h: the DPM-Solver++(2M) step with its history;
+ *                          dd_denoise_step_n: the eta > 0 step with its noise)
  *   dd_transform_guidance  transform_guidance (+ linfball_proj)                 generate_data.py:687-732, 124-137
  *   dd_direct_guidance     direct_guidance                                      generate_data.py:735-767
  *   dd_decode              vae.decode + image_processor.postprocess             generate_data.py:1221-1228
@@ -48,12 +49,13 @@ enum dd_status { DD_OK = 0, DD_ERR_ARG = -1, DD_ERR_HIP = -2, DD_ERR_STATE = -3,
 /* Layout version of the structs and argument lists of this header and distdiff_hip_ops.h.  A caller sets dd_config.abi_version =
  * DD_ABI_VERSION (after zero-initialising the struct: every struct of this ABI must be zero-initialised, new fields are appended and
  * mean "off" at 0); dd_create refuses another value with DD_ERR_ARG, and dd_abi_version() tells what the loaded library was built
- * as.  9: dd_set_schedule_s (the schedule with a solver: 0 = DDIM, the sampler of version 8; 1 = DPM-Solver++(2M)), dd_denoise_step_h /
+ * as.  10: dd_set_schedule_e (the schedule with eta in [0, 1]: stochastic DDIM), dd_denoise_step_n / dd_direct_guidance_n /
+ * dd_op_step_coefs_eta / dd_op_sampler_step_n are new, dd_randn_units takes the streams 16 + i, no struct changed; 9: dd_set_schedule_s (the schedule with a solver: 0 = DDIM, the sampler of version 8; 1 = DPM-Solver++(2M)), dd_denoise_step_h /
  * dd_direct_guidance_h / dd_op_step_coef_2m / dd_op_sampler_step_2m are new, no struct changed; 8: dd_sampler_params gained prediction_type /
  * guidance_rescale (0 = the sampler of version 7), the dd_op_sampler_step* entry points are new; 7: dd_expand_args gained seed / unit_ids / noise_mode / offset_noise / text_to_img (all 0 = the call of version 6), dd_randn_units
  * is new; 6: dd_config gained unet_attn_fp8 + abi_version, AttnParams gained no_shortk; 5 (unversioned): workspace_bytes in the dd_op_attention_gemm_* lists,
  * ConvGemmParams.wgroup_rows / wgroup_elems, AttnParams.pv_fp8. */
-#define DD_ABI_VERSION 9
+#define DD_ABI_VERSION 10
 
 typedef struct dd_config {
   /* UNet2DConditionModel (unet/config.json) */
@@ -191,6 +193,21 @@ int dd_set_schedule(dd_engine* e, const int* timesteps, int n, const float* alph
  * Any other solver is refused.  The solver travels as an argument and not in dd_sampler_params, whose layout stays version 8's. */
 int dd_set_schedule_s(dd_engine* e, const int* timesteps, int n, const float* alphas_cumprod, int num_train_timesteps,
                       float final_alpha_cumprod, const dd_sampler_params* sp, int solver);
+/* dd_set_schedule_s with eta (version 10); eta 0 IS dd_set_schedule_s: the same kernels, the same bits, nothing more allocated.
+ * eta in (0, 1] is stochastic DDIM (diffusers DDIMScheduler.step(eta=...), use_clipped_model_output False; beyond the reference, which
+ * steps with eta = 0).  With x0 and eps as in dd_sampler_params:
+ *   var = (1 - a') / (1 - a) (1 - a / a')    sigma = eta sqrt(var)    d = sqrt(max(0, 1 - a' - sigma^2))
+ *   z' = sqrt(a') x0 + d eps + sigma n       n ~ N(0, 1) per element, at every step, the last included
+ * x0 does not depend on eta or on n.  Where it applies: the plain steps of dd_expand's loop, the step it executes again after transform
+ * guidance, and the step inside direct guidance (z_next = the stochastic step - rho g; g, x0 and the score are those of eta = 0, the
+ * gradient flows through x0 alone).  dd_transform_guidance's chained steps are a look-ahead whose z_next is discarded: they stay
+ * eta = 0, forward and backward.  The noise is explicit at the step level -- the step_noise argument of dd_denoise_step_n /
+ * dd_direct_guidance_n -- and generated inside the step kernel by dd_expand, from (seed, unit id, stream 16 + step index) of
+ * dd_randn_units: bit for bit what the explicit call gives on dd_randn_units' output, with no noise tensor in memory.
+ * Refused: eta outside [0, 1] or not finite; eta > 0 with solver 1 (the SDE variant is another solver); more than 4096 steps.
+ * eta travels as an argument: the layout of dd_sampler_params stays version 8's. */
+int dd_set_schedule_e(dd_engine* e, const int* timesteps, int n, const float* alphas_cumprod, int num_train_timesteps,
+                      float final_alpha_cumprod, const dd_sampler_params* sp, int solver, float eta);
 /* Pc [C,D], Pg [C,K,D] HOST fp32, already L2-normalised by the caller as the reference does */
 int dd_set_prototypes(dd_engine* e, const float* Pc, const float* Pg, int C, int K, int D);
 /* embeds: DEVICE fp32 [2B, text_len, cross_dim], negative half first */
@@ -216,16 +233,29 @@ int dd_denoise_step_h(dd_engine* e, const float* z, int step_index, const float*
                       void* stream);
 int dd_direct_guidance_h(dd_engine* e, const float* z, const int* targets, int step_index, const float* x0_prev, float* z_next_out,
                          float* x0_out, float* score_out, float* grad_z_out, int B, void* stream);
+/* dd_denoise_step / dd_direct_guidance with explicit step noise (a schedule set with eta > 0): step_noise DEVICE [B,4,L,L] fp32, e.g.
+ * dd_randn_units(seed, 16 + step_index, ...) or any tensor of the caller's; z' gains sigma_i n, rounded as a product and then a sum.
+ * step_noise == NULL makes them dd_denoise_step / dd_direct_guidance, the eta = 0 step; a non-NULL step_noise on a schedule set with
+ * eta = 0 returns DD_ERR_STATE. */
+int dd_denoise_step_n(dd_engine* e, const float* z, int step_index, const float* step_noise, float* z_prev_out, float* x0_out, int B,
+                      void* stream);
+int dd_direct_guidance_n(dd_engine* e, const float* z, const int* targets, int step_index, const float* step_noise, float* z_next_out,
+                         float* x0_out, float* score_out, float* grad_z_out, int B, void* stream);
 int dd_decode(dd_engine* e, const float* z, float* image_out, int denormalize, int B, void* stream);
 /* Under solver 1 the loop keeps the history itself, in one buffer of the engine, for every input mode: plain and direct-guidance steps
  * read it and leave their x0 in it; the first executed step, the step executed again after transform guidance and the last step run
- * without one (first-order). */
+ * without one (first-order).
+ * Under eta > 0 the loop needs unit_ids in either noise_mode (DD_ERR_ARG without): step i of row k takes its noise from
+ * (seed, unit_ids[k], stream 16 + i), generated inside the step kernel.  With noise_mode 0 the caller's noise / e / b are read as
+ * before and seed / unit_ids key the step noise alone. */
 int dd_expand(dd_engine* e, const dd_expand_args* a, void* stream);
 /* The counter-based generator of dd_expand's noise_mode 1 on its own: out DEVICE fp32 [B, n_per_unit].  Philox4x32-10 (Salmon et al.,
  * Random123), key = (seed lo, seed hi), counter = (j / 4, rng_stream, unit id lo, unit id hi) for element j of a unit: one 128-bit
  * block (words w0..w3) per 4 outputs.  Normals by Box-Muller from the word pairs (w0, w1) and (w2, w3): u1 = (wa + 0.5) 2^-32,
  * u2 = (wb + 0.5) 2^-32, r = sqrt(-2 ln u1) -> r cos(2 pi u2), r sin(2 pi u2).  rng_stream: 0 initial noise [C,L,L], 1 offset noise
- * [C] (unscaled), 3 b [4] -- N(0,1); 2 e [4] -- uniform (w >> 8) 2^-24 in [0,1).  unit_ids: HOST [B], read before the call returns. */
+ * [C] (unscaled), 3 b [4] -- N(0,1); 2 e [4] -- uniform (w >> 8) 2^-24 in [0,1); 16 + i, i < 4096: the noise of step index i of the
+ * schedule under eta > 0 [C,L,L] -- N(0,1) by the same Box-Muller.  4-15 are reserved: they and anything else return DD_ERR_ARG.
+ * unit_ids: HOST [B], read before the call returns. */
 int dd_randn_units(dd_engine* e, uint64_t seed, int rng_stream, const uint64_t* unit_ids, int B, int64_t n_per_unit, float* out,
                    void* stream);
 /* The reference's energy is a `.mean()` over ITS batch (train_batch_size images: generate_data.py:709, :716, :751, :758), so each

@@ -12,7 +12,8 @@
  *   dd_op_layernorm_*    LayerNorm in BasicTransformerBlock (:112)
  *   dd_op_attention_*    scaled-dot-product attention (self, cross, VAE mid block) (:112, :701)
  *   dd_op_sampler_step*  classifier-free guidance + DDIMScheduler.step (:116-119) for every prediction type, with optional CFG rescale
- *                        and, as dd_op_sampler_step_2m, the step of DPM-Solver++(2M) (both beyond the reference, which builds an
+ *                        and, as dd_op_sampler_step_2m, the step of DPM-Solver++(2M), as dd_op_sampler_step_n the stochastic step
+ *                        of eta > 0 (all beyond the reference, which builds an
  *                        epsilon DDIMScheduler); dd_op_cfg_ddim* are its (epsilon, no rescale) mode under their first names
  *   dd_op_bicubic*       F.interpolate(..., (224,224), 'bicubic') (:704, :745)
  *   dd_op_conv_f32       timm conv+BN(+ReLU) of image_encoder.encode_image and its input-gradient in exact fp32
@@ -93,7 +94,7 @@ int dd_op_nchw_f32_to_nhwc_bf16(const float* src, uint16_t* dst, int B, int C, i
                                 float scale, void* stream);
 int dd_op_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int B, int C, int H, int W, int ld, float scale,
                            float shift, int clamp, float lo, float hi, void* stream);
-/* The sampler step: ONE operation (one forward kernel, one backward kernel; distdiff_amd/csrc/sampler_step.hip) behind the five entry
+/* The sampler step: ONE operation (one forward kernel, one backward kernel; distdiff_amd/csrc/sampler_step.hip) behind the entry
  * points below, for every prediction_type (0 epsilon, 1 v_prediction, 2 sample; diffusers DDIMScheduler.step, eta = 0) with optional
  * classifier-free-guidance rescale (guidance_rescale = phi of Lin et al. 2023, diffusers rescale_noise_cfg) and optional second-order
  * term of DPM-Solver++(2M) (dd_set_schedule_s, solver 1; forward only):
@@ -114,6 +115,13 @@ int dd_op_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int B, int 
  *       i - 1, at step i and at step i's previous timestep: with lambda(a) = ln(a / (1 - a)) / 2, h = lambda(a_prev) - lambda(a),
  *       r = (lambda(a) - lambda(a_before)) / h, c = sqrt(a_prev) (1 - e^-h) / (2 r); exactly 0.0f for i = 0, i = n - 1 and wherever a
  *       lambda or c is not finite.  With x0_prev NULL or c == 0 the history is not read and x0 may be NULL: dd_op_sampler_step is that call.
+ *   sigma != 0 and a noise source (dd_op_sampler_step_n; forward only, no history)  adds sigma n: coef_dev[4] = d (division form) or
+ *       lin_dev = the first four floats of dd_op_step_coefs_eta(type, a, a_prev, eta, out5) = {A_z, A_m, B_z, B_m, sigma} (host, double
+ *       arithmetic; -1 as dd_op_step_coefs, for eta outside [0, 1] and for a result that is not finite; eta = 0: the floats of
+ *       dd_op_step_coefs and sigma = 0.0f).  n is `noise` DEVICE NCHW fp32 [B, C, HW] when given; otherwise, with unit_ids HOST [B] (read
+ *       before the call returns), it is generated in registers: element j = ch * HW + pix of row b is value j of
+ *       dd_randn_units(seed, rng_stream, unit_ids[b]), rng_stream = 16 + step index -- the same bits, 16 rows per launch.  z' =
+ *       (the step on those coefficients) + sigma * n: the product rounded, then the sum.  sigma == 0 or neither source: dd_op_sampler_step.
  * m2 fp32 rows [2B*HW, ld], unconditional half first; z, x0_prev, z', x0 and the cotangents NCHW fp32; g_m2 bf16 rows (every column
  * written, padding 0); g_x0 or g_zprev may be NULL.
  * Shapes: ld a multiple of 8, C <= 8, B <= 65535, for EVERY entry point; anything else returns hipErrorInvalidValue and launches
@@ -135,6 +143,10 @@ float dd_op_step_coef_2m(int step_index, int n_steps, double a_before, double a,
 int dd_op_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c, float* z_prev, float* x0, int B, int C,
                           int HW, const float* coef_dev, const float* lin_dev, int prediction_type, float guidance_rescale, float* stats,
                           float* part, void* stream);
+int dd_op_step_coefs_eta(int prediction_type, double a, double a_prev, double eta, float* out5);
+int dd_op_sampler_step_n(const float* m2, int ld, const float* z, const float* noise, float sigma, uint64_t seed, int rng_stream,
+                         const uint64_t* unit_ids, float* z_prev, float* x0, int B, int C, int HW, const float* coef_dev,
+                         const float* lin_dev, int prediction_type, float guidance_rescale, float* stats, float* part, void* stream);
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int accumulate,
                      void* stream);
 int dd_op_geglu_bwd(const uint16_t* raw, int ld_raw, const uint16_t* dout, int ld_dout, uint16_t* draw, int ld_draw, int M,
