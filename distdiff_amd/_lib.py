@@ -8,38 +8,65 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DD_LIB") or os.path.join(_HERE, "libdistdiff_hip.so")   # DD_LIB: A/B builds for benchmarking
+# the fp16 variant (the same sources compiled with -DDD_ACT_F16, build.py); DD_LIB moves the bf16 library alone, DD_LIB_F16 this one
+LIB_PATH_F16 = os.environ.get("DD_LIB_F16") or os.path.join(_HERE, "libdistdiff_hip_f16.so")
 
-ABI_VERSION = 10     # DD_ABI_VERSION of include/distdiff_hip.h this package's ctypes mirrors were written against
+ABI_VERSION = 11     # DD_ABI_VERSION of include/distdiff_hip.h this package's ctypes mirrors were written against
+ACT_DTYPES = ("bf16", "fp16")        # dd_act_dtype() of a library: index into this
 
-_lib = None
+_lib = None          # the bf16 library
+_lib_f16 = None
 
 
 class DistDiffLibraryError(RuntimeError):
     pass
 
 
-def lib():
-    """Returns the loaded shared library; raises loudly when it is absent (no CPU fallback)."""
-    global _lib
+def act_dtype_name(dtype):
+    """'bf16' / 'fp16' from a name or from a torch dtype (the 16-bit storage format of a library's tensors)."""
+    if dtype in ACT_DTYPES:
+        return dtype
+    import torch
+    if dtype == torch.bfloat16:
+        return "bf16"
+    if dtype == torch.float16:
+        return "fp16"
+    raise ValueError("activation dtype %r: the libraries store bf16 or fp16" % (dtype,))
+
+
+def _load(path, want):
+    if not os.path.exists(path):
+        raise DistDiffLibraryError(
+            "%s not built: run `python -m distdiff_amd.build` (needs hipcc, gfx950). "
+            "There is no CPU fallback for the product path." % os.path.basename(path))
+    try:
+        # PyTorch-ROCm bundles its own libamdhip64 (same SONAME as /opt/rocm's): load torch FIRST so that this library binds to
+        # the HIP runtime instance torch uses (one runtime per process; the other order leaves a runtime that sees no device)
+        import torch  # noqa: F401
+        l = C.CDLL(path)
+    except OSError as e:  # missing libamdhip64 etc.
+        raise DistDiffLibraryError("cannot load %s: %s" % (path, e))
+    # one version for both header surfaces (struct layouts and argument lists): a stale build must not be called with new mirrors
+    got = l.dd_abi_version() if hasattr(l, "dd_abi_version") else 5
+    if got != ABI_VERSION:
+        raise DistDiffLibraryError("%s was built as ABI version %d, this package speaks %d: rebuild with `python -m distdiff_amd.build`"
+                                   % (path, got, ABI_VERSION))
+    if l.dd_act_dtype() != ACT_DTYPES.index(want):
+        raise DistDiffLibraryError("%s stores %s, asked for the %s library" % (path, ACT_DTYPES[l.dd_act_dtype()], want))
+    _declare(l)
+    return l
+
+
+def lib(act_dtype="bf16"):
+    """Returns the loaded shared library of that storage format ('bf16' | 'fp16' or the torch dtype; one CDLL per format and process);
+    raises loudly when it is absent (no CPU fallback)."""
+    global _lib, _lib_f16
+    if act_dtype_name(act_dtype) == "fp16":
+        if _lib_f16 is None:
+            _lib_f16 = _load(LIB_PATH_F16, "fp16")
+        return _lib_f16
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise DistDiffLibraryError(
-                "libdistdiff_hip.so not built: run `python -m distdiff_amd.build` (needs hipcc, gfx950). "
-                "There is no CPU fallback for the product path.")
-        try:
-            # PyTorch-ROCm bundles its own libamdhip64 (same SONAME as /opt/rocm's): load torch FIRST so that this library binds to
-            # the HIP runtime instance torch uses (one runtime per process; the other order leaves a runtime that sees no device)
-            import torch  # noqa: F401
-            _lib = C.CDLL(LIB_PATH)
-        except OSError as e:  # missing libamdhip64 etc.
-            raise DistDiffLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-        # one version for both header surfaces (struct layouts and argument lists): a stale build must not be called with new mirrors
-        got = _lib.dd_abi_version() if hasattr(_lib, "dd_abi_version") else 5
-        if got != ABI_VERSION:
-            _lib = None
-            raise DistDiffLibraryError("%s was built as ABI version %d, this package speaks %d: rebuild with `python -m distdiff_amd.build`"
-                                       % (LIB_PATH, got, ABI_VERSION))
-        _declare(_lib)
+        _lib = _load(LIB_PATH, "bf16")
     return _lib
 
 
@@ -109,7 +136,7 @@ OPS_SYMBOLS = [
     "dd_debug_tensor", "dd_debug_num_tensors", "dd_debug_fusion_plan", "dd_debug_set_image", "dd_debug_set_images",
 ]
 ENGINE_SYMBOLS = [
-    "dd_abi_version", "dd_create", "dd_destroy", "dd_last_error", "dd_load_tensor", "dd_finalize_weights", "dd_set_prototypes",
+    "dd_abi_version", "dd_act_dtype", "dd_create", "dd_destroy", "dd_last_error", "dd_load_tensor", "dd_finalize_weights", "dd_set_prototypes",
     "dd_set_schedule", "dd_add_noise", "dd_denoise_step", "dd_transform_guidance", "dd_direct_guidance", "dd_decode",
     "dd_expand", "dd_image_to_u8", "dd_guide_encode", "dd_guide_encode_pooled", "dd_unet_forward", "dd_unet_vjp", "dd_decode_vjp", "dd_guide_vjp",
     "dd_set_prompt", "dd_set_added_cond", "dd_vae_encode", "dd_text_encode", "dd_text_encode_tower", "dd_set_sample_weights", "dd_get_image_scores", "dd_declare_tensor", "dd_packed_bytes", "dd_export_packed", "dd_import_packed", "dd_profile_enable", "dd_profile_read", "dd_workspace_bytes", "dd_flops_last", "dd_randn_units",

@@ -1,4 +1,4 @@
-"""Builds libdistdiff_hip.so (hand-written gfx950 kernels + engine + C ABI) in-tree with hipcc.
+"""Builds libdistdiff_hip.so (hand-written gfx950 kernels + engine + C ABI) and its fp16 variant libdistdiff_hip_f16.so in-tree with hipcc.
 
     python -m distdiff_amd.build            # incremental
     python -m distdiff_amd.build --force
@@ -38,37 +38,47 @@ def _newer(src, dst):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+# The variants of the library: (name, object directory, library, extra flags).  The fp16 library is the same SOURCES compiled with
+# -DDD_ACT_F16 (csrc/common.h: IEEE half instead of bf16 as the 16-bit storage format); an engine is a bf16 or an fp16 engine by the
+# library it was created in (_lib.lib(act_dtype)).  DD_BUILD_OBJ / DD_BUILD_LIB move the bf16 variant alone.
+LIB_F16 = os.path.join(HERE, "libdistdiff_hip_f16.so")
+VARIANTS = [("bf16", OBJ, LIB, []), ("fp16", os.path.join(HERE, "csrc", "_obj_f16"), LIB_F16, ["-DDD_ACT_F16"])]
+
+
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    os.makedirs(OBJ, exist_ok=True)
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     jobs = []
-    for s in srcs:
-        src = os.path.join(CSRC, s)
-        obj = os.path.join(OBJ, s + ".o")
-        if force or _newer(src, obj):
-            jobs.append((src, obj))
+    for name, objdir, _, extra in VARIANTS:
+        os.makedirs(objdir, exist_ok=True)
+        for s in srcs:
+            src = os.path.join(CSRC, s)
+            obj = os.path.join(objdir, s + ".o")
+            if force or _newer(src, obj):
+                jobs.append((name, src, obj, extra))
 
     def cc(job):
-        src, obj = job
-        cmd = [hipcc] + FLAGS + PER_FILE.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
+        name, src, obj, extra = job
+        cmd = [hipcc] + FLAGS + extra + PER_FILE.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         if verbose:
-            print("[build]", os.path.basename(src), flush=True)
+            print("[build]", name, os.path.basename(src), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
-            raise RuntimeError("hipcc failed for %s:\n%s" % (src, r.stderr[-4000:]))
+            raise RuntimeError("hipcc failed for %s (%s):\n%s" % (src, name, r.stderr[-4000:]))
         return obj
 
-    with ThreadPoolExecutor(max_workers=4) as ex:
+    # eight compilers: both variants in the wall time one took on four
+    with ThreadPoolExecutor(max_workers=8) as ex:
         list(ex.map(cc, jobs))
-    objs = [os.path.join(OBJ, s + ".o") for s in srcs]
-    if jobs or force or not os.path.exists(LIB):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("link failed:\n%s" % r.stderr[-4000:])
-        if verbose:
-            print("[build] linked", LIB, flush=True)
+    for name, objdir, lib, _ in VARIANTS:
+        objs = [os.path.join(objdir, s + ".o") for s in srcs]
+        if force or any(j[0] == name for j in jobs) or not os.path.exists(lib):
+            cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError("link failed (%s):\n%s" % (name, r.stderr[-4000:]))
+            if verbose:
+                print("[build] linked", lib, flush=True)
     return LIB
 
 

@@ -31,7 +31,7 @@ __device__ __forceinline__ void stage_tile(unsigned char* lds, int S, const bf16
     const int r = idx / VPR, v = idx % VPR;
     uint4 val = make_uint4(0, 0, 0, 0);
     if (r < nvalid && v * 8 < D) val = *(const uint4*)(g + (size_t)r * ld + v * 8);
-    if (ONES && v * 8 == D) val.x = 0x3f80u;
+    if (ONES && v * 8 == D) val.x = DD_ACT_ONE;
     *(uint4*)(lds + r * S + v * 16) = val;
   }
 }
@@ -47,7 +47,7 @@ __device__ __forceinline__ void tile_load(TileRegs<ROWS, DPK>& t, const bf16_t* 
     const int r = idx / VPR, v = idx % VPR;
     uint4 val = make_uint4(0, 0, 0, 0);
     if (idx < ROWS * VPR && r < nvalid && v * 8 < D) val = *(const uint4*)(g + (size_t)r * ld + v * 8);
-    if (ONES && v * 8 == D) val.x = 0x3f80u;
+    if (ONES && v * 8 == D) val.x = DD_ACT_ONE;
     t.v[i] = val;
   }
 }
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams 
       for (int ks = 0; ks < KS; ++ks) {
         const bf16x8 kf = lds_row_frag(Ks, kt * 16 + i16, S, g + 4 * ks);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) st[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][ks], st[qt][kt], 0, 0, 0);
+        for (int qt = 0; qt < QT; ++qt) st[qt][kt] = mfma16(kf, qf[qt][ks], st[qt][kt]);
       }
     }
     bf16x8 pf[QT][NC];
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams 
       for (int c = 0; c < NC; ++c) {
         const bf16x8 vf = lds_col_frag(Vs, 32 * c, S, dt0 + dt, lane);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qt][c], o[qt][dt], 0, 0, 0);
+        for (int qt = 0; qt < QT; ++qt) o[qt][dt] = mfma16(vf, pf[qt][c], o[qt][dt]);
       }
   };
   {
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
     const bool isv = (r / KT) & 1;
 #pragma unroll
     for (int v = DG; v < RG; ++v)
-      *(uint4*)(smem + r * S + v * 16) = make_uint4((ONES && isv && v == DG) ? 0x3f80u : 0u, 0, 0, 0);
+      *(uint4*)(smem + r * S + v * 16) = make_uint4((ONES && isv && v == DG) ? DD_ACT_ONE : 0u, 0, 0, 0);
   }
   if (tid < 8) *(uint4*)(smem + 4 * TILE + tid * 16) = make_uint4(0, 0, 0, 0);
   unsigned char* const VQ = smem + 4 * TILE + 128;          // FP8: the staged V tile as e4m3, [d 64][lane group 4][32 keys] = 8 KB
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
       for (int ks = 0; ks < KS; ++ks) {
         const bf16x8 kf = lds_row_frag(Ks, kt * 16 + i16, S, g + 4 * ks);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) st[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][ks], st[qt][kt], 0, 0, 0);
+        for (int qt = 0; qt < QT; ++qt) st[qt][kt] = mfma16(kf, qf[qt][ks], st[qt][kt]);
       }
     }
     bf16x8 pf[QT][NC];
@@ -431,7 +431,14 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
         // the tile's row maximum.  Later tiles: the optimistic pass (SAFE = false) exponentiates them as they are -- no row maximum,
         // nothing to wait for -- and the row sums tell at the end whether a row ran away from its reference (see the tail of the
         // kernel); the safe pass rebases a tile more than 2^LZ_SLACK above the reference before its exponentials (wave-uniform, rare).
+#ifdef DD_ACT_F16
+        // fp16 probabilities: p <= 2^8 in the safe pass, 2^8 below the largest half (65504).  The optimistic pass has no bound of its
+        // own: a p beyond 65504 packs to inf, the P.V MFMA turns it into inf or NaN in every O column (and in the row sum of the ones
+        // column), and the finiteness test behind the sweep sends the workgroup to the safe pass.
+        constexpr float LZ_SLACK = FP8 ? 6.f : 8.f;
+#else
         constexpr float LZ_SLACK = FP8 ? 6.f : 24.f;         // FP8: the probabilities must stay inside e4m3 (448)
+#endif
         bool rebase = FIRST;
         if constexpr (!FIRST && SAFE) rebase = __any(mx > LZ_SLACK);
         if (rebase) {
@@ -509,7 +516,7 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
       for (int c = 0; c < NC; ++c) {
         const bf16x8 vf = lds_col_frag(Vs, 32 * c, S, dt, lane);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qt][c], o[qt][dt], 0, 0, 0);
+        for (int qt = 0; qt < QT; ++qt) o[qt][dt] = mfma16(vf, pf[qt][c], o[qt][dt]);
       }
   };
   using T_ = std::true_type;
@@ -703,8 +710,8 @@ __global__ __launch_bounds__(256, DD_AW_DQ(D)) void attn_bwd_dq_kernel(AttnParam
           const bf16x8 vf = lds_row_frag(Vs, kt * 16 + i16, S, g + 4 * ks);
 #pragma unroll
           for (int qt = 0; qt < QT; ++qt) {
-            st[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][ks], st[qt][kt], 0, 0, 0);
-            dpt[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dof[qt][ks], dpt[qt][kt], 0, 0, 0);
+            st[qt][kt] = mfma16(kf, qf[qt][ks], st[qt][kt]);
+            dpt[qt][kt] = mfma16(vf, dof[qt][ks], dpt[qt][kt]);
           }
         }
       }
@@ -728,7 +735,7 @@ __global__ __launch_bounds__(256, DD_AW_DQ(D)) void attn_bwd_dq_kernel(AttnParam
       for (int c = 0; c < NC; ++c) {
         const bf16x8 kcf = lds_col_frag(Ks, 32 * c, S, dt0 + dt, lane);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) dq[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kcf, dsf[qt][c], dq[qt][dt], 0, 0, 0);
+        for (int qt = 0; qt < QT; ++qt) dq[qt][dt] = mfma16(kcf, dsf[qt][c], dq[qt][dt]);
       }
   };
   {
@@ -845,8 +852,8 @@ __global__ __launch_bounds__(256, DD_AW_DKV(D)) void attn_bwd_dkv_kernel(AttnPar
           const bf16x8 ofr = lds_row_frag(Os, qt * 16 + i16, S, g + 4 * ks);
 #pragma unroll
           for (int kt = 0; kt < KTW; ++kt) {
-            s[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfr, kf[kt][ks], ks == 0 ? sin4 : s[kt][qt], 0, 0, 0);
-            dp[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ofr, vf[kt][ks], ks == 0 ? din4 : dp[kt][qt], 0, 0, 0);
+            s[kt][qt] = mfma16(qfr, kf[kt][ks], ks == 0 ? sin4 : s[kt][qt]);
+            dp[kt][qt] = mfma16(ofr, vf[kt][ks], ks == 0 ? din4 : dp[kt][qt]);
           }
         }
       }
@@ -878,8 +885,8 @@ __global__ __launch_bounds__(256, DD_AW_DKV(D)) void attn_bwd_dkv_kernel(AttnPar
         const bf16x8 qcf = lds_col_frag(Qs, 32 * c, S, dt0 + dt, lane);
 #pragma unroll
         for (int kt = 0; kt < KTW; ++kt) {
-          dv[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ocf, pf[kt][c], dv[kt][dt], 0, 0, 0);
-          dk[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qcf, dsf[kt][c], dk[kt][dt], 0, 0, 0);
+          dv[kt][dt] = mfma16(ocf, pf[kt][c], dv[kt][dt]);
+          dk[kt][dt] = mfma16(qcf, dsf[kt][c], dk[kt][dt]);
         }
       }
   }
@@ -977,6 +984,9 @@ hipError_t run_plan(const AttnParams& p, const AttnScratch& scratch, const AttnP
 AttnPlan attention_plan(const AttnParams& p, const AttnScratch& sc, bool bwd, int force) {
   AttnPlan plan;
   if (p.Nq <= 0 || p.Nk <= 0) return plan;
+#ifdef DD_ACT_F16
+  if (p.pv_fp8) return plan;                                   // the fp16 build has no fp8 P.V form (its V quantisation pass reads bf16 tiles)
+#endif
   const bool ld8 = !(p.ldq & 7) && !(p.ldk & 7) && !(p.ldv & 7);
   if (sc.workspace && sc.tap1x1 && attn_gemm_shape(p.Nq, p.Nk, p.D, p.causal) && ld8 && !(p.ldo & 7) && (!bwd || (p.dk && p.dv)) &&
       sc.workspace_bytes >= attention_gemm_workspace(p.Nq, p.Nk, p.D, bwd)) {

@@ -66,7 +66,7 @@ __device__ __forceinline__ void sk_tile_frags(const AttnParams& p, const unsigne
     for (int ks = 0; ks < KS; ++ks) {
       const bf16x8 kf = lds_row_frag(Ks, kt * 16 + i16, S, g + 4 * ks);
 #pragma unroll
-      for (int qt = 0; qt < 2; ++qt) st[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][ks], st[qt][kt], 0, 0, 0);
+      for (int qt = 0; qt < 2; ++qt) st[qt][kt] = mfma16(kf, qf[qt][ks], st[qt][kt]);
     }
   }
   f32x4 o[2][DVT];
@@ -106,7 +106,7 @@ __device__ __forceinline__ void sk_tile_frags(const AttnParams& p, const unsigne
       o[qt][dt] = zero;
 #pragma unroll
       for (int cc = 0; cc < 3; ++cc)
-        o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_col_frag(Vs, 32 * cc, S, dt, lane), pf[cc], o[qt][dt], 0, 0, 0);
+        o[qt][dt] = mfma16(lds_col_frag(Vs, 32 * cc, S, dt, lane), pf[cc], o[qt][dt]);
     }
     // row sum: d % 16 == 8 (d = 40) -- column D of the staged V block is 1.0, so P.V delivered the sum of the bf16-ROUNDED probabilities in
     // O column D (lane group (D % 16) / 4, register 0): O is then an exact convex combination of the value rows, as in the streaming
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_shortk_kernel(AttnParams 
   for (int v = tid; v < (2 * NPK * 1024 + NW * 2 * QSLOT) / 16; v += NW * 64) *(uint4*)(smem + v * 16) = make_uint4(0, 0, 0, 0);
   __syncthreads();
   if constexpr ((D % 16) == 8) {                               // column D of every staged V row = 1.0: P.V also delivers the row sums
-    for (int r = tid; r < SK_KROWS; r += NW * 64) *(unsigned*)(Vs + r * S + DG * 16) = 0x3f80u;
+    for (int r = tid; r < SK_KROWS; r += NW * 64) *(unsigned*)(Vs + r * S + DG * 16) = DD_ACT_ONE;
     __syncthreads();
   }
 

@@ -3,23 +3,55 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-typedef unsigned short bf16_t;  // raw bf16 storage
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+// The 16-bit storage format of activations, weights and gradients is fixed when the library is compiled: bf16 (the product library),
+// or IEEE half with -DDD_ACT_F16 (libdistdiff_hip_f16.so).  It lives in this block alone: the raw storage type, the five conversions,
+// the MFMA operand vector with its instruction, and the constant 1.0.  bf16_t names the raw 16 bits in either build.
+typedef unsigned short bf16_t;  // raw 16-bit storage (bf16, or fp16 under DD_ACT_F16)
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 #define DD_WAVE 64
 
+#ifdef DD_ACT_F16
+#define DD_ACT_DTYPE 1
+#define DD_ACT_ONE 0x3c00u      // 1.0
+typedef __attribute__((ext_vector_type(8))) _Float16 bf16x8;
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+// v_cvt_f32_f16 / v_cvt_pk_f16_f32: RNE, NaN preserved, no saturation (beyond 65504 -> inf); never cvt_pkrtz, which rounds toward zero
+__device__ __forceinline__ float bf2f(bf16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
+__device__ __forceinline__ bf16_t f2bf(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
+__device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
+  const f32x2_t v = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
+}
+// one dword of two stored values -> two floats (lo in bits 0-15)
+__device__ __forceinline__ void unpack2(unsigned u, float& lo, float& hi) {
+  const f32x2_t v = __builtin_convertvector(__builtin_bit_cast(f16x2_t, u), f32x2_t);
+  lo = v[0]; hi = v[1];
+}
+__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
+  unpack2(v.x, f[0], f[1]); unpack2(v.y, f[2], f[3]); unpack2(v.z, f[4], f[5]); unpack2(v.w, f[6], f[7]);
+}
+// the one MFMA of the 16-bit kernels (a macro: the bf16 build must compile to the code it was before the two formats shared it)
+#define mfma16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
+#else
+#define DD_ACT_DTYPE 0
+#define DD_ACT_ONE 0x3f80u      // 1.0
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {
   __bf16 h = (__bf16)f;  // v_cvt_pk_bf16_f32: RNE, NaN preserved
   return __builtin_bit_cast(unsigned short, h);
 }
 // two floats -> one dword of two bf16 (lo in bits 0-15): a single v_cvt_pk_bf16_f32 (RNE), not two conversions + shift + or
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
   const f32x2_t v = {lo, hi};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
+}
+// one dword of two stored values -> two floats (lo in bits 0-15)
+__device__ __forceinline__ void unpack2(unsigned u, float& lo, float& hi) {
+  lo = __uint_as_float(u << 16); hi = __uint_as_float(u & 0xffff0000u);
 }
 __device__ __forceinline__ void unpack8(const uint4& v, float* f) {
   f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
@@ -27,10 +59,58 @@ __device__ __forceinline__ void unpack8(const uint4& v, float* f) {
   f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
   f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
 }
+#define mfma16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
+#endif
 __device__ __forceinline__ uint4 pack8(const float* f) {
   uint4 v; v.x = pack2bf(f[0], f[1]); v.y = pack2bf(f[2], f[3]); v.z = pack2bf(f[4], f[5]); v.w = pack2bf(f[6], f[7]);
   return v;
 }
+// the residual of four output columns, two dwords of stored values, added to their fp32 sums (the conv / GEMM epilogues; a macro for the
+// reason given at DD_STORED4 below)
+#ifdef DD_ACT_F16
+#define add_res4(q0, q1, v0, v1, v2, v3)                        \
+  do {                                                          \
+    float lo_, hi_;                                             \
+    unpack2(q0, lo_, hi_); v0 += lo_; v1 += hi_;                \
+    unpack2(q1, lo_, hi_); v2 += lo_; v3 += hi_;                \
+  } while (0)
+#else
+#define add_res4(q0, q1, v0, v1, v2, v3)                                                 \
+  do {                                                                                   \
+    v0 += __uint_as_float((q0) << 16); v1 += __uint_as_float((q0) & 0xffff0000u);        \
+    v2 += __uint_as_float((q1) << 16); v3 += __uint_as_float((q1) & 0xffff0000u);        \
+  } while (0)
+#endif
+// What the CF_STATS partials sum for four values on their way to a 16-bit store.  The fp16 build sums the values the tensor STORES (the
+// rounded ones, read back from the very dwords the epilogue writes: the compiler shares the two packs with the store), so the GroupNorm
+// that merges the partials normalises the tensor with that tensor's own statistics.  The bf16 build sums the fp32 values in front of the
+// rounding, as it always has: its bits are the record the bit tests compare with.
+// (a macro that declares u0 .. u3: as a function with reference results it moved the bf16 build's epilogue schedule)
+#ifdef DD_ACT_F16
+#define DD_STORED4(v0, v1, v2, v3, u0, u1, u2, u3) \
+  float u0, u1, u2, u3;                            \
+  unpack2(pack2bf(v0, v1), u0, u1);                \
+  unpack2(pack2bf(v2, v3), u2, u3)
+#else
+#define DD_STORED4(v0, v1, v2, v3, u0, u1, u2, u3) const float u0 = (v0), u1 = (v1), u2 = (v2), u3 = (v3)
+#endif
+// Cotangent normalisation of the fp16 build.  A reverse program is linear in its cotangent, is entered from an fp32
+// tensor and left into one: the entry kernel multiplies by a power of two s that puts the cotangent's absolute maximum into
+// [2^7, 2^8) -- 2^8 below the largest half for growth inside the program, 21 binades of normal range below the maximum -- and the exit
+// kernel by 1 / s, both exact.  s lives in a device scalar (launch_cot_scale, elementwise.hip); CotScale is how those kernels see it.
+// The bf16 build has bf16's fp32 exponent range and none of this: its CotScale is empty and mul() is the constant 1.
+#ifdef DD_ACT_F16
+struct CotScale {
+  const float* p;
+  __device__ __forceinline__ float mul() const { return p ? *p : 1.f; }
+};
+inline CotScale cot_scale_arg(const float* p) { return CotScale{p}; }
+#else
+struct CotScale {
+  __device__ __forceinline__ float mul() const { return 1.f; }
+};
+inline CotScale cot_scale_arg(const float*) { return CotScale{}; }
+#endif
 // A row of T (bf16_t or float) as the side kernels see it: one 16-byte vector holds V = 1 << SH elements, which are fp32 between
 // ld and st; get / put move one element.  bf16 rounds in st / put (RNE), fp32 is stored as it is.
 template <typename T> struct Row;

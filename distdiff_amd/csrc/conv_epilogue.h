@@ -70,8 +70,7 @@ struct Epi {
         const bf16_t* rp = (const bf16_t*)p.res + (size_t)m * p.res_ld + ob;
         if (full && !(p.res_ld & 3)) {
           uint2 rv = *(const uint2*)rp;
-          h[0] += __uint_as_float(rv.x << 16); h[1] += __uint_as_float(rv.x & 0xffff0000u);
-          h[2] += __uint_as_float(rv.y << 16); h[3] += __uint_as_float(rv.y & 0xffff0000u);
+          add_res4(rv.x, rv.y, h[0], h[1], h[2], h[3]);
         } else {
 #pragma unroll
           for (int r = 0; r < 4; ++r)

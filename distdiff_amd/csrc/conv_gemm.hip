@@ -166,7 +166,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(ConvGemmParams p
       for (int jn = 0; jn < 4; ++jn)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          acc[jn][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[jn], xf[i], acc[jn][i], 0, 0, 0);
+          acc[jn][i] = mfma16(wf[jn], xf[i], acc[jn][i]);
     }
   };
 

@@ -314,7 +314,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void conv_gemm
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int jn = 0; jn < TN; ++jn) acc[jn][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F.wf[jn], F.xf[i], acc[jn][i], 0, 0, 0);
+      for (int jn = 0; jn < TN; ++jn) acc[jn][i] = mfma16(F.wf[jn], F.xf[i], acc[jn][i]);
   };
   // CF_STATS: per-(64-row block, channel) partial statistics of the values this wave stores, for the GroupNorm that consumes the
   // tensor: s1 / s2 hold this lane's sums over its 4 pixel rows, the 16 lanes of an MFMA row are summed with 4 DPP adds per value,
@@ -453,14 +453,14 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void conv_gemm
           (void)jn;
           float v0 = a[0] * p.alpha + b.x, v1 = a[1] * p.alpha + b.y, v2 = a[2] * p.alpha + b.z, v3 = a[3] * p.alpha + b.w;
           if (fl & CF_RES) {
-            v0 += __uint_as_float(r0 << 16); v1 += __uint_as_float(r0 & 0xffff0000u);
-            v2 += __uint_as_float(r1 << 16); v3 += __uint_as_float(r1 & 0xffff0000u);
+            add_res4(r0, r1, v0, v1, v2, v3);
           }
           if (fl & CF_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
           if (ST == 1 && (fl & CF_STATS)) {
-            t1[0] += v0; t1[1] += v1; t1[2] += v2; t1[3] += v3;
-            t2[0] = __builtin_fmaf(v0, v0, t2[0]); t2[1] = __builtin_fmaf(v1, v1, t2[1]);
-            t2[2] = __builtin_fmaf(v2, v2, t2[2]); t2[3] = __builtin_fmaf(v3, v3, t2[3]);
+            DD_STORED4(v0, v1, v2, v3, u0, u1, u2, u3);
+            t1[0] += u0; t1[1] += u1; t1[2] += u2; t1[3] += u3;
+            t2[0] = __builtin_fmaf(u0, u0, t2[0]); t2[1] = __builtin_fmaf(u1, u1, t2[1]);
+            t2[2] = __builtin_fmaf(u2, u2, t2[2]); t2[3] = __builtin_fmaf(u3, u3, t2[3]);
           }
           if constexpr (ST == 2) {
             rs1[i] += (v0 + v1) + (v2 + v3);
@@ -581,8 +581,10 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void conv_gemm
           for (int r = 0; r < 4; ++r) h[r] = acc[jn][i][r];
           Epi::apply(p, bias, m, nb, h, h, 0);     // leaves the stored values (before the bf16 rounding) in h
           if (ST == 1 && (p.flags & CF_STATS)) {
+            DD_STORED4(h[0], h[1], h[2], h[3], u0, u1, u2, u3);
+            const float u[4] = {u0, u1, u2, u3};
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { s1[jn][r] += h[r]; s2[jn][r] = __builtin_fmaf(h[r], h[r], s2[jn][r]); }
+            for (int r = 0; r < 4; ++r) { s1[jn][r] += u[r]; s2[jn][r] = __builtin_fmaf(u[r], u[r], s2[jn][r]); }
           }
         }
       }

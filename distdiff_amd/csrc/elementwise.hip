@@ -21,8 +21,9 @@ inline int nblocks(size_t n, int threads = 256, int cap = 8192) {
 // DUP: the form that can write the batch twice (dup) and scale it; without it dup and scale are not read, and the instance is the
 // plain re-layout it was before the two formats shared this kernel (same registers, same instructions)
 template <typename T, bool DUP>
-__global__ void nchw_to_nhwc_kernel(const float* src, T* dst, int B, int C, int HW, int Cpad, int ld, int dup, float scale) {
+__global__ void nchw_to_nhwc_kernel(const float* src, T* dst, int B, int C, int HW, int Cpad, int ld, int dup, float scale, CotScale cs) {
   const size_t total = (size_t)(DUP && dup ? 2 * B : B) * HW * Cpad;
+  if (DUP) scale *= cs.mul();
   GRID_STRIDE(i, total) {
     const int c = (int)(i % Cpad);
     const size_t row = i / Cpad;
@@ -34,8 +35,9 @@ __global__ void nchw_to_nhwc_kernel(const float* src, T* dst, int B, int C, int 
 }
 
 __global__ void nhwc_to_nchw_kernel(const void* src, int src_f32, float* dst, int B, int C, int HW, int ld, float scale,
-                                    float shift, int clamp, float lo, float hi) {
+                                    float shift, int clamp, float lo, float hi, CotScale cs) {
   const size_t total = (size_t)B * C * HW;
+  scale *= cs.mul();
   GRID_STRIDE(i, total) {
     const int pix = (int)(i % HW);
     const int c = (int)((i / HW) % C);
@@ -49,14 +51,16 @@ __global__ void nhwc_to_nchw_kernel(const void* src, int src_f32, float* dst, in
 }
 
 // g_z[b,c,pix] += gin[(b*HW+pix), c] + gin[((B+b)*HW+pix), c]   (backward of cat[z, z] + layout change)
-__global__ void dup_bwd_kernel(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves) {
+__global__ void dup_bwd_kernel(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, CotScale cs) {
   const size_t total = (size_t)B * C * HW;
+  const float inv = cs.mul();
   GRID_STRIDE(i, total) {
     const int pix = (int)(i % HW);
     const int c = (int)((i / HW) % C);
     const int b = (int)(i / ((size_t)HW * C));
     float v = bf2f(gin[((size_t)b * HW + pix) * ld + c]);
     if (halves == 2) v += bf2f(gin[((size_t)(B + b) * HW + pix) * ld + c]);
+    v *= inv;
     g_z[i] = accumulate ? g_z[i] + v : v;
   }
 }
@@ -261,8 +265,8 @@ __global__ void bicubic_kernel(const T* src, int ld_s, T* dst, int ld_d, int B, 
 // source pixel: deterministic, no atomics. For a down-scale factor s the candidate dst range is small.  The gradient may change
 // format on the way: fp32 ddst -> bf16 dsrc is the guide's input gradient written into the VAE decoder's gradient slab.
 template <typename TI, typename TO>
-__global__ void bicubic_bwd_kernel(const TI* ddst, int ld_d, TO* dsrc, int ld_s, int B, int Hs, int Ws, int Hd, int Wd, int C) {
-  const float sh = (float)Hs / (float)Hd, sw = (float)Ws / (float)Wd;
+__global__ void bicubic_bwd_kernel(const TI* ddst, int ld_d, TO* dsrc, int ld_s, int B, int Hs, int Ws, int Hd, int Wd, int C, CotScale cs) {
+  const float sh = (float)Hs / (float)Hd, sw = (float)Ws / (float)Wd, mul = cs.mul();
   GRID_STRIDE(i, (size_t)B * Hs * Ws) {
     const int sx = (int)(i % Ws), sy = (int)((i / Ws) % Hs), b = (int)(i / ((size_t)Ws * Hs));
     // dst rows whose taps (fy-1..fy+2, clamped) can touch sy: fy in [sy-2, sy+1] -> invert ry = sh*(d+.5)-.5
@@ -292,7 +296,7 @@ __global__ void bicubic_bwd_kernel(const TI* ddst, int ld_d, TO* dsrc, int ld_s,
         for (int c = 0; c < C && c < 4; ++c) acc[c] += wys * wxs * Row<TI>::get(d + c);
       }
     }
-    for (int c = 0; c < C && c < 4; ++c) Row<TO>::put(dsrc + i * ld_s + c, acc[c]);
+    for (int c = 0; c < C && c < 4; ++c) Row<TO>::put(dsrc + i * ld_s + c, acc[c] * mul);
   }
 }
 
@@ -449,7 +453,10 @@ __global__ __launch_bounds__(256) void transform_update_kernel(const float* z, c
 __global__ void sub_scaled_kernel(const float* a, const float* g, float* out, size_t n, float rho) {
   GRID_STRIDE(i, n) out[i] = a[i] - rho * g[i];
 }
-__global__ void f32_to_bf16_kernel(const float* s, bf16_t* d, size_t n) { GRID_STRIDE(i, n) d[i] = f2bf(s[i]); }
+__global__ void f32_to_bf16_kernel(const float* s, bf16_t* d, size_t n, CotScale cs) {
+  const float mul = cs.mul();
+  GRID_STRIDE(i, n) d[i] = f2bf(s[i] * mul);
+}
 __global__ void fill_kernel(float* d, float v, size_t n) { GRID_STRIDE(i, n) d[i] = v; }
 __global__ void to_uint8_kernel(const float* nchw, uint8_t* hwc, int B, int C, int HW) {
   GRID_STRIDE(i, (size_t)B * HW * C) {
@@ -636,6 +643,42 @@ __global__ void rows_bf16_to_f32_kernel(const bf16_t* x, int ld, float* y, int M
   GRID_STRIDE(i, total) { y[i] = bf2f(x[(i / C) * ld + (i % C)]); }
 }
 
+#ifdef DD_ACT_F16
+// The cotangent scale of the fp16 build (common.h: CotScale).  Absolute maximum of x[r * ld + c], c < C, over up to two fp32 tensors in
+// two stages without atomics -- COT_BLOCKS block maxima per tensor, then one wave -- and from it scale2 = {s, 1 / s} with s the power of
+// two that puts the maximum into [2^7, 2^8); s = 1 for a maximum of 0 (an all-zero cotangent) or one that is not finite.  fmaxf drops
+// NaN operands: a NaN element does not decide the scale, it propagates through the program as it does in the bf16 build.
+constexpr int COT_BLOCKS = 256;
+__global__ __launch_bounds__(256) void cot_absmax_part_kernel(const float* x, size_t rows, int C, int ld, float* part) {
+  float m = 0.f;
+  GRID_STRIDE(i, rows * (size_t)C) m = fmaxf(m, fabsf(x[(i / C) * ld + (i % C)]));
+  m = wave_max(m);
+  __shared__ float sm[4];
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+}
+__global__ __launch_bounds__(64) void cot_absmax_final_kernel(const float* part, int n, float* scale2) {
+  float m = 0.f;
+  for (int i = threadIdx.x; i < n; i += 64) m = fmaxf(m, part[i]);
+  m = wave_max(m);
+  if (threadIdx.x == 0) {
+    int k = 0;
+    if (m > 0.f && m < INFINITY) {
+      int e;
+      (void)frexpf(m, &e);                                   // m in [2^(e-1), 2^e)
+      k = min(max(8 - e, -120), 120);                        // s m in [2^7, 2^8); clamped so that s and 1 / s are normal floats
+    }
+    scale2[0] = ldexpf(1.f, k);
+    scale2[1] = ldexpf(1.f, -k);
+  }
+}
+__global__ void cot_mul_kernel(float* x, size_t rows, int C, int ld, const float* mul) {
+  const float m = *mul;
+  GRID_STRIDE(i, rows * (size_t)C) x[(i / C) * ld + (i % C)] *= m;
+}
+#endif
+
 }  // namespace
 
 #define LAUNCH(kern, n, ...) hipLaunchKernelGGL(kern, dim3(nblocks(n)), dim3(256), 0, s, __VA_ARGS__); return hipGetLastError()
@@ -668,25 +711,26 @@ hipError_t maxpool_bwd_rows(const T* x, const T* dy, T* dx, int B, int H, int W,
   LAUNCH(maxpool_bwd_kernel<T>, (size_t)B * H * W * (C / Row<T>::V), x, dy, dx, B, H, W, C);
 }
 template <typename TI, typename TO>
-hipError_t bicubic_bwd_rows(const TI* ddst, int ld_d, TO* dsrc, int ld_s, int B, int Hs, int Ws, int Hd, int Wd, int C, hipStream_t s) {
+hipError_t bicubic_bwd_rows(const TI* ddst, int ld_d, TO* dsrc, int ld_s, int B, int Hs, int Ws, int Hd, int Wd, int C, hipStream_t s,
+                            const float* cot_mul = nullptr) {
   if (C > 4) return hipErrorInvalidValue;
-  LAUNCH((bicubic_bwd_kernel<TI, TO>), (size_t)B * Hs * Ws, ddst, ld_d, dsrc, ld_s, B, Hs, Ws, Hd, Wd, C);
+  LAUNCH((bicubic_bwd_kernel<TI, TO>), (size_t)B * Hs * Ws, ddst, ld_d, dsrc, ld_s, B, Hs, Ws, Hd, Wd, C, cot_scale_arg(cot_mul));
 }
 }  // namespace
 
 hipError_t launch_nchw_f32_to_nhwc_bf16(const float* src, bf16_t* dst, int B, int C, int H, int W, int Cpad, int ld, int dup,
-                                        float scale, hipStream_t s) {
-  LAUNCH((nchw_to_nhwc_kernel<bf16_t, true>), (size_t)(dup ? 2 : 1) * B * H * W * Cpad, src, dst, B, C, H * W, Cpad, ld, dup, scale);
+                                        float scale, hipStream_t s, const float* cot_mul) {
+  LAUNCH((nchw_to_nhwc_kernel<bf16_t, true>), (size_t)(dup ? 2 : 1) * B * H * W * Cpad, src, dst, B, C, H * W, Cpad, ld, dup, scale, cot_scale_arg(cot_mul));
 }
 hipError_t launch_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int H, int W, int Cpad, int ld, hipStream_t s) {
-  LAUNCH((nchw_to_nhwc_kernel<float, false>), (size_t)B * H * W * Cpad, src, dst, B, C, H * W, Cpad, ld, 0, 1.f);
+  LAUNCH((nchw_to_nhwc_kernel<float, false>), (size_t)B * H * W * Cpad, src, dst, B, C, H * W, Cpad, ld, 0, 1.f, cot_scale_arg(nullptr));
 }
 hipError_t launch_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int B, int C, int H, int W, int ld, float scale,
-                                   float shift, int clamp, float lo, float hi, hipStream_t s) {
-  LAUNCH(nhwc_to_nchw_kernel, (size_t)B * C * H * W, src, src_f32, dst, B, C, H * W, ld, scale, shift, clamp, lo, hi);
+                                   float shift, int clamp, float lo, float hi, hipStream_t s, const float* cot_mul) {
+  LAUNCH(nhwc_to_nchw_kernel, (size_t)B * C * H * W, src, src_f32, dst, B, C, H * W, ld, scale, shift, clamp, lo, hi, cot_scale_arg(cot_mul));
 }
-hipError_t launch_dup_bwd(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, hipStream_t s) {
-  LAUNCH(dup_bwd_kernel, (size_t)B * C * HW, gin, ld, g_z, B, C, HW, accumulate, halves);
+hipError_t launch_dup_bwd(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, hipStream_t s, const float* cot_mul) {
+  LAUNCH(dup_bwd_kernel, (size_t)B * C * HW, gin, ld, g_z, B, C, HW, accumulate, halves, cot_scale_arg(cot_mul));
 }
 hipError_t launch_axpby(const float* x, const float* n, float* out, size_t count, const float* coef_dev, hipStream_t s) {
   LAUNCH(axpby_kernel, count, x, n, out, count, coef_dev);
@@ -745,9 +789,9 @@ hipError_t launch_bicubic_bwd(const bf16_t* ddst, int ld_d, bf16_t* dsrc, int ld
   return bicubic_bwd_rows(ddst, ld_d, dsrc, ld_s, B, Hs, Ws, Hd, Wd, C, s);
 }
 hipError_t launch_bicubic_bwd_f32(const float* ddst, int ld_d, void* dsrc, int dsrc_bf16, int ld_s, int B, int Hs, int Ws, int Hd, int Wd,
-                                  int C, hipStream_t s) {
-  return dsrc_bf16 ? bicubic_bwd_rows(ddst, ld_d, (bf16_t*)dsrc, ld_s, B, Hs, Ws, Hd, Wd, C, s)
-                   : bicubic_bwd_rows(ddst, ld_d, (float*)dsrc, ld_s, B, Hs, Ws, Hd, Wd, C, s);
+                                  int C, hipStream_t s, const float* cot_mul) {
+  return dsrc_bf16 ? bicubic_bwd_rows(ddst, ld_d, (bf16_t*)dsrc, ld_s, B, Hs, Ws, Hd, Wd, C, s, cot_mul)
+                   : bicubic_bwd_rows(ddst, ld_d, (float*)dsrc, ld_s, B, Hs, Ws, Hd, Wd, C, s, cot_mul);
 }
 hipError_t launch_gap(const bf16_t* x, int ld, float* f, int B, int HW, int C, hipStream_t s) {
   LAUNCH((gap_kernel<bf16_t, false>), (size_t)B * C, x, ld, f, (int*)nullptr, B, HW, C, 0);
@@ -781,7 +825,24 @@ hipError_t launch_transform_update(const float* z, const float* g, const float* 
 hipError_t launch_sub_scaled(const float* a, const float* g, float* out, size_t n, float rho, hipStream_t s) {
   LAUNCH(sub_scaled_kernel, n, a, g, out, n, rho);
 }
-hipError_t launch_f32_to_bf16(const float* src, bf16_t* dst, size_t n, hipStream_t s) { LAUNCH(f32_to_bf16_kernel, n, src, dst, n); }
+hipError_t launch_f32_to_bf16(const float* src, bf16_t* dst, size_t n, hipStream_t s, const float* cot_mul) {
+  LAUNCH(f32_to_bf16_kernel, n, src, dst, n, cot_scale_arg(cot_mul));
+}
+#ifdef DD_ACT_F16
+size_t cot_scale_scratch_floats() { return 2 * COT_BLOCKS; }
+hipError_t launch_cot_scale(const float* x, size_t rows, int C, int ld, const float* x2, size_t rows2, int C2, int ld2, float* part, float* scale2,
+                            hipStream_t s) {
+  if (!x || !part || !scale2 || C < 1 || ld < C || (x2 && (C2 < 1 || ld2 < C2))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cot_absmax_part_kernel, dim3(COT_BLOCKS), dim3(256), 0, s, x, rows, C, ld, part);
+  if (x2) hipLaunchKernelGGL(cot_absmax_part_kernel, dim3(COT_BLOCKS), dim3(256), 0, s, x2, rows2, C2, ld2, part + COT_BLOCKS);
+  hipLaunchKernelGGL(cot_absmax_final_kernel, dim3(1), dim3(64), 0, s, (const float*)part, x2 ? 2 * COT_BLOCKS : COT_BLOCKS, scale2);
+  return hipGetLastError();
+}
+hipError_t launch_cot_mul(float* x, size_t rows, int C, int ld, const float* mul, hipStream_t s) {
+  if (!x || !mul || C < 1 || ld < C) return hipErrorInvalidValue;
+  LAUNCH(cot_mul_kernel, rows * (size_t)C, x, rows, C, ld, mul);
+}
+#endif
 hipError_t launch_fill_f32(float* dst, float v, size_t n, hipStream_t s) { LAUNCH(fill_kernel, n, dst, v, n); }
 hipError_t launch_sinusoid_f32(const float* x, float* out, int n, int dim, int ld, int off, int flip, hipStream_t s) {
   LAUNCH(sinusoid_kernel, (size_t)n * (dim / 2), x, out, n, dim, ld, off, flip);

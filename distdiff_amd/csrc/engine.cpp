@@ -27,6 +27,21 @@ void check_batch(dd_engine* E, int B) {
   if (!E->finalized) throw std::runtime_error("dd_finalize_weights has not been called");
 }
 
+// Cotangent scale of the fp16 build (common.h: CotScale).  cot_normalise computes {s, 1 / s} from the fp32 cotangent(s) in front of a
+// reverse program and returns the device pointer to s for the entry kernel; cot_inv(that) is what the exit kernel takes.  The bf16
+// build launches nothing and hands null to both.
+#ifdef DD_ACT_F16
+const float* cot_normalise(dd_engine* E, const float* g, size_t rows, int C, int ld, hipStream_t s, const float* g2 = nullptr) {
+  HIPCHK(launch_cot_scale(g, rows, C, ld, g2, rows, C, ld, E->cot_part, E->cot_scale, s));
+  return E->cot_scale;
+}
+void cot_mul(float* x, size_t rows, int C, int ld, const float* mul, hipStream_t s) { HIPCHK(launch_cot_mul(x, rows, C, ld, mul, s)); }
+#else
+inline const float* cot_normalise(dd_engine*, const float*, size_t, int, int, hipStream_t, const float* = nullptr) { return nullptr; }
+inline void cot_mul(float*, size_t, int, int, const float*, hipStream_t) {}
+#endif
+inline const float* cot_inv(const float* cs) { return cs ? cs + 1 : nullptr; }
+
 // UNet forward on instance k: z fp32 NCHW -> eps2 fp32 NHWC [2B*HW, ld] inside the slab
 void unet_fwd(dd_engine* E, int k, const float* z, int step_index, hipStream_t s, bool stash = true) {
   const dd_config& c = E->cfg;
@@ -62,16 +77,19 @@ void guide_features_out(dd_engine* E, const Ctx& gc, float* feats, hipStream_t s
   if (c.guide_kind == 1) HIPCHK(hipMemcpy2DAsync(feats, (size_t)f.C * 4, act_f32(gc, f), (size_t)f.ld * 4, (size_t)f.C * 4, f.rows, hipMemcpyDeviceToDevice, s));
   else HIPCHK(launch_gap_f32(act_f32(gc, f), f.ld, feats, nullptr, c.max_batch, f.H * f.W, f.C, use_max, s));
 }
-// cotangent of the features [B, D] fp32 -> gradient of the guide's output tensor (reverse of guide_features_out)
-void guide_features_grad_in(dd_engine* E, const Ctx& gc, const float* gfeat, hipStream_t s) {
+// cotangent of the features [B, D] fp32 -> gradient of the guide's output tensor (reverse of guide_features_out).  Returns the
+// cotangent scale the 16-bit ViT program was entered with (null: the fp32 guides, the bf16 build)
+const float* guide_features_grad_in(dd_engine* E, const Ctx& gc, const float* gfeat, hipStream_t s) {
   const dd_config& c = E->cfg;
   const Tn& f = E->guide.t[E->guide_feat];
   if (c.guide_kind == 1) {
     if (f.ld != f.C) throw std::runtime_error("ViT guide: feature dim must be a multiple of 8");
-    HIPCHK(launch_f32_to_bf16(gfeat, grad_ptr(gc, f), (size_t)f.rows * f.C, s));
-  } else {
-    HIPCHK(launch_gap_bwd_f32(gfeat, grad_f32(gc, f), f.ld, c.max_batch, f.H * f.W, f.C, nullptr, s));
+    const float* cs = cot_normalise(E, gfeat, f.rows, f.C, f.C, s);
+    HIPCHK(launch_f32_to_bf16(gfeat, grad_ptr(gc, f), (size_t)f.rows * f.C, s, cs));
+    return cs;
   }
+  HIPCHK(launch_gap_bwd_f32(gfeat, grad_f32(gc, f), f.ld, c.max_batch, f.H * f.W, f.C, nullptr, s));
+  return nullptr;
 }
 
 // guide forward from the decoded image of instance k (bicubic -> guide network -> features) -> feat [B, D]
@@ -102,16 +120,19 @@ void guide_vae_bwd(dd_engine* E, int k, float* g_x0, hipStream_t s) {
   const Tn& f = E->guide.t[E->guide_feat];
   // GAP^T; the ReLU mask of the last bottleneck is applied by that conv op's backward
   (void)f;
-  guide_features_grad_in(E, gc, E->inst[k].gfeat, s);
+  const float* gcs = guide_features_grad_in(E, gc, E->inst[k].gfeat, s);
   run_bwd(E->guide, gc);
   const Tn& gin = E->guide.t[E->guide_in];
   const Tn& img = E->vae.t[E->vae_out];
+  // the ViT program's exit is its own patch re-layout into the fp32 image gradient: unscaled in place (fp16 build only)
+  if (gcs) cot_mul(grad_f32(gc, gin), gin.rows, 3, gin.ld, cot_inv(gcs), s);
   // the guide (fp32) and VAE (bf16) gradient regions are disjoint parts of the shared gradient slab (see finalize)
-  HIPCHK(launch_bicubic_bwd_f32(grad_f32(gc, gin), gin.ld, grad_ptr(vc, img), 1, img.ld, c.max_batch, img.H, img.W, gin.H, gin.W, 3, s));
+  const float* cs = cot_normalise(E, grad_f32(gc, gin), gin.rows, 3, gin.ld, s);
+  HIPCHK(launch_bicubic_bwd_f32(grad_f32(gc, gin), gin.ld, grad_ptr(vc, img), 1, img.ld, c.max_batch, img.H, img.W, gin.H, gin.W, 3, s, cs));
   run_bwd(E->vae, vc);
   const Tn& vin = E->vae.t[E->vae_in];
   HIPCHK(launch_nhwc_to_nchw_f32(grad_ptr(vc, vin), 0, g_x0, c.max_batch, c.vae_latent_channels, c.latent_size, c.latent_size, vin.ld,
-                                 1.f / c.vae_scaling_factor, 0.f, 0, 0.f, 0.f, s));
+                                 1.f / c.vae_scaling_factor, 0.f, 0, 0.f, 0.f, s, cot_inv(cs)));
 }
 
 // The sampler step on the UNet output of instance k (kernels.h: StepParams lists its modes), and its VJP
@@ -180,17 +201,27 @@ void guided_forward(dd_engine* E, int k, const float* z_in, int step_index, cons
 }
 
 // reverse of guided_forward: given g_znext (may be null) returns g_z (fp32 NCHW) in g_z_out
-void guided_backward(dd_engine* E, int k, int step_index, const float* g_znext, float* g_z_out, float* g_x0_tmp, hipStream_t s) {
+// (g_znext and g_x0_tmp are the engine's own buffers and are dead after this call: the fp16 build scales them in place)
+void guided_backward(dd_engine* E, int k, int step_index, float* g_znext, float* g_z_out, float* g_x0_tmp, hipStream_t s) {
   const dd_config& c = E->cfg;
   const int HW = c.latent_size * c.latent_size;
   Run r{E, s};
   guide_vae_bwd(E, k, g_x0_tmp, s);
   Ctx uc = r.ctx(E->unet, E->inst[k].unet);
   uc.step_index = step_index;
+  // The UNet's reverse program is entered through the sampler step's VJP, which also writes the direct part of g_z: the fp16 build
+  // scales both of its fp32 inputs, so that g_z_out carries the scale until the UNet's part has been added, and unscales it at the end
+  const size_t zrows = (size_t)c.max_batch * c.unet_out_channels;
+  const float* cs = cot_normalise(E, g_x0_tmp, zrows, HW, HW, s, g_znext);
+  if (cs) {
+    cot_mul(g_x0_tmp, zrows, HW, HW, cs, s);
+    if (g_znext) cot_mul(g_znext, zrows, HW, HW, cs, s);
+  }
   sampler_step_bwd(E, k, uc, step_index, g_x0_tmp, g_znext, g_z_out, s);
   run_bwd(E->unet, uc);
   const Tn& in = E->unet.t[E->unet_in];
   HIPCHK(launch_dup_bwd(grad_ptr(uc, in), in.ld, g_z_out, c.max_batch, c.unet_in_channels, HW, 1, in.B == 2 * c.max_batch ? 2 : 1, s));
+  if (cs) cot_mul(g_z_out, (size_t)c.max_batch * c.unet_in_channels, HW, HW, cot_inv(cs), s);
 }
 
 void set_config_defaults(dd_config& c) {
@@ -211,6 +242,11 @@ void set_config_defaults(dd_config& c) {
 extern "C" {
 
 int dd_abi_version(void) { return DD_ABI_VERSION; }
+#ifdef DD_ACT_F16
+int dd_act_dtype(void) { return 1; }
+#else
+int dd_act_dtype(void) { return 0; }
+#endif
 
 int dd_create(const dd_config* cfg, dd_engine** out) {
   if (!cfg || !out) return DD_ERR_ARG;
@@ -221,6 +257,12 @@ int dd_create(const dd_config* cfg, dd_engine** out) {
   }
   if (cfg->unet_levels > DD_MAX_LEVELS || cfg->vae_levels > DD_MAX_LEVELS || cfg->guide_stages > DD_MAX_LEVELS || cfg->max_batch < 1)
     return DD_ERR_ARG;
+#ifdef DD_ACT_F16
+  if (cfg->unet_attn_fp8 || getenv("DD_ATTN_FP8")) {
+    fprintf(stderr, "dd_create: the fp16 library has no fp8 P.V attention (unet_attn_fp8 / DD_ATTN_FP8)\n");
+    return DD_ERR_ARG;
+  }
+#endif
   dd_engine* e = new dd_engine();
   e->cfg = *cfg;
   set_config_defaults(e->cfg);
@@ -343,6 +385,12 @@ int dd_finalize_weights(dd_engine* E) {
     // the CFG-rescale backward re-reads the UNet's forward output of its step: it must live in the instance slab
     if (E->unet.t[E->unet_out].transient) throw std::runtime_error("the UNet output is a transient tensor");
     E->rs_part = (float*)E->dmalloc(sampler_step_scratch_floats(B, L * L) * 4);
+#ifdef DD_ACT_F16
+    if (c.enable_grad) {
+      E->cot_part = (float*)E->dmalloc(cot_scale_scratch_floats() * 4);
+      E->cot_scale = (float*)E->dmalloc(2 * 4);
+    }
+#endif
     E->tr_slab = (char*)E->dmalloc(2 * std::max({E->unet.tr_max, E->vae.tr_max, E->guide.tr_max, E->venc.tr_max, E->text.tr_max, E->text2.tr_max, (size_t)256}));
     if (c.enable_grad) {
       // UNet gradients alone; VAE and guide gradients live side by side (bicubic^T bridges them)
@@ -944,11 +992,12 @@ int dd_unet_vjp(dd_engine* E, const float* z, int step_index, const float* g_eps
     Ctx uc = r.ctx(E->unet, E->inst[0].unet);
     uc.step_index = step_index;
     const Tn& out = E->unet.t[E->unet_out];
+    const float* cs = cot_normalise(E, g_eps2, (size_t)2 * B * c.unet_out_channels, HW, HW, s);
     HIPCHK(launch_nchw_f32_to_nhwc_bf16(g_eps2, grad_ptr(uc, out), 2 * B, c.unet_out_channels, c.latent_size, c.latent_size, out.ld, out.ld, 0,
-                                        1.f, s));
+                                        1.f, s, cs));
     run_bwd(E->unet, uc);
     const Tn& in = E->unet.t[E->unet_in];
-    HIPCHK(launch_dup_bwd(grad_ptr(uc, in), in.ld, g_z_out, B, c.unet_in_channels, HW, 0, in.B == 2 * B ? 2 : 1, s));
+    HIPCHK(launch_dup_bwd(grad_ptr(uc, in), in.ld, g_z_out, B, c.unet_in_channels, HW, 0, in.B == 2 * B ? 2 : 1, s, cot_inv(cs)));
   });
 }
 
@@ -963,11 +1012,12 @@ int dd_decode_vjp(dd_engine* E, const float* z, const float* g_image, float* g_z
     Run r{E, s};
     Ctx vc = r.ctx(E->vae, E->inst[0].vae);
     const Tn& img = E->vae.t[E->vae_out];
-    HIPCHK(launch_nchw_f32_to_nhwc_bf16(g_image, grad_ptr(vc, img), B, c.vae_out_channels, img.H, img.W, img.ld, img.ld, 0, 1.f, s));
+    const float* cs = cot_normalise(E, g_image, (size_t)B * c.vae_out_channels, img.H * img.W, img.H * img.W, s);
+    HIPCHK(launch_nchw_f32_to_nhwc_bf16(g_image, grad_ptr(vc, img), B, c.vae_out_channels, img.H, img.W, img.ld, img.ld, 0, 1.f, s, cs));
     run_bwd(E->vae, vc);
     const Tn& vin = E->vae.t[E->vae_in];
     HIPCHK(launch_nhwc_to_nchw_f32(grad_ptr(vc, vin), 0, g_z_out, B, c.vae_latent_channels, c.latent_size, c.latent_size, vin.ld,
-                                   1.f / c.vae_scaling_factor, 0.f, 0, 0.f, 0.f, s));
+                                   1.f / c.vae_scaling_factor, 0.f, 0, 0.f, 0.f, s, cot_inv(cs)));
   });
 }
 
@@ -983,9 +1033,9 @@ int dd_guide_vjp(dd_engine* E, const float* images, const float* g_feats, float*
     const Tn& gin = E->guide.t[E->guide_in];
     HIPCHK(launch_nchw_to_nhwc_f32(images, act_f32(gc, gin), B, 3, gin.H, gin.W, gin.ld, gin.ld, s));
     run_fwd(E->guide, gc);
-    guide_features_grad_in(E, gc, g_feats, s);
+    const float* cs = guide_features_grad_in(E, gc, g_feats, s);
     run_bwd(E->guide, gc);
-    HIPCHK(launch_nhwc_to_nchw_f32(grad_f32(gc, gin), 1, g_images_out, B, 3, gin.H, gin.W, gin.ld, 1.f, 0.f, 0, 0.f, 0.f, s));
+    HIPCHK(launch_nhwc_to_nchw_f32(grad_f32(gc, gin), 1, g_images_out, B, 3, gin.H, gin.W, gin.ld, 1.f, 0.f, 0, 0.f, 0.f, s, cot_inv(cs)));
   });
 }
 

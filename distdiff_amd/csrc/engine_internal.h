@@ -279,6 +279,7 @@ struct dd_engine {
   std::vector<float> sigma;
   float* coef_table_eta = nullptr; float* step_table_eta = nullptr;
   float eta = 0.f;
+  float* cot_part = nullptr; float* cot_scale = nullptr;   // fp16 build only: partials and {s, 1 / s} of the cotangent scale (launch_cot_scale)
   float* rs_part = nullptr;      // CFG rescale: block partials of the per-image reductions (scratch, consumed by the next kernel)
   dd_sampler_params sp{};
   int solver = 0;                // dd_set_schedule_s: 0 DDIM, 1 DPM-Solver++(2M)

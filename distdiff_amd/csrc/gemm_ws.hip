@@ -180,7 +180,7 @@ __device__ __forceinline__ void ws_wave(const ConvGemmParams& p, unsigned char* 
       for (int kc = 0; kc < WS_KC; ++kc)
 #pragma unroll
         for (int jn = 0; jn < NTW; ++jn) {
-          acc[jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[jn][kc], xf[kc], acc[jn], 0, 0, 0);
+          acc[jn] = mfma16(wreg[jn][kc], xf[kc], acc[jn]);
         }
       if (a < 3) {
         load_xf(slot, a + 1);

@@ -187,11 +187,13 @@ hipError_t launch_attention_gemm_bwd(const AttnParams& p, void* workspace, size_
 // fp32 guide below; both formats are instances of one kernel each (elementwise.hip).
 // NCHW fp32 [B,C,H,W] -> NHWC bf16 [B*H*W, ld] (channels >= C zero-filled up to Cpad); dup copies
 // the batch twice (CFG: cat[z, z]).  scale multiplies.
+// cot_mul (here and below): a device scalar the values are multiplied by on top of `scale`, or null -- the cotangent scale of the fp16
+// build at the entry of a reverse program, its inverse at the exit (launch_cot_scale); the bf16 build does not read it
 hipError_t launch_nchw_f32_to_nhwc_bf16(const float* src, bf16_t* dst, int B, int C, int H, int W, int Cpad, int ld,
-                                        int dup, float scale, hipStream_t s);
+                                        int dup, float scale, hipStream_t s, const float* cot_mul = nullptr);
 // NHWC (bf16 or fp32) [B*H*W, ld] -> NCHW fp32 [B,C,H,W];  out = in * scale + shift, optional clamp to [lo, hi]
 hipError_t launch_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int B, int C, int H, int W, int ld,
-                                   float scale, float shift, int clamp, float lo, float hi, hipStream_t s);
+                                   float scale, float shift, int clamp, float lo, float hi, hipStream_t s, const float* cot_mul = nullptr);
 // The sampler step (sampler_step.hip; generate_data.py:116-119 is its epsilon / DDIM mode): CFG mix, optional CFG rescale phi (Lin et al.
 // 2023; diffusers rescale_noise_cfg), the scheduler update, and its VJP.
 //   m = u + s (c - u),  m^ = m (phi sigma_c / sigma_m + 1 - phi) per image,  x0 = A_z z + A_m m^,  z' = B_z z + B_m m^ + c2m (x0 - x0_prev)
@@ -247,7 +249,8 @@ hipError_t launch_sampler_step_units(const StepParams& p, const uint64_t* unit_i
 hipError_t launch_sampler_step_bwd(const StepParams& p, const float* g_x0, const float* g_zprev, bf16_t* g_m2, float* g_z, hipStream_t s);
 // backward of cat[z, z] + NCHW->NHWC: g_z[b,c,pix] (+)= gin[b*HW+pix, c] + gin[(B+b)*HW+pix, c]   (halves = 2), or of the plain
 // layout change when the UNet input itself is not duplicated (halves = 1: the two CFG halves share their prefix, engine.cpp)
-hipError_t launch_dup_bwd(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, hipStream_t s);
+hipError_t launch_dup_bwd(const bf16_t* gin, int ld, float* g_z, int B, int C, int HW, int accumulate, int halves, hipStream_t s,
+                          const float* cot_mul = nullptr);
 // y = dy * (mask > 0)  (ReLU backward)
 hipError_t launch_mask_bf16(const bf16_t* dy, int ldd, const bf16_t* mask, int ldm, bf16_t* y, int ldy, int M, int C,
                             hipStream_t s);
@@ -310,7 +313,16 @@ hipError_t launch_transform_update(const float* z, const float* g, const float* 
 hipError_t launch_sub_scaled(const float* a, const float* g, float* out, size_t n, float rho, hipStream_t s);
 // NHWC bf16 [M, ld] (first C channels) -> NCHW fp32, used for gradients wrt latents
 // fp32 -> bf16 pack rows (weights upload helpers)
-hipError_t launch_f32_to_bf16(const float* src, bf16_t* dst, size_t n, hipStream_t s);
+hipError_t launch_f32_to_bf16(const float* src, bf16_t* dst, size_t n, hipStream_t s, const float* cot_mul = nullptr);
+#ifdef DD_ACT_F16
+// The cotangent scale of the fp16 build (common.h: CotScale): scale2 = {s, 1 / s}, s the power of two that puts the absolute maximum of
+// x[r * ld + c] (r < rows, c < C; and of x2 likewise, or null) into [2^7, 2^8), 1 for an all-zero cotangent.  Two stages, no atomics;
+// part: cot_scale_scratch_floats() floats.  launch_cot_mul: x *= *mul in place.
+size_t cot_scale_scratch_floats();
+hipError_t launch_cot_scale(const float* x, size_t rows, int C, int ld, const float* x2, size_t rows2, int C2, int ld2, float* part, float* scale2,
+                            hipStream_t s);
+hipError_t launch_cot_mul(float* x, size_t rows, int C, int ld, const float* mul, hipStream_t s);
+#endif
 // setup-time fp32 linear: y = act(x) W^T + b (time-embedding tables)
 hipError_t launch_linear_f32(const float* x, const float* W, const float* b, float* y, int M, int N, int K, int silu_in, hipStream_t s);
 hipError_t launch_fill_f32(float* dst, float v, size_t n, hipStream_t s);
@@ -374,7 +386,7 @@ hipError_t launch_maxpool3x3s2_bwd_f32(const float* x, const float* dy, float* d
 hipError_t launch_bicubic_f32(const float* src, int ld_s, float* dst, int ld_d, int B, int Hs, int Ws, int Hd, int Wd, int C, int Cpad,
                               hipStream_t s);
 hipError_t launch_bicubic_bwd_f32(const float* ddst, int ld_d, void* dsrc, int dsrc_bf16, int ld_s, int B, int Hs, int Ws, int Hd, int Wd,
-                                  int C, hipStream_t s);
+                                  int C, hipStream_t s, const float* cot_mul = nullptr);
 // global average (or max, model_utils.py:34-35) pool of fp32 rows -> f [B, C]; argmax [B, C] only for the max form
 hipError_t launch_gap_f32(const float* x, int ld, float* f, int* argmax, int B, int HW, int C, int use_max, hipStream_t s);
 hipError_t launch_gap_bwd_f32(const float* gf, float* dx, int ld, int B, int HW, int C, const int* argmax, hipStream_t s);

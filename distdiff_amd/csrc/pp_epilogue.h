@@ -65,14 +65,14 @@ __device__ __forceinline__ void pp_epilogue(const ConvGemmParams& p, f32x4 (&acc
         }
         float v0 = __builtin_fmaf(v[0], rs, b.x), v1 = __builtin_fmaf(v[1], rs, b.y), v2 = __builtin_fmaf(v[2], rs, b.z), v3 = __builtin_fmaf(v[3], rs, b.w);
         if (fl & CF_RES) {
-          v0 += __uint_as_float(q0 << 16); v1 += __uint_as_float(q0 & 0xffff0000u);
-          v2 += __uint_as_float(q1 << 16); v3 += __uint_as_float(q1 & 0xffff0000u);
+          add_res4(q0, q1, v0, v1, v2, v3);
         }
         if (fl & CF_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
         if (fl & CF_STATS) {
-          t1[0] += v0; t1[1] += v1; t1[2] += v2; t1[3] += v3;
-          t2[0] = __builtin_fmaf(v0, v0, t2[0]); t2[1] = __builtin_fmaf(v1, v1, t2[1]);
-          t2[2] = __builtin_fmaf(v2, v2, t2[2]); t2[3] = __builtin_fmaf(v3, v3, t2[3]);
+          DD_STORED4(v0, v1, v2, v3, u0, u1, u2, u3);
+          t1[0] += u0; t1[1] += u1; t1[2] += u2; t1[3] += u3;
+          t2[0] = __builtin_fmaf(u0, u0, t2[0]); t2[1] = __builtin_fmaf(u1, u1, t2[1]);
+          t2[2] = __builtin_fmaf(u2, u2, t2[2]); t2[3] = __builtin_fmaf(u3, u3, t2[3]);
         }
         if (fl & CF_ROWSTATS) {
           r1 += (v0 + v1) + (v2 + v3);

@@ -57,7 +57,7 @@ __device__ __forceinline__ void pp_kstep(f32x4 (&acc)[8][TN], const unsigned cha
     for (int a = 0; a < 8; ++a)
 #pragma unroll
       for (int jn = 0; jn < TN; ++jn)
-        acc[a][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[jn], xf[a], acc[a][jn], 0, 0, 0);
+        acc[a][jn] = mfma16(wf[jn], xf[a], acc[a][jn]);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_s_barrier();
   }

@@ -3,6 +3,33 @@
 #include <string.h>
 #include "kernels.h"
 
+#ifdef DD_ACT_F16
+// fp32 -> IEEE half, round to nearest even: NaN stays NaN (quiet), beyond 65504 + half an ulp goes to inf, subnormals are kept
+bf16_t host_f2bf(float f) {
+  uint32_t u; memcpy(&u, &f, 4);
+  const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return (bf16_t)(sign | 0x7e00u | ((a >> 13) & 0x3ffu));
+  if (a >= 0x47800000u) return (bf16_t)(sign | 0x7c00u);                       // >= 65536 (and inf); [65520, 65536) rounds up below
+  if (a < 0x38800000u) {                                                          // below 2^-14: subnormal half, units of 2^-24
+    if (a < 0x33000000u) return (bf16_t)sign;                                     // below 2^-25: zero (2^-25 itself ties to even = 0)
+    const int shift = 126 - (int)(a >> 23);                                       // 14 .. 24
+    const uint32_t m = (a & 0x7fffffu) | 0x800000u;
+    const uint32_t q = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    return (bf16_t)(sign | (q + (rem > half || (rem == half && (q & 1u)) ? 1u : 0u)));
+  }
+  const uint32_t r = a + 0xfffu + ((a >> 13) & 1u);                               // RNE at bit 13; a carry into the exponent is the right answer
+  return (bf16_t)(sign | ((r - 0x38000000u) >> 13));
+}
+float host_bf2f(bf16_t v) {
+  const uint32_t sign = ((uint32_t)v & 0x8000u) << 16, e = (v >> 10) & 0x1fu, m = v & 0x3ffu;
+  uint32_t u;
+  if (e == 0x1f) u = sign | 0x7f800000u | (m << 13);
+  else if (e) u = sign | ((e + 112u) << 23) | (m << 13);
+  else if (!m) u = sign;
+  else { float f = (float)m * 5.9604644775390625e-8f; memcpy(&u, &f, 4); u |= sign; }
+  float f; memcpy(&f, &u, 4); return f;
+}
+#else
 bf16_t host_f2bf(float f) {
   uint32_t u; memcpy(&u, &f, 4);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);  // NaN stays NaN
@@ -10,6 +37,7 @@ bf16_t host_f2bf(float f) {
   return (bf16_t)(u >> 16);
 }
 float host_bf2f(bf16_t v) { uint32_t u = ((uint32_t)v) << 16; float f; memcpy(&f, &u, 4); return f; }
+#endif
 
 int geglu_perm(int pr, int F) {
   const int group = pr >> 5, within = pr & 31;

@@ -58,6 +58,7 @@ class DDExpandArgs(C.Structure):
 def _declare(l):
     i, f = C.c_int, C.c_float
     l.dd_abi_version.argtypes = []
+    l.dd_act_dtype.argtypes = []
     l.dd_create.argtypes = [C.POINTER(DDConfig), C.POINTER(vp)]
     l.dd_destroy.argtypes = [vp]
     l.dd_destroy.restype = None
@@ -203,16 +204,25 @@ def batch_for_free_hbm(free_bytes, guided=True, latent_size=64):
 class Engine:
     """One engine per device. Mirrors the objects the reference builds at generate_data.py:863-922, 1100-1125."""
 
-    def __init__(self, cfg: EngineConfig, weights, enable_grad=True, max_guidance_period=2, device="cuda:0", layout=None, attn_fp8=False):
+    def __init__(self, cfg: EngineConfig, weights, enable_grad=True, max_guidance_period=2, device="cuda:0", layout=None, attn_fp8=False,
+                 act_dtype="bf16"):
         """attn_fp8: BASELINE configs[4]'s fp8 MFMA attention (P.V of the UNet's d = 64 heads in e4m3; dd_config.unet_attn_fp8).
+        act_dtype: 'bf16' | 'fp16', the 16-bit storage format of every activation, weight and gradient of the UNet / VAE / text / ViT
+        programs.  It is the library the engine is created in (_lib.lib(act_dtype): libdistdiff_hip.so or libdistdiff_hip_f16.so) and
+        every call of this engine goes through that library; engines of both kinds can live in one process.  The boundary is fp32
+        either way.  The fp16 library has no fp8 P.V attention: act_dtype='fp16' with attn_fp8 raises.
         weights: {"unet" | "vae" | "guide" | "text" | "text2": state dict} -- packed on this rank; or None with `layout` = the
         `weight_layout()` of the rank that has them: the engine is then built from the tensor shapes alone and its packed weight
         buffers are filled by `import_packed` (launcher.broadcast_packed_weights: one RCCL broadcast of the packed device buffers
         instead of every process loading its own copy, scripts/exps/expand_diff.sh:19-24)."""
         self.cfg = cfg
+        self._h = vp()
+        self.act_dtype = _lib.act_dtype_name(act_dtype)
+        if self.act_dtype == "fp16" and attn_fp8:
+            raise ValueError("act_dtype='fp16' with attn_fp8: the fp16 library has no fp8 P.V attention")
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
-        self.L = _lib.lib()
+        self.L = _lib.lib(self.act_dtype)
         self._h = vp()
         cc = _to_c_config(cfg, enable_grad, max_guidance_period, attn_fp8)
         self._chk(self.L.dd_create(C.byref(cc), C.byref(self._h)), "dd_create")

@@ -42,6 +42,9 @@ plain and direct-guidance step of the main loop adds sigma_t * N(0,1), so the ex
 first latent.  The step noise is counter-based under both --noise_rng settings -- generated inside the step kernel from (--seed, unit
 id, step index) -- so it never depends on how the run is packed; under `stream` the initial noise / e / b still come from the host
 generators.  The look-ahead steps inside transform guidance stay deterministic.  Not with --sampler dpmsolver++.
+`--act_dtype fp16` (default `bf16`) runs the UNet, VAE, text encoder and ViT guide in IEEE half instead of bf16 (three more mantissa
+bits; the fp16 build of the same kernels).  `--mixed_precision` stays accepted and ignored: the reference ignores
+it on this path too -- generate_data.py:1034-1040 sets `weight_dtype = torch.float16` whatever the flag says.
 The stage before the loop runs on the engine too: image latents come from the reference's cache
 `save/vae_embedding/<dataset>/<model>/image_latents.pt` when it exists and are otherwise produced by the HIP VAE encoder and
 written to that path in the same format (dataloader.py:788-811); class prompts go through the Hugging Face tokenizer of the
@@ -141,6 +144,10 @@ def parse_args(argv=None):
                    "e.g. 13.2 GB per image at 768x768; SDXL at 1024x1024: 4 or 2 --, the minimum over the ranks of a run); units (image, expand index) are independent")
     p.add_argument("--attn_fp8", action="store_true", help="BASELINE configs[4]: P.V of the UNet's d = 64 attention heads (SDXL) on the fp8 MFMA "
                    "(dd_config.unet_attn_fp8).  Off by default: the bf16 form is faster on MI355X and closer to fp32 (DESIGN.md Appendix A row 28)")
+    p.add_argument("--act_dtype", default="bf16", choices=["bf16", "fp16"],
+                   help="16-bit storage format of the UNet / VAE / text / ViT activations, weights and gradients: bf16 (default, libdistdiff_hip.so) "
+                   "or fp16 (IEEE half, what the reference runs in: libdistdiff_hip_f16.so, the same kernels compiled with -DDD_ACT_F16; "
+                   "DESIGN.md section 14).  The ranks of --gpus get it with the rest of the command line.  Not with --attn_fp8")
     p.add_argument("--data_root", type=str, default="data")
     p.add_argument("--gpus", type=int, default=1, help="spawn this many ranks (one per GPU) that shard the images like --total_split; "
                    "weights are loaded once on rank 0 and broadcast over RCCL")
@@ -159,6 +166,8 @@ def parse_args(argv=None):
         raise SystemExit("--eta must be in [0, 1]")
     if args.eta > 0.0 and args.sampler != "ddim":
         raise SystemExit("--eta > 0 is stochastic DDIM: it does not go with --sampler %s" % args.sampler)
+    if args.act_dtype == "fp16" and args.attn_fp8:
+        raise SystemExit("--act_dtype fp16 does not go with --attn_fp8: the fp16 library has no fp8 P.V attention")
     if not args.do_classifier_free_guidance:
         raise SystemExit("the engine always runs classifier-free guidance (the reference's type=bool flag cannot be switched off either)")
     return args
@@ -587,7 +596,8 @@ def build_engine(args, device=None, distributed=False):
     stash = max(1, args.guidance_period) if args.guidance_type == "transform_guidance" else 1
 
     def make_engine(cfg, weights, layout):
-        return Engine(cfg, weights, enable_grad=guided, max_guidance_period=stash, device=dev, layout=layout, attn_fp8=args.attn_fp8)
+        return Engine(cfg, weights, enable_grad=guided, max_guidance_period=stash, device=dev, layout=layout, attn_fp8=args.attn_fp8,
+                      **({"act_dtype": args.act_dtype} if getattr(args, "act_dtype", "bf16") != "bf16" else {}))
 
     if distributed:
         # rank 0 loads + packs once; the packed device buffers go to the other ranks in one RCCL broadcast (launcher.py)

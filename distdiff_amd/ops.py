@@ -2,6 +2,10 @@
 
 Used by the parity tests and for debugging; the production loop goes through distdiff_amd.engine.
 Tensors are NHWC bf16 (a [pixels, C] matrix) unless stated. Nothing here computes on the CPU.
+
+The 16-bit storage format is a property of the library (libdistdiff_hip.so: bf16, libdistdiff_hip_f16.so: IEEE half).  Every wrapper
+picks the library from the dtype of its activation tensor (torch.bfloat16 / torch.float16; packed weights: PackedConv(dtype=)), and
+outputs take that dtype; the plan queries without a tensor take it from the packed weights or a `dtype` keyword.
 """
 import ctypes as C
 
@@ -17,6 +21,11 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _L(t):
+    """the library whose storage format is the dtype of t (a tensor, a PackedConv or a torch dtype)"""
+    return _lib.lib(t if isinstance(t, torch.dtype) else t.dtype)
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
@@ -24,20 +33,21 @@ def _ptr(t):
 class PackedConv:
     """Device copy of pre-packed weights for one conv/linear (forward or dgrad form)."""
 
-    def __init__(self, w_oihw, pad, mode=0, geglu=False, bias=None, device="cuda"):
+    def __init__(self, w_oihw, pad, mode=0, geglu=False, bias=None, device="cuda", dtype=torch.bfloat16):
+        self.dtype = dtype                        # torch.bfloat16 | torch.float16: packed (host side, RNE) by the library of that format
         w = w_oihw.detach().float().contiguous().cpu()
         if w.dim() == 2:
             w = w[:, :, None, None].contiguous()
         Cout, Cin, KH, KW = w.shape
         out4 = (C.c_int * 4)()
-        L = _lib.lib()
+        L = _L(dtype)
         L.dd_pack_conv_weight(C.c_void_p(w.data_ptr()), Cout, Cin, KH, KW, pad, mode, int(geglu), None, None, out4)
         self.N, self.K, self.cin, self.ntaps = out4[0], out4[1], out4[2], out4[3]
         wp = np.zeros((self.N, self.K), dtype=np.uint16)
         tt = np.zeros((self.ntaps,), dtype=np.int32)
         L.dd_pack_conv_weight(C.c_void_p(w.data_ptr()), Cout, Cin, KH, KW, pad, mode, int(geglu),
                               wp.ctypes.data_as(C.c_void_p), tt.ctypes.data_as(C.c_void_p), out4)
-        self.w = torch.from_numpy(wp.view(np.int16)).to(device).view(torch.bfloat16)
+        self.w = torch.from_numpy(wp.view(np.int16)).to(device).view(dtype)
         self.taptab = torch.from_numpy(tt).to(device)
         self.taptab_host = tt.copy()              # host copy: contract checks without a device round trip (conv_gemm); read-only
         self.taptab_host.setflags(write=False)
@@ -128,7 +138,7 @@ def _conv_gemm_params(x, pk, B, H, W, Ho, Wo, stride=1, shift=0, parity=0, res=N
     if pk.ntaps == 1 and stride == 1 and (H, W) == (Ho, Wo) and shift == 0 and int(pk.taptab_host[0]) != ((32 << 6) | 32):
         raise RuntimeError("conv_gemm: a one-tap stride-1 launch must be the centre tap (got %#x)" % int(pk.taptab_host[0]))
     if y is None and not dry:
-        y = torch.empty((M, ncols), device=x.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+        y = torch.empty((M, ncols), device=x.device, dtype=torch.float32 if out_f32 else pk.dtype)
     p.x, p.w, p.taptab, p.y = _ptr(x), _ptr(pk.w), _ptr(pk.taptab), _ptr(y)
     p.x_ld = x_ld if x_ld is not None else (x.stride(0) if x is not None else pk.cin)
     p.y_ld = y.stride(0) if y is not None else ncols
@@ -181,8 +191,8 @@ def conv_gemm(x, pk, B, H, W, Ho, Wo, *args, check_device_taps=False, **kw):
     launcher picks for this shape cannot emit them).  Keywords: _conv_gemm_params."""
     p, cap, y, _keep = _conv_gemm_params(x, pk, B, H, W, Ho, Wo, *args, **kw)
     if check_device_taps:      # synchronous: the tap contract against the DEVICE table (dd_op_conv_gemm_check)
-        check(_lib.lib().dd_op_conv_gemm_check(C.byref(p), _stream()), "conv_gemm tap table check")
-    check(_lib.lib().dd_op_conv_gemm(C.byref(p), cap, _stream()), "conv_gemm")
+        check(_L(pk).dd_op_conv_gemm_check(C.byref(p), _stream()), "conv_gemm tap table check")
+    check(_L(pk).dd_op_conv_gemm(C.byref(p), cap, _stream()), "conv_gemm")
     return y
 
 
@@ -194,7 +204,7 @@ def conv_gemm_kind(x, pk, B, H, W, Ho, Wo, *args, **kw):
     own decision, nothing is launched or allocated).  Buffers may be left out: x / y = None mean contiguous rows, res / stats /
     ln_stats / rowpart = True mean "present".  Raises for a problem the launcher refuses."""
     p, cap, _y, _keep = _conv_gemm_params(x, pk, B, H, W, Ho, Wo, *args, dry=True, **kw)
-    kind = _lib.lib().dd_op_conv_gemm_kind(C.byref(p), cap)
+    kind = _L(pk).dd_op_conv_gemm_kind(C.byref(p), cap)
     if kind < 0:
         raise RuntimeError("conv_gemm_kind: the launcher refuses this problem (status %d)" % kind)
     return kind
@@ -210,7 +220,7 @@ def conv_gemm_plan(x, pk, B, H, W, Ho, Wo, *args, **kw):
     kinds; split is the split-K (the chunk split at the 8 x 8 halo level) in use, 1 = none."""
     p, cap, _y, _keep = _conv_gemm_params(x, pk, B, H, W, Ho, Wo, *args, dry=True, **kw)
     out4 = (C.c_int * 4)()
-    kind = _lib.lib().dd_op_conv_gemm_plan(C.byref(p), cap, out4)
+    kind = _L(pk).dd_op_conv_gemm_plan(C.byref(p), cap, out4)
     if kind < 0:
         raise RuntimeError("conv_gemm_plan: the launcher refuses this problem (status %d)" % kind)
     form = None
@@ -224,7 +234,7 @@ def groupnorm(x, gamma, beta, B, HW, G, eps, silu, dy=None, stats=None, chan_par
     is added to it in place (GroupNormParams.accumulate) and it is returned.  y / dx: write the forward result / the gradient there (a
     column view of a wider buffer is fine) instead of into a fresh tensor."""
     Cc = x.shape[1]
-    L = _lib.lib()
+    L = _L(x)
     p = GroupNormParams()
     if y is None:
         y = torch.empty(x.shape, device=x.device, dtype=x.dtype)
@@ -256,14 +266,14 @@ def layernorm_stats(x, eps, rowpart=None, spans=0):
     p.x, p.x_ld, p.stats, p.M, p.C, p.eps = _ptr(x), x.stride(0), _ptr(stats), M, Cc, eps
     if rowpart is not None:
         p.rowpart, p.rowpart_ld, p.spans = _ptr(rowpart), rowpart.stride(0) // 2, spans
-    check(_lib.lib().dd_op_layernorm_fwd(C.byref(p), _stream()), "ln_stats")
+    check(_L(x).dd_op_layernorm_fwd(C.byref(p), _stream()), "ln_stats")
     return stats
 
 
 def layernorm(x, gamma, beta, eps, dy=None, stats=None, accumulate_into=None, y=None, dx=None):
     """Forward (y, stats), or with dy the input-gradient dx; accumulate_into, y and dx as for groupnorm (LayerNormParams.accumulate)."""
     M, Cc = x.shape
-    L = _lib.lib()
+    L = _L(x)
     p = LayerNormParams()
     if y is None:
         y = torch.empty(x.shape, device=x.device, dtype=x.dtype)
@@ -285,7 +295,7 @@ def layernorm(x, gamma, beta, eps, dy=None, stats=None, accumulate_into=None, y=
 
 def _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, causal=False, q_prescaled=False, pv_fp8=False, no_shortk=False):
     p = AttnParams()
-    o = torch.zeros((B * Nq, H * D), device=q.device, dtype=torch.bfloat16)
+    o = torch.zeros((B * Nq, H * D), device=q.device, dtype=q.dtype)
     lse = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
     p.q, p.k, p.v, p.o, p.lse = _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse)
     p.ldq, p.ldk, p.ldv, p.ldo = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
@@ -300,7 +310,7 @@ def _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, causal=False, q_prescaled=
 def _attn_bwd_params(p, o, d_o, need_dkv=True):
     """adds the backward's buffers to p; returns (dq, dk, dv, delta): delta only has to stay alive"""
     dq = torch.zeros_like(o)
-    dk = torch.zeros((p.B * p.Nk, p.H * p.D), device=o.device, dtype=torch.bfloat16) if need_dkv else None
+    dk = torch.zeros((p.B * p.Nk, p.H * p.D), device=o.device, dtype=o.dtype) if need_dkv else None
     dv = torch.zeros_like(dk) if need_dkv else None
     delta = torch.empty((p.B, p.H, p.Nq), device=o.device, dtype=torch.float32)
     p.d_o, p.lddo, p.dq, p.lddq, p.delta = _ptr(d_o), d_o.stride(0), _ptr(dq), dq.stride(0), _ptr(delta)
@@ -311,7 +321,7 @@ def _attn_bwd_params(p, o, d_o, need_dkv=True):
 
 def _attn_scratch(q, Nq, Nk, D, ws_images):
     """(workspace, bytes, tap1x1, partial, bytes) of the dd_op_attention* argument lists, and the tensors behind them"""
-    L = _lib.lib()
+    L = _L(q)
     L.dd_op_attention_gemm_workspace.restype = C.c_size_t
     if ws_images <= 0:
         return (None, C.c_size_t(0), None, None, C.c_size_t(0)), None
@@ -324,7 +334,7 @@ def _attn_scratch(q, Nq, Nk, D, ws_images):
 def attention_gemm(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, ws_images=8):
     """wide-head attention through the GEMM kernel (dd_op_attention_gemm_*): same arguments / results as `attention`.  ws_images: scratch
     for that many images (single-head layers then run min(ws_images, 8, B) images per launch)."""
-    L = _lib.lib()
+    L = _L(q)
     p, o, lse = _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale)
     sc, _keep = _attn_scratch(q, Nq, Nk, D, max(1, ws_images))
     check(L.dd_op_attention_gemm_fwd(C.byref(p), *sc, _stream()), "attn_gemm_fwd")
@@ -340,7 +350,7 @@ def attention(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, need_dkv=True, **flags)
     """q [B*Nq, >=H*D], k/v [B*Nk, >=H*D] bf16 (row strides taken from the tensors), on the flash kernels.  flags: causal; q_prescaled: q
     already carries 1/sqrt(D) * log2(e) (the engine folds it into the to_q weights); pass scale = ln 2 then.  pv_fp8 (D = 64, forward): the
     P.V product on the block-scaled fp8 MFMA (e4m3 probabilities and values); no_shortk."""
-    L = _lib.lib()
+    L = _L(q)
     p, o, lse = _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, **flags)
     check(L.dd_op_attention_fwd(C.byref(p), _stream()), "attn_fwd")
     if d_o is None:
@@ -353,9 +363,9 @@ def attention(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, need_dkv=True, **flags)
 ATTENTION_ROUTES = ("gemm", "shortk", "dma", "stream", "flash_bwd")      # dd_op_attention_plan
 
 
-def _attention_plan(p, ws_bytes, bwd):
+def _attention_plan(p, ws_bytes, bwd, dtype=torch.bfloat16):
     out = (C.c_int * 26)()
-    route = _lib.lib().dd_op_attention_plan(C.byref(p), ws_bytes, int(bwd), out)
+    route = _L(dtype).dd_op_attention_plan(C.byref(p), ws_bytes, int(bwd), out)
     if route < 0:
         raise RuntimeError("attention_plan: the launcher refuses this problem (status %d)" % route)
     return {"route": ATTENTION_ROUTES[route], "d": out[1], "qt": out[2], "kt": out[3], "dsplit": out[4], "ktw": out[5], "qtl": out[6],
@@ -367,27 +377,27 @@ def attention_planned(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, need_dkv=True, 
     """The launcher's one entry (dd_op_attention): `attention` with scratch for ws_images images offered (0: none), so that the planner
     may take the GEMM route.  Returns the results of `attention` and the plans (dd_op_attention_plan, asked with the same arguments) of
     the forward and, with d_o, the backward: dicts of route (ATTENTION_ROUTES), tile form, flags, group and launches."""
-    L = _lib.lib()
+    L = _L(q)
     p, o, lse = _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, **flags)
     sc, _keep = _attn_scratch(q, Nq, Nk, D, ws_images)
-    plans = [_attention_plan(p, sc[1], False)]
+    plans = [_attention_plan(p, sc[1], False, q.dtype)]
     check(L.dd_op_attention(C.byref(p), *sc, 0, _stream()), "attention fwd")
     if d_o is None:
         return (o, lse), plans
     dq, dk, dv, _delta = _attn_bwd_params(p, o, d_o, need_dkv)
-    plans.append(_attention_plan(p, sc[1], True))
+    plans.append(_attention_plan(p, sc[1], True, q.dtype))
     check(L.dd_op_attention(C.byref(p), *sc, 1, _stream()), "attention bwd")
     torch.cuda.synchronize()
     return (o, lse, dq, dk, dv), plans
 
 
-def to_nhwc_bf16(x_nchw, cpad=None):
-    """host/torch-side helper for tests: NCHW fp32 -> [B*H*W, Cpad] bf16 (zero padded)."""
+def to_nhwc_bf16(x_nchw, cpad=None, dtype=torch.bfloat16):
+    """host/torch-side helper for tests: NCHW fp32 -> [B*H*W, Cpad] bf16 (or `dtype`), zero padded."""
     B, Cc, H, W = x_nchw.shape
     cpad = cpad or Cc
     y = torch.zeros((B, H, W, cpad), dtype=torch.float32)
     y[..., :Cc] = x_nchw.permute(0, 2, 3, 1)
-    return y.reshape(B * H * W, cpad).to(torch.bfloat16)
+    return y.reshape(B * H * W, cpad).to(dtype)
 
 
 def from_nhwc(y, B, H, W):

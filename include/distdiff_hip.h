@@ -49,13 +49,13 @@ enum dd_status { DD_OK = 0, DD_ERR_ARG = -1, DD_ERR_HIP = -2, DD_ERR_STATE = -3,
 /* Layout version of the structs and argument lists of this header and distdiff_hip_ops.h.  A caller sets dd_config.abi_version =
  * DD_ABI_VERSION (after zero-initialising the struct: every struct of this ABI must be zero-initialised, new fields are appended and
  * mean "off" at 0); dd_create refuses another value with DD_ERR_ARG, and dd_abi_version() tells what the loaded library was built
- * as.  10: dd_set_schedule_e (the schedule with eta in [0, 1]: stochastic DDIM), dd_denoise_step_n / dd_direct_guidance_n /
+ * as.  11: dd_act_dtype() is new (the 16-bit storage format the library was compiled for), no struct changed; 10: dd_set_schedule_e (the schedule with eta in [0, 1]: stochastic DDIM), dd_denoise_step_n / dd_direct_guidance_n /
  * dd_op_step_coefs_eta / dd_op_sampler_step_n are new, dd_randn_units takes the streams 16 + i, no struct changed; 9: dd_set_schedule_s (the schedule with a solver: 0 = DDIM, the sampler of version 8; 1 = DPM-Solver++(2M)), dd_denoise_step_h /
  * dd_direct_guidance_h / dd_op_step_coef_2m / dd_op_sampler_step_2m are new, no struct changed; 8: dd_sampler_params gained prediction_type /
  * guidance_rescale (0 = the sampler of version 7), the dd_op_sampler_step* entry points are new; 7: dd_expand_args gained seed / unit_ids / noise_mode / offset_noise / text_to_img (all 0 = the call of version 6), dd_randn_units
  * is new; 6: dd_config gained unet_attn_fp8 + abi_version, AttnParams gained no_shortk; 5 (unversioned): workspace_bytes in the dd_op_attention_gemm_* lists,
  * ConvGemmParams.wgroup_rows / wgroup_elems, AttnParams.pv_fp8. */
-#define DD_ABI_VERSION 10
+#define DD_ABI_VERSION 11
 
 typedef struct dd_config {
   /* UNet2DConditionModel (unet/config.json) */
@@ -159,6 +159,10 @@ typedef struct dd_expand_args {
 } dd_expand_args;
 
 int dd_abi_version(void);                     /* DD_ABI_VERSION the library was built with */
+/* The 16-bit storage format of activations, weights and gradients, fixed when the library is compiled: 0 = bf16 (libdistdiff_hip.so),
+ * 1 = IEEE half (libdistdiff_hip_f16.so, the same sources with -DDD_ACT_F16).  The engine ABI is fp32 at its boundary in both; the
+ * dd_op_* entry points take and return raw 16-bit tensors of this format.  The fp16 library refuses unet_attn_fp8 / AttnParams.pv_fp8. */
+int dd_act_dtype(void);
 int dd_create(const dd_config* cfg, dd_engine** out);   /* DD_ERR_ARG when cfg->abi_version != DD_ABI_VERSION */
 void dd_destroy(dd_engine* e);
 const char* dd_last_error(dd_engine* e);
