@@ -13,6 +13,9 @@
 // inside a 32-deep step is the permutation key = 32c + 16*(j>>2) + 4*(lane>>4) + (j&3), which is exactly the
 // 4-row block order ds_read_b64_tr_b16 delivers. Row stride of the LDS tiles is 2*DPK+32 bytes:
 // bank-conflict free for both read kinds (tools/lds_conflicts.py).
+// The steps the kernels share (geometry, fragment reads, staging functions, owner rows, score chains, mask, softmax, P.V loop,
+// row sum, row epilogue, fp8 P.V) are in attention_frag.h, whose header says which kernel uses which; this file holds the
+// kernels' own loops, the planner and the launcher.
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
@@ -21,57 +24,6 @@
 #include "attention_frag.h"
 
 namespace {
-
-// stage ROWS x DPK bf16 (zero padded beyond D columns / nvalid rows) into LDS with row stride S bytes
-// ONES: column D of the tile (a padding column) is set to 1.0, so that P.V also accumulates the softmax row sums (forward V tile)
-template <int ROWS, int DPK, bool ONES = false>
-__device__ __forceinline__ void stage_tile(unsigned char* lds, int S, const bf16_t* g, int ld, int nvalid, int D, int tid) {
-  constexpr int VPR = DPK / 8;
-  for (int idx = tid; idx < ROWS * VPR; idx += 256) {
-    const int r = idx / VPR, v = idx % VPR;
-    uint4 val = make_uint4(0, 0, 0, 0);
-    if (r < nvalid && v * 8 < D) val = *(const uint4*)(g + (size_t)r * ld + v * 8);
-    if (ONES && v * 8 == D) val.x = DD_ACT_ONE;
-    *(uint4*)(lds + r * S + v * 16) = val;
-  }
-}
-// register-staged variant: issue the global loads of a tile early, write them to LDS after the compute of the previous tile
-template <int ROWS, int DPK>
-struct TileRegs { uint4 v[(ROWS * (DPK / 8) + 255) / 256]; };
-template <int ROWS, int DPK, bool ONES = false>
-__device__ __forceinline__ void tile_load(TileRegs<ROWS, DPK>& t, const bf16_t* g, int ld, int nvalid, int D, int tid) {
-  constexpr int VPR = DPK / 8, N = (ROWS * VPR + 255) / 256;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const int idx = tid + i * 256;
-    const int r = idx / VPR, v = idx % VPR;
-    uint4 val = make_uint4(0, 0, 0, 0);
-    if (idx < ROWS * VPR && r < nvalid && v * 8 < D) val = *(const uint4*)(g + (size_t)r * ld + v * 8);
-    if (ONES && v * 8 == D) val.x = DD_ACT_ONE;
-    t.v[i] = val;
-  }
-}
-template <int ROWS, int DPK>
-__device__ __forceinline__ void tile_store(const TileRegs<ROWS, DPK>& t, unsigned char* lds, int S, int tid) {
-  constexpr int VPR = DPK / 8, N = (ROWS * VPR + 255) / 256;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const int idx = tid + i * 256;
-    const int r = idx / VPR, v = idx % VPR;
-    if (idx < ROWS * VPR) *(uint4*)(lds + r * S + v * 16) = t.v[i];
-  }
-}
-template <int DPK>
-__device__ __forceinline__ void load_row_frags(bf16x8* f, const bf16_t* g, bool valid, int D, int lane) {
-  const int gq = lane >> 4;
-#pragma unroll
-  for (int ks = 0; ks < DPK / 32; ++ks) {
-    const int d0 = ks * 32 + gq * 8;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (valid && d0 < D) v = *(const uint4*)(g + d0);
-    f[ks] = __builtin_bit_cast(bf16x8, v);
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // forward.  grid (ceil(Nq / QB), H, B), 256 threads. DSPLIT=1: each wave owns QT 16-query tiles;
@@ -93,52 +45,41 @@ __device__ __forceinline__ void load_row_frags(bf16x8* f, const bf16_t* g, bool 
 #endif
 template <int D, int QT, int KT, int DSPLIT, bool CAUSAL>
 __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams p) {
-  constexpr int DPK = (D + 31) / 32 * 32;
-  constexpr int KS = DPK / 32;
-  constexpr int DVT = (D + 15) / 16;
-  constexpr int DTW = DVT / DSPLIT;          // dv tiles per wave
-  constexpr int S = DPK * 2 + 32;
-  constexpr int NKT = KT / 16, NC = KT / 32;
-  constexpr int QB = (DSPLIT == 1 ? 4 : 1) * QT * 16;
+  using G = AttnStreamGeo<D, DSPLIT>;
+  constexpr int KS = G::KS, DTW = G::DTW, S = G::S, NKT = KT / 16, NC = KT / 32;
+  constexpr bool ONES = DSPLIT == 1 && attn_ones(D);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* Ks = smem;
-  unsigned char* Vs = smem + KT * S;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i16 = lane & 15, g = lane >> 4;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
   const int h = blockIdx.y, b = blockIdx.z;
-  const int qbase = blockIdx.x * QB + (DSPLIT == 1 ? wave * QT * 16 : 0);
-  const int dt0 = (DSPLIT == 1) ? 0 : wave * DTW;
+  const int dt0 = G::dt0(wave);
 
   bf16x8 qf[QT][KS];
-  int qrow[QT];
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    qrow[qt] = qbase + qt * 16 + i16;
-    const bool valid = qrow[qt] < p.Nq;
-    load_row_frags<DPK>(qf[qt], p.q + ((size_t)b * p.Nq + (valid ? qrow[qt] : 0)) * p.ldq + h * D, valid, D, lane);
-  }
+  OwnerRow qr[QT];
   f32x4 o[QT][DTW];
   float mrun[QT], lsum[QT];
   int klim[QT];   // first masked key of this lane's query row
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    klim[qt] = CAUSAL ? min(p.Nk, qrow[qt] + 1) : p.Nk;
+    qr[qt] = owner_row(G::row0(QT, wave) + qt * 16, p.Nq, lane);
+    owner_frags<D>(qf[qt], p.q, p.ldq, p.Nq, b, h, qr[qt], lane);
+  }
+#pragma unroll
+  for (int qt = 0; qt < QT; ++qt) {
+    klim[qt] = CAUSAL ? min(p.Nk, qr[qt].row + 1) : p.Nk;
     mrun[qt] = -INFINITY; lsum[qt] = 0.f;
 #pragma unroll
-    for (int dt = 0; dt < DTW; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < DTW; ++dt) o[qt][dt] = splat4(0.f);
   }
   const float sl2 = p.scale * LOG2E;
   const bf16_t* kg = p.k + (size_t)b * p.Nk * p.ldk + h * D;
   const bf16_t* vg = p.v + (size_t)b * p.Nk * p.ldv + h * D;
-
+  unsigned char* Ks = smem;
+  unsigned char* Vs = smem + KT * S;
   // K/V tiles are register-staged one tile ahead (global latency hides under the MFMAs of the current tile) for the small
   // head dims; d = 512 keeps the direct staging (its tile would need 64 staging VGPRs)
+  constexpr int DPK = G::DPK;
   constexpr bool PREFETCH = (DPK <= 160);
-  // head dims with a padded column inside the last 16-wide output tile (d = 40): that column of V is set to 1.0, so the P.V MFMAs
-  // also deliver the softmax row sums (of exactly the bf16 P the outputs are built from) and the 16 VALU adds per query tile and
-  // KV tile disappear -- the forward is VALU-bound at d = 40
-  constexpr bool ONES = DSPLIT == 1 && (D % 16) != 0 && (D % 8) == 0;
   TileRegs<KT, PREFETCH ? DPK : 32> kreg, vreg;
   if (PREFETCH) {
     tile_load<KT, PREFETCH ? DPK : 32>(kreg, kg, p.ldk, p.Nk, D, tid);
@@ -162,63 +103,15 @@ __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams 
       tile_load<KT, PREFETCH ? DPK : 32, ONES>(vreg, vg + (size_t)(k0 + KT) * p.ldv, p.ldv, p.Nk - k0 - KT, D, tid);
     }
     f32x4 st[QT][NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) st[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const bf16x8 kf = lds_row_frag(Ks, kt * 16 + i16, S, g + 4 * ks);
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) st[qt][kt] = mfma16(kf, qf[qt][ks], st[qt][kt]);
-      }
-    }
+    score_chains(st, Ks, S, qf, lane, [](int, int) { return splat4(0.f); });
     bf16x8 pf[QT][NC];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-      // softmax is VALU-bound at d = 40 (one exp per score): keep it to max + fma + exp + add per element
-      if constexpr (partial) {
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (k0 + kt * 16 + 4 * g + r >= klim[qt]) st[qt][kt][r] = -INFINITY;
-      }
-      float mx = st[qt][0][0];
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[qt][kt][r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mnew = fmaxf(mrun[qt], mx * sl2);           // running max in the scaled log2 domain (sl2 > 0)
-      const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
-      float ps = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(st[qt][kt][r], sl2, -mnew));
-          st[qt][kt][r] = e;
-          if (!ONES) ps += e;
-        }
-      if (!ONES) lsum[qt] = lsum[qt] * alpha + ps;
-      mrun[qt] = mnew;
-      if (__any(alpha != 1.f)) {                              // wave-uniform: skip the O rescale when no row max moved
-#pragma unroll
-        for (int dt = 0; dt < DTW; ++dt) o[qt][dt] *= alpha;
-      }
-#pragma unroll
-      for (int c = 0; c < NC; ++c) pf[qt][c] = pack_frag(st[qt][2 * c], st[qt][2 * c + 1]);
+      if constexpr (partial) mask_keys(st[qt], k0, klim[qt], g);
+      online_softmax<ONES>(st[qt], mrun[qt], lsum[qt], o[qt], sl2);
+      pack_probs(pf[qt], st[qt]);
     }
-#pragma unroll
-    for (int dt = 0; dt < DTW; ++dt)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const bf16x8 vf = lds_col_frag(Vs, 32 * c, S, dt0 + dt, lane);
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) o[qt][dt] = mfma16(vf, pf[qt][c], o[qt][dt]);
-      }
+    colfrag_mfma(o, Vs, S, pf, dt0, lane);
   };
   {
     int k0 = 0;
@@ -228,30 +121,10 @@ __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams 
   }
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    float l;
-    if (ONES) {
-      // row sums sit in the ones column: output row D % 16 of the last tile = lane group (D % 16) / 4, register (D % 16) % 4
-      l = __shfl(o[qt][DTW - 1][(D % 16) % 4], ((D % 16) / 4) * 16 + i16, 64);
-    } else {
-      l = lsum[qt];
-      l += __shfl_xor(l, 16, 64);
-      l += __shfl_xor(l, 32, 64);
-    }
-    if (qrow[qt] >= p.Nq) continue;
-    const float inv = 1.f / l;
-    bf16_t* op = p.o + ((size_t)b * p.Nq + qrow[qt]) * p.ldo + h * D;
-#pragma unroll
-    for (int dt = 0; dt < DTW; ++dt) {
-      const int dv = (dt0 + dt) * 16 + 4 * g;
-      if (dv < D) {
-        uint2 u;
-        u.x = pack2bf(o[qt][dt][0] * inv, o[qt][dt][1] * inv);
-        u.y = pack2bf(o[qt][dt][2] * inv, o[qt][dt][3] * inv);
-        *(uint2*)(op + dv) = u;
-      }
-    }
-    if (p.lse && g == 0 && (DSPLIT == 1 || wave == 0))
-      p.lse[((size_t)b * p.H + h) * p.Nq + qrow[qt]] = (mrun[qt] + log2f(l)) * 0.6931471805599453f;
+    const float l = row_sum<D, ONES>(lsum[qt], o[qt][DTW - 1], lane);
+    if (!qr[qt].valid()) continue;
+    store_row<D>(p.o + ((size_t)b * p.Nq + qr[qt].row) * p.ldo + h * D, o[qt], 1.f / l, dt0, g);
+    store_lse(p, b, h, qr[qt].row, mrun[qt], l, g == 0 && (DSPLIT == 1 || wave == 0));
   }
 }
 
@@ -280,27 +153,24 @@ __global__ __launch_bounds__(256, DD_AW_FWD(D)) void attn_fwd_kernel(AttnParams 
 // sums and the LSE stay as they are (bf16 MFMA, fp32).  tools/micro/pv_fp8.hip measured the UPPER bound of the gain on a register-only
 // loop: 1.18x; with the in-kernel quantisation pass and 90 KB of LDS (one 8-wave workgroup per CU) this form is not faster than the bf16
 // kernel and is not the default.  Accuracy: e4m3 carries 3 mantissa bits (tests/test_kernels_gpu.py states the tolerance).
-typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 template <int D, int QT, int KT, int NW, bool LZ, bool FP8 = false>
 __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_kernel(AttnParams p) {
   static_assert(!FP8 || (D == 64 && KT == 128 && LZ), "fp8 P.V: d = 64, 128-key tiles, lazy-reference softmax");
   using G = AttnLdsGeo<D>;
-  constexpr int DPK = G::DPK, KS = DPK / 32, DVT = (D + 15) / 16, S = G::RB, RG = G::RG, DG = G::DG;
+  constexpr int KS = G::KS, DVT = G::DVT, S = G::RB, RG = G::RG, DG = G::DG;
   constexpr int NKT = KT / 16, NC = KT / 32;
-  constexpr int QB = NW * QT * 16;
   constexpr int TILE = KT * S;                               // bytes of one K (or V) tile
   constexpr int NPM = KT * RG / 64;                          // DMA pieces (64 granules) per matrix and tile
   constexpr int NPW = (2 * NPM + NW - 1) / NW;               // ... per wave (K pieces first, then V)
   static_assert((KT * RG) % 64 == 0, "tile must be a whole number of 1 KB pieces");
-  constexpr bool ONES = (D % 16) != 0 && (D % 8) == 0;
+  constexpr bool ONES = attn_ones(D);
   constexpr unsigned OOR = 0xffffff00u;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];    // [buf][K tile | V tile] + 128 B of zeros
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int i16 = lane & 15, g = lane >> 4;
+  const int g = lane >> 4;
   const int h = blockIdx.y, b = blockIdx.z;
-  const int qbase = blockIdx.x * QB + wave * QT * 16;
 
   // ---- padding granules (and the tail behind the last row: the 64-wide K fragments / 16-wide V column tiles read past a row's end)
   for (int r = tid; r < 2 * 2 * KT; r += NW * 64) {              // rows of both buffers, K and V alike
@@ -313,12 +183,11 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
   unsigned char* const VQ = smem + 4 * TILE + 128;          // FP8: the staged V tile as e4m3, [d 64][lane group 4][32 keys] = 8 KB
 
   bf16x8 qf[QT][KS];
-  int qrow[QT];
+  OwnerRow qr[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    qrow[qt] = qbase + qt * 16 + i16;
-    const bool valid = qrow[qt] < p.Nq;
-    load_row_frags<DPK>(qf[qt], p.q + ((size_t)b * p.Nq + (valid ? qrow[qt] : 0)) * p.ldq + h * D, valid, D, lane);
+    qr[qt] = owner_row((blockIdx.x * NW + wave) * QT * 16 + qt * 16, p.Nq, lane);
+    owner_frags<D>(qf[qt], p.q, p.ldq, p.Nq, b, h, qr[qt], lane);
     if (LZ && !p.q_prescaled) {                            // Q not prescaled by the producer: fold scale * log2(e) in here (one more bf16 rounding)
       const float c = p.scale * LOG2E;
 #pragma unroll
@@ -333,16 +202,17 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
   }
   f32x4 o[QT][DVT];
   float mrun[QT], lsum[QT];
+  f32x4 negm[QT];                                           // LZ: -reference of this lane's query row, the start value of its score chains (else 0)
+  auto reset = [&] {
 #pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    mrun[qt] = -INFINITY; lsum[qt] = 0.f;
+    for (int qt = 0; qt < QT; ++qt) {
+      mrun[qt] = -INFINITY; lsum[qt] = 0.f; negm[qt] = splat4(0.f);
 #pragma unroll
-    for (int dt = 0; dt < DVT; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+      for (int dt = 0; dt < DVT; ++dt) o[qt][dt] = splat4(0.f);
+    }
+  };
+  reset();
   const float sl2 = p.scale * LOG2E;
-  f32x4 negm[QT];                                           // LZ: -reference of this lane's query row, the start value of its score chains
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) negm[qt] = f32x4{0.f, 0.f, 0.f, 0.f};
   const bf16_t* kg = p.k + (size_t)b * p.Nk * p.ldk + h * D;
   const bf16_t* vg = p.v + (size_t)b * p.Nk * p.ldv + h * D;
 
@@ -379,53 +249,15 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
     if (!PARTIAL && k0 + KT < p.Nk) issue_tile(k0 + KT, buf ^ 1);
     const unsigned char* Ks = smem + buf * 2 * TILE;
     const unsigned char* Vs = Ks + TILE;
-    if constexpr (FP8) {
-      // V tile -> e4m3 in the operand order of the probabilities: dword ((dt * 4 + g) * 16 + i16) * 8 + kt = V[16 kt + 4 g + r][16 dt + i16], r = 0 .. 3
-      // (everybody finished the previous tile's P.V in front of the barrier above; the barrier in front of this tile's P.V publishes it)
-      for (int w = tid; w < 64 * 4 * 8; w += NW * 64) {
-        const int kt = w & 7, d = ((w >> 9) << 4) + ((w >> 3) & 15), gg = (w >> 7) & 3;
-        const unsigned char* src = Vs + (16 * kt + 4 * gg) * S + d * 2;
-        const float f0 = bf2f(*(const bf16_t*)src), f1 = bf2f(*(const bf16_t*)(src + S)), f2 = bf2f(*(const bf16_t*)(src + 2 * S)), f3 = bf2f(*(const bf16_t*)(src + 3 * S));
-        int wv = __builtin_amdgcn_cvt_pk_fp8_f32(f0, f1, 0, false);
-        wv = __builtin_amdgcn_cvt_pk_fp8_f32(f2, f3, wv, true);
-        *(int*)(VQ + w * 4) = wv;
-      }
-    }
+    // FP8: (everybody finished the previous tile's P.V in front of the barrier above; the barrier in front of this tile's P.V publishes it)
+    if constexpr (FP8) fp8_quantise_v<NW * 64>(VQ, Vs, S, tid);
     f32x4 st[QT][NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) st[qt][kt] = LZ ? negm[qt] : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const bf16x8 kf = lds_row_frag(Ks, kt * 16 + i16, S, g + 4 * ks);
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) st[qt][kt] = mfma16(kf, qf[qt][ks], st[qt][kt]);
-      }
-    }
+    score_chains(st, Ks, S, qf, lane, [&](int qt, int) { return LZ ? negm[qt] : splat4(0.f); });
     bf16x8 pf[QT][NC];
     i32x8_t pf8[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-      if constexpr (PARTIAL) {                               // only the last tile of a ragged key count needs masking
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (k0 + kt * 16 + 4 * g + r >= p.Nk) st[qt][kt][r] = -INFINITY;
-      }
-      float mx = st[qt][0][0];
-      if (!LZ || FIRST || SAFE) {
-        mx = vmax3(mx, st[qt][0][1], st[qt][0][2]);
-        mx = vmax2(mx, st[qt][0][3]);
-#pragma unroll
-        for (int kt = 1; kt < NKT; ++kt) {
-          mx = vmax3(mx, st[qt][kt][0], st[qt][kt][1]);
-          mx = vmax3(mx, st[qt][kt][2], st[qt][kt][3]);
-        }
-        mx = vmax2(mx, __shfl_xor(mx, 16, 64));
-        mx = vmax2(mx, __shfl_xor(mx, 32, 64));
-      }
+      if constexpr (PARTIAL) mask_keys(st[qt], k0, p.Nk, g);  // only the last tile of a ragged key count needs masking
       if constexpr (LZ) {
         // The scores already are differences to the row's reference.  First tile (reference 0: plain scores): the reference becomes
         // the tile's row maximum.  Later tiles: the optimistic pass (SAFE = false) exponentiates them as they are -- no row maximum,
@@ -439,6 +271,8 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
 #else
         constexpr float LZ_SLACK = FP8 ? 6.f : 24.f;         // FP8: the probabilities must stay inside e4m3 (448)
 #endif
+        float mx = 0.f;
+        if constexpr (FIRST || SAFE) mx = row_max(st[qt]);
         bool rebase = FIRST;
         if constexpr (!FIRST && SAFE) rebase = __any(mx > LZ_SLACK);
         if (rebase) {
@@ -455,69 +289,22 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
           }
           mrun[qt] = (FIRST ? 0.f : mrun[qt]) + d;
           const float nm = -mrun[qt];
-          negm[qt] = f32x4{nm, nm, nm, nm};
+          negm[qt] = splat4(nm);
         }
-        float ps = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float e = __builtin_amdgcn_exp2f(st[qt][kt][r]);
-            st[qt][kt][r] = e;
-            if (!ONES) ps += e;
-          }
+        const float ps = exp2_scores<false, ONES>(st[qt], 1.f, 0.f);
         if (!ONES) lsum[qt] += ps;
       } else {
-      const float mnew = vmax2(mrun[qt], mx * sl2);           // running max in the scaled log2 domain (sl2 > 0)
-      const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
-      float ps = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(st[qt][kt][r], sl2, -mnew));
-          st[qt][kt][r] = e;
-          if (!ONES) ps += e;
-        }
-      if (!ONES) lsum[qt] = lsum[qt] * alpha + ps;
-      mrun[qt] = mnew;
-      if (__any(alpha != 1.f)) {                              // wave-uniform: skip the O rescale when no row max moved
-#pragma unroll
-        for (int dt = 0; dt < DVT; ++dt) o[qt][dt] *= alpha;
+        online_softmax<ONES>(st[qt], mrun[qt], lsum[qt], o[qt], sl2);
       }
-      }
-      if constexpr (FP8) {
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-          const int lo = __builtin_amdgcn_cvt_pk_fp8_f32(st[qt][kt][0], st[qt][kt][1], 0, false);
-          pf8[qt][kt] = __builtin_amdgcn_cvt_pk_fp8_f32(st[qt][kt][2], st[qt][kt][3], lo, true);
-        }
-      } else {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) pf[qt][c] = pack_frag(st[qt][2 * c], st[qt][2 * c + 1]);
-      }
+      if constexpr (FP8) pf8[qt] = fp8_pack_probs(st[qt]);
+      else pack_probs(pf[qt], st[qt]);
     }
     if constexpr (FP8) {
       __syncthreads();                                       // the e4m3 V tile is complete
-#pragma unroll
-      for (int dt = 0; dt < DVT; ++dt) {
-        const unsigned char* vq = VQ + ((dt * 4 + g) * 16 + i16) * 32;
-        const uint4 v0 = *(const uint4*)vq, v1 = *(const uint4*)(vq + 16);
-        const i32x8_t vf8 = {(int)v0.x, (int)v0.y, (int)v0.z, (int)v0.w, (int)v1.x, (int)v1.y, (int)v1.z, (int)v1.w};
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt)
-          o[qt][dt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(vf8, pf8[qt], o[qt][dt], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-      }
-      return;
+      fp8_pv(o, VQ, pf8, lane);
+    } else {
+      colfrag_mfma(o, Vs, S, pf, 0, lane);
     }
-#pragma unroll
-    for (int dt = 0; dt < DVT; ++dt)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const bf16x8 vf = lds_col_frag(Vs, 32 * c, S, dt, lane);
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) o[qt][dt] = mfma16(vf, pf[qt][c], o[qt][dt]);
-      }
   };
   using T_ = std::true_type;
   using F_ = std::false_type;
@@ -551,42 +338,16 @@ __global__ __launch_bounds__(NW * 64, FP8 ? 2 : DD_AW_FWD(D)) void attn_fwd_dma_
       }
       bad = __syncthreads_or(bad);
     }
-    if (bad) {
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-        mrun[qt] = -INFINITY; lsum[qt] = 0.f; negm[qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int dt = 0; dt < DVT; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      sweep(T_{});
-    }
+    if (bad) { reset(); sweep(T_{}); }
   } else {
     sweep(T_{});
   }
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    float l;
-    if (ONES) {
-      l = __shfl(o[qt][DVT - 1][(D % 16) % 4], ((D % 16) / 4) * 16 + i16, 64);
-    } else {
-      l = lsum[qt];
-      l += __shfl_xor(l, 16, 64);
-      l += __shfl_xor(l, 32, 64);
-    }
-    if (qrow[qt] >= p.Nq) continue;
-    const float inv = 1.f / l;
-    bf16_t* op = p.o + ((size_t)b * p.Nq + qrow[qt]) * p.ldo + h * D;
-#pragma unroll
-    for (int dt = 0; dt < DVT; ++dt) {
-      const int dv = dt * 16 + 4 * g;
-      if (dv < D) {
-        uint2 u;
-        u.x = pack2bf(o[qt][dt][0] * inv, o[qt][dt][1] * inv);
-        u.y = pack2bf(o[qt][dt][2] * inv, o[qt][dt][3] * inv);
-        *(uint2*)(op + dv) = u;
-      }
-    }
-    if (p.lse && g == 0) p.lse[((size_t)b * p.H + h) * p.Nq + qrow[qt]] = (mrun[qt] + log2f(l)) * 0.6931471805599453f;
+    const float l = row_sum<D, ONES>(lsum[qt], o[qt][DVT - 1], lane);
+    if (!qr[qt].valid()) continue;
+    store_row<D>(p.o + ((size_t)b * p.Nq + qr[qt].row) * p.ldo + h * D, o[qt], 1.f / l, 0, g);
+    store_lse(p, b, h, qr[qt].row, mrun[qt], l, g == 0);
   }
 }
 
@@ -622,13 +383,9 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(AttnParams p) {
 // need no subtraction per score (cdna_hip_programming.md, attention backward: "Row constants as the initial accumulator").
 template <int D, int QT, int KT, int DSPLIT, bool PS>
 __global__ __launch_bounds__(256, DD_AW_DQ(D)) void attn_bwd_dq_kernel(AttnParams p) {
-  constexpr int DPK = (D + 31) / 32 * 32;
-  constexpr int KS = DPK / 32;
-  constexpr int DVT = (D + 15) / 16;
-  constexpr int DTW = DVT / DSPLIT;
-  constexpr int S = DPK * 2 + 32;
+  using G = AttnStreamGeo<D, DSPLIT>;
+  constexpr int DPK = G::DPK, KS = G::KS, DTW = G::DTW, S = G::S;
   constexpr int NKT = KT / 16, NC = KT / 32;
-  constexpr int QB = (DSPLIT == 1 ? 4 : 1) * QT * 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Ks = smem;
   unsigned char* Vs = smem + KT * S;
@@ -636,19 +393,18 @@ __global__ __launch_bounds__(256, DD_AW_DQ(D)) void attn_bwd_dq_kernel(AttnParam
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i16 = lane & 15, g = lane >> 4;
   const int h = blockIdx.y, b = blockIdx.z;
-  const int qbase = blockIdx.x * QB + (DSPLIT == 1 ? wave * QT * 16 : 0);
-  const int dt0 = (DSPLIT == 1) ? 0 : wave * DTW;
+  const int qbase = G::row0(QT, wave), dt0 = G::dt0(wave);
 
   bf16x8 qf[QT][KS], dof[QT][KS];
   int qrow[QT];
   float lse2[QT], delta[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    qrow[qt] = qbase + qt * 16 + i16;
-    const bool valid = qrow[qt] < p.Nq;
-    const size_t r = (size_t)b * p.Nq + (valid ? qrow[qt] : 0);
-    load_row_frags<DPK>(qf[qt], p.q + r * p.ldq + h * D, valid, D, lane);
-    load_row_frags<DPK>(dof[qt], p.d_o + r * p.lddo + h * D, valid, D, lane);
+    const OwnerRow orow = owner_row(qbase + qt * 16, p.Nq, lane);
+    qrow[qt] = orow.row;
+    const bool valid = orow.valid();
+    owner_frags<D>(qf[qt], p.q, p.ldq, p.Nq, b, h, orow, lane);
+    owner_frags<D>(dof[qt], p.d_o, p.lddo, p.Nq, b, h, orow, lane);
     const size_t si = ((size_t)b * p.H + h) * p.Nq + (valid ? qrow[qt] : 0);
     lse2[qt] = valid ? p.lse[si] * LOG2E : 0.f;
     delta[qt] = valid ? p.delta[si] : 0.f;
@@ -747,16 +503,7 @@ __global__ __launch_bounds__(256, DD_AW_DQ(D)) void attn_bwd_dq_kernel(AttnParam
   for (int qt = 0; qt < QT; ++qt) {
     if (qrow[qt] >= p.Nq) continue;
     bf16_t* op = p.dq + ((size_t)b * p.Nq + qrow[qt]) * p.lddq + h * D;
-#pragma unroll
-    for (int dt = 0; dt < DTW; ++dt) {
-      const int dv = (dt0 + dt) * 16 + 4 * g;
-      if (dv < D) {
-        uint2 u;
-        u.x = pack2bf(dq[qt][dt][0] * p.scale, dq[qt][dt][1] * p.scale);
-        u.y = pack2bf(dq[qt][dt][2] * p.scale, dq[qt][dt][3] * p.scale);
-        *(uint2*)(op + dv) = u;
-      }
-    }
+    store_row<D>(op, dq[qt], p.scale, dt0, g);
   }
 }
 
@@ -767,13 +514,9 @@ __global__ __launch_bounds__(256, DD_AW_DQ(D)) void attn_bwd_dq_kernel(AttnParam
 // ------------------------------------------------------------------------------------------------
 template <int D, int KTW, int QTL, int DSPLIT, bool PS>
 __global__ __launch_bounds__(256, DD_AW_DKV(D)) void attn_bwd_dkv_kernel(AttnParams p) {
-  constexpr int DPK = (D + 31) / 32 * 32;
-  constexpr int KS = DPK / 32;
-  constexpr int DVT = (D + 15) / 16;
-  constexpr int DTW = DVT / DSPLIT;
-  constexpr int S = DPK * 2 + 32;
+  using G = AttnStreamGeo<D, DSPLIT>;
+  constexpr int DPK = G::DPK, KS = G::KS, DTW = G::DTW, S = G::S;
   constexpr int NQT = QTL / 16, NC = QTL / 32;
-  constexpr int KB = (DSPLIT == 1 ? 4 : 1) * KTW * 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Qs = smem;
   unsigned char* Os = smem + QTL * S;
@@ -782,18 +525,16 @@ __global__ __launch_bounds__(256, DD_AW_DKV(D)) void attn_bwd_dkv_kernel(AttnPar
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i16 = lane & 15, g = lane >> 4;
   const int h = blockIdx.y, b = blockIdx.z;
-  const int kbase = blockIdx.x * KB + (DSPLIT == 1 ? wave * KTW * 16 : 0);
-  const int dt0 = (DSPLIT == 1) ? 0 : wave * DTW;
+  const int kbase = G::row0(KTW, wave), dt0 = G::dt0(wave);
 
   bf16x8 kf[KTW][KS], vf[KTW][KS];
   int krow[KTW];
 #pragma unroll
   for (int kt = 0; kt < KTW; ++kt) {
-    krow[kt] = kbase + kt * 16 + i16;
-    const bool valid = krow[kt] < p.Nk;
-    const size_t r = (size_t)b * p.Nk + (valid ? krow[kt] : 0);
-    load_row_frags<DPK>(kf[kt], p.k + r * p.ldk + h * D, valid, D, lane);
-    load_row_frags<DPK>(vf[kt], p.v + r * p.ldv + h * D, valid, D, lane);
+    const OwnerRow orow = owner_row(kbase + kt * 16, p.Nk, lane);
+    krow[kt] = orow.row;
+    owner_frags<D>(kf[kt], p.k, p.ldk, p.Nk, b, h, orow, lane);
+    owner_frags<D>(vf[kt], p.v, p.ldv, p.Nk, b, h, orow, lane);
   }
   f32x4 dk[KTW][DTW], dv[KTW][DTW];
 #pragma unroll
@@ -895,19 +636,8 @@ __global__ __launch_bounds__(256, DD_AW_DKV(D)) void attn_bwd_dkv_kernel(AttnPar
     if (krow[kt] >= p.Nk) continue;
     bf16_t* kp = p.dk + ((size_t)b * p.Nk + krow[kt]) * p.lddk + h * D;
     bf16_t* vp = p.dv + ((size_t)b * p.Nk + krow[kt]) * p.lddv + h * D;
-#pragma unroll
-    for (int dt = 0; dt < DTW; ++dt) {
-      const int d = (dt0 + dt) * 16 + 4 * g;
-      if (d < D) {
-        uint2 u;
-        u.x = pack2bf(dk[kt][dt][0] * p.scale, dk[kt][dt][1] * p.scale);
-        u.y = pack2bf(dk[kt][dt][2] * p.scale, dk[kt][dt][3] * p.scale);
-        *(uint2*)(kp + d) = u;
-        u.x = pack2bf(dv[kt][dt][0], dv[kt][dt][1]);
-        u.y = pack2bf(dv[kt][dt][2], dv[kt][dt][3]);
-        *(uint2*)(vp + d) = u;
-      }
-    }
+    store_row<D>(kp, dk[kt], p.scale, dt0, g);
+    store_row<D>(vp, dv[kt], 1.f, dt0, g);
   }
 }
 
@@ -1005,7 +735,7 @@ AttnPlan attention_plan(const AttnParams& p, const AttnScratch& sc, bool bwd, in
     if ((p.lddo & 7) || (p.lddq & 3) || !p.delta || !p.lse || !p.d_o || !p.o || form < 0) return plan;
     if (p.dk && ((p.lddk & 3) || (p.lddv & 3))) return plan;
     const AttnForm& f = ATTN_FORMS[form];
-    const int span = (f.dsplit == 1 ? 4 : 1) * 16, S = attn_dpk(f.d) * 2 + 32;      // rows of a 16-row tile over the workgroup, LDS row bytes
+    const int span = attn_stream_span(f.dsplit), S = attn_stream_row_bytes(f.d);    // rows of a 16-row tile over the workgroup, LDS row bytes
     plan.route = ATTN_FLASH_BWD; plan.form = form; plan.waves = 4; plan.prescaled = p.q_prescaled != 0;
     plan.launch[0] = delta_launch(p);
     plan.launch[1] = AttnLaunch{grid(p.Nq, span * f.dq_qt), 256, (size_t)2 * f.dq_kt * S};
@@ -1043,7 +773,7 @@ AttnPlan attention_plan(const AttnParams& p, const AttnScratch& sc, bool bwd, in
     return plan;
   }
   plan.route = ATTN_STREAM; plan.waves = 4; plan.causal = p.causal != 0;
-  plan.launch[0] = AttnLaunch{grid(p.Nq, (f.dsplit == 1 ? 4 : 1) * f.qt * 16), 256, (size_t)2 * f.kt * (attn_dpk(f.d) * 2 + 32)};
+  plan.launch[0] = AttnLaunch{grid(p.Nq, attn_stream_span(f.dsplit) * f.qt), 256, (size_t)2 * f.kt * attn_stream_row_bytes(f.d)};
   return plan;
 }
 
