@@ -133,6 +133,7 @@ OPS_SYMBOLS = [
     "dd_op_maxpool3x3s2_bwd_f32", "dd_op_bicubic_f32", "dd_op_bicubic_bwd_f32", "dd_op_gap_f32", "dd_op_gap_bwd_f32", "dd_op_nchw_to_nhwc_f32",
     "dd_op_step_coefs", "dd_op_sampler_step_scratch_floats", "dd_op_sampler_step", "dd_op_sampler_step_bwd",
     "dd_op_step_coef_2m", "dd_op_sampler_step_2m", "dd_op_step_coefs_eta", "dd_op_sampler_step_n",
+    "dd_op_step_coefs_sde", "dd_op_step_coef_2m_sde", "dd_op_sampler_step_2m_n",
     "dd_debug_tensor", "dd_debug_num_tensors", "dd_debug_fusion_plan", "dd_debug_set_image", "dd_debug_set_images",
 ]
 ENGINE_SYMBOLS = [
@@ -142,6 +143,7 @@ ENGINE_SYMBOLS = [
     "dd_set_prompt", "dd_set_added_cond", "dd_vae_encode", "dd_text_encode", "dd_text_encode_tower", "dd_set_sample_weights", "dd_get_image_scores", "dd_declare_tensor", "dd_packed_bytes", "dd_export_packed", "dd_import_packed", "dd_profile_enable", "dd_profile_read", "dd_workspace_bytes", "dd_flops_last", "dd_randn_units",
     "dd_set_schedule_s", "dd_denoise_step_h", "dd_direct_guidance_h",
     "dd_set_schedule_e", "dd_denoise_step_n", "dd_direct_guidance_n",
+    "dd_set_schedule_sde", "dd_denoise_step_hn", "dd_direct_guidance_hn",
 ]
 
 
@@ -180,6 +182,9 @@ def _declare(l):
     l.dd_op_sampler_step_2m.argtypes = [vp, i, vp, vp, f, vp, vp, i, i, i, vp, vp, i, f, vp, vp, vp]
     l.dd_op_step_coefs_eta.argtypes = [i, C.c_double, C.c_double, C.c_double, vp]
     l.dd_op_sampler_step_n.argtypes = [vp, i, vp, vp, f, C.c_uint64, i, vp, vp, vp, i, i, i, vp, vp, i, f, vp, vp, vp]
+    l.dd_op_step_coefs_sde.argtypes = [i, C.c_double, C.c_double, C.c_double, vp]
+    l.dd_op_step_coef_2m_sde.argtypes = [i, i, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+    l.dd_op_sampler_step_2m_n.argtypes = [vp, i, vp, vp, f, vp, f, C.c_uint64, i, vp, vp, vp, i, i, i, vp, vp, i, f, vp, vp, vp]
     l.dd_op_sumpool2x2.argtypes = [vp, i, vp, i, i, i, i, i, i, vp]
     l.dd_op_geglu_bwd.argtypes = [vp, i, vp, i, vp, i, i, i, vp]
     l.dd_op_maxpool3x3s2.argtypes = [vp, vp, i, i, i, i, vp]

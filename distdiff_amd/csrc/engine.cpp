@@ -147,8 +147,8 @@ StepParams step_params(dd_engine* E, int k, int step_index) {
   p.stats = E->inst[k].rs_stats; p.part = E->rs_part;
   return p;
 }
-// the noise of a stochastic step (eta > 0): the caller's tensor [B,C,L,L], or generated inside the step kernel from (seed, unit id of
-// the row, stream 16 + step index) -- what dd_randn_units writes for that stream.  Neither: the eta = 0 step
+// the noise of a stochastic step (eta > 0 or sde_eta > 0): the caller's tensor [B,C,L,L], or generated inside the step kernel from (seed, unit id of
+// the row, stream 16 + step index) -- what dd_randn_units writes for that stream.  Neither: the deterministic step
 struct StepNoise {
   const float* noise = nullptr; const uint64_t* unit_ids = nullptr; uint64_t seed = 0;
   bool on() const { return noise || unit_ids; }
@@ -158,18 +158,19 @@ void sampler_step(dd_engine* E, int k, const float* z, int step_index, const flo
                   const StepNoise& sn = StepNoise()) {
   StepParams p = step_params(E, k, step_index);
   p.z = z; p.z_prev = z_prev; p.x0_prev = x0_prev;
-  if (sn.on() && E->eta > 0.f && E->sigma[step_index] != 0.f) {     // sigma = 0 (a' = 1): d = sqrt(1-a'), the eta = 0 rows and kernel
+  // sigma = 0 (a' = 1, a' = a): d = sqrt(1-a'), the deterministic rows, c and kernel
+  const bool noisy = sn.on() && (E->eta > 0.f || E->sde_eta > 0.f) && E->sigma[step_index] != 0.f;
+  if (noisy) {
     p.coef = E->coef_table_eta + (size_t)step_index * 8; p.lin = E->step_table_eta + (size_t)step_index * 4;
-    p.x0 = x0; p.sigma = E->sigma[step_index]; p.noise = sn.noise;
+    p.sigma = E->sigma[step_index]; p.noise = sn.noise;
     p.rng_seed = sn.seed; p.rng_stream = DD_RNG_STEP_STREAM + step_index;
-    HIPCHK(launch_sampler_step_units(p, sn.unit_ids, s));
-    return;
   }
-  p.c2m = x0_prev ? E->c2m[step_index] : 0.f;
+  // a history comes with solver 1 alone (history_refused): under sde_eta > 0 the stochastic step takes its own c
+  p.c2m = x0_prev ? (noisy ? E->c2m_sde : E->c2m)[step_index] : 0.f;
   // the second-order term needs x0 of this step: a caller that does not ask for it has it written to the instance's own buffer
   const bool second_order = x0_prev && p.c2m != 0.f;
   p.x0 = !x0 && second_order ? E->inst[k].x0 : x0;
-  HIPCHK(launch_sampler_step(p, s));
+  HIPCHK(noisy ? launch_sampler_step_units(p, sn.unit_ids, s) : launch_sampler_step(p, s));
 }
 void sampler_step_bwd(dd_engine* E, int k, const Ctx& uc, int step_index, const float* g_x0, const float* g_znext, float* g_z, hipStream_t s) {
   HIPCHK(launch_sampler_step_bwd(step_params(E, k, step_index), g_x0, g_znext, grad_ptr(uc, E->unet.t[E->unet_out]), g_z, s));
@@ -179,10 +180,11 @@ bool history_refused(dd_engine* E, const float* x0_prev) {
   if (x0_prev && E->solver != 1) E->err = "x0_prev is the history of DPM-Solver++(2M): this schedule was set with solver 0 (DDIM)";
   return x0_prev && E->solver != 1;
 }
-// step noise is the input of a schedule set with eta > 0 alone
+// step noise is the input of a schedule set with eta > 0 or sde_eta > 0 alone
 bool noise_refused(dd_engine* E, const float* step_noise) {
-  if (step_noise && !(E->eta > 0.f)) E->err = "step_noise is the noise of a stochastic DDIM step: this schedule was set with eta = 0";
-  return step_noise && !(E->eta > 0.f);
+  const bool refused = step_noise && !(E->eta > 0.f || E->sde_eta > 0.f);
+  if (refused) E->err = "step_noise is the noise of a stochastic DDIM step: this schedule was set with eta = 0";
+  return refused;
 }
 
 // one guided forward step on instance k: z_in -> (z_next, x0, feat) ; energy accumulates into score, writes gfeat.  x0_prev: the
@@ -457,7 +459,20 @@ int dd_set_schedule_s(dd_engine* E, const int* timesteps, int n, const float* al
 
 int dd_set_schedule_e(dd_engine* E, const int* timesteps, int n, const float* alphas_cumprod, int num_train, float final_alpha,
                       const dd_sampler_params* sp, int solver, float eta) {
+  return dd_set_schedule_sde(E, timesteps, n, alphas_cumprod, num_train, final_alpha, sp, solver, eta, 0.f);
+}
+
+int dd_set_schedule_sde(dd_engine* E, const int* timesteps, int n, const float* alphas_cumprod, int num_train, float final_alpha,
+                        const dd_sampler_params* sp, int solver, float eta, float sde_eta) {
   if (!E || !timesteps || n < 1 || !alphas_cumprod || !sp) return DD_ERR_ARG;
+  // sde_eta > 0 is SDE-DPM-Solver++(2M): solver 1 with eta = 0, one noise stream per step
+  static_assert(DD_RNG_STEP_STREAMS == 4096, "the message below names the count");
+  const char* bad = !(sde_eta >= 0.f && sde_eta <= 1.f) ? "sde_eta must be in [0, 1]"
+                    : !(sde_eta > 0.f)                  ? nullptr
+                    : eta > 0.f                         ? "sde_eta > 0 needs eta = 0: eta is the noise of stochastic DDIM (solver 0)"
+                    : solver != 1                       ? "sde_eta > 0 is SDE-DPM-Solver++(2M): it needs solver 1"
+                    : n > DD_RNG_STEP_STREAMS           ? "sde_eta > 0: at most 4096 steps (one noise stream per step)" : nullptr;
+  if (bad) { E->err = bad; return DD_ERR_ARG; }
   if (!E->finalized) { E->err = "finalize first"; return DD_ERR_STATE; }
   DD_TRY(E, {
     const dd_config& c = E->cfg;
@@ -465,16 +480,17 @@ int dd_set_schedule_e(dd_engine* E, const int* timesteps, int n, const float* al
     if (!(sp->guidance_rescale >= 0.f && sp->guidance_rescale <= 1.f)) throw std::runtime_error("guidance_rescale must be in [0, 1]");
     if (solver < 0 || solver > 1) throw std::runtime_error("solver must be 0 (DDIM) or 1 (DPM-Solver++(2M))");
     if (!(eta >= 0.f && eta <= 1.f)) throw std::runtime_error("eta must be in [0, 1]");
-    if (eta > 0.f && solver != 0) throw std::runtime_error("eta > 0 is stochastic DDIM (solver 0): the SDE variant of DPM-Solver++ is another solver");
+    if (eta > 0.f && solver != 0) throw std::runtime_error("eta > 0 is stochastic DDIM (solver 0): the per-step noise of solver 1 is sde_eta (dd_set_schedule_sde)");
     if (eta > 0.f && n > DD_RNG_STEP_STREAMS) throw std::runtime_error("eta > 0: at most " + std::to_string(DD_RNG_STEP_STREAMS) + " steps (one noise stream per step)");
     std::vector<float> coef((size_t)n * 8, 0.f), lin((size_t)n * 4, 0.f), c2m;
-    std::vector<float> coef_eta, lin_eta, sigma;          // eta > 0 only
+    std::vector<float> coef_eta, lin_eta, sigma, c2m_sde; // a stochastic schedule only (c2m_sde: sde_eta > 0)
     const int ratio = num_train / n;
     for (int i = 0; i < n; ++i) {
       const int t = timesteps[i], prev = t - ratio;
       if (t < 0 || t >= num_train) throw std::runtime_error("timestep out of range");
       const double a = alphas_cumprod[t], ap = prev >= 0 ? alphas_cumprod[prev] : final_alpha;
-      if (solver == 1) c2m.push_back(sampler_step_coef_2m(i, n, i > 0 ? alphas_cumprod[timesteps[i - 1]] : 0.0, a, ap));
+      const double a_before = i > 0 ? alphas_cumprod[timesteps[i - 1]] : 0.0;
+      if (solver == 1) c2m.push_back(sampler_step_coef_2m(i, n, a_before, a, ap));
       float* q = &coef[(size_t)i * 8];
       q[0] = sp->guidance_scale; q[1] = (float)sqrt(a); q[2] = (float)sqrt(1 - a); q[3] = (float)sqrt(ap); q[4] = (float)sqrt(1 - ap);
       if (sampler_step_coefs(sp->prediction_type, a, ap, &lin[(size_t)i * 4]))      // the division form of the step divides by sqrt(a) as well
@@ -488,6 +504,16 @@ int dd_set_schedule_e(dd_engine* E, const int* timesteps, int n, const float* al
         lin_eta.insert(lin_eta.end(), o, o + 4);
         sigma.push_back(o[4]);
       }
+      if (sde_eta > 0.f) {
+        float o[5], c;
+        if (sampler_step_coefs_sde(sp->prediction_type, a, ap, sde_eta, o) || sampler_step_coef_2m_sde(i, n, a_before, a, ap, sde_eta, &c))
+          throw std::runtime_error("sde_eta > 0: the step at timestep " + std::to_string(t) + " has no finite sigma");
+        coef_eta.insert(coef_eta.end(), q, q + 8);
+        coef_eta[(size_t)i * 8 + 4] = sampler_step_sde_d(a, ap, sde_eta);
+        lin_eta.insert(lin_eta.end(), o, o + 4);
+        sigma.push_back(o[4]);
+        c2m_sde.push_back(c);
+      }
     }
     // every refusal is above: from here on the engine's schedule is replaced
     E->timesteps.assign(timesteps, timesteps + n);
@@ -498,8 +524,9 @@ int dd_set_schedule_e(dd_engine* E, const int* timesteps, int n, const float* al
     E->sched_allocs.clear();
     E->c2m = c2m;
     E->eta = eta; E->sigma = sigma;
+    E->sde_eta = sde_eta; E->c2m_sde = c2m_sde;
     E->coef_table_eta = nullptr; E->step_table_eta = nullptr;
-    if (eta > 0.f) {
+    if (eta > 0.f || sde_eta > 0.f) {
       E->step_table_eta = (float*)E->dmalloc(lin_eta.size() * 4, false);
       E->sched_allocs.push_back(E->step_table_eta);
       HIPCHK(hipMemcpy(E->step_table_eta, lin_eta.data(), lin_eta.size() * 4, hipMemcpyHostToDevice));
@@ -659,7 +686,7 @@ int dd_denoise_step(dd_engine* E, const float* z, int step_index, float* z_prev_
   return dd_denoise_step_h(E, z, step_index, nullptr, z_prev_out, x0_out, B, stream);
 }
 
-// one plain step with its optional inputs: the history (solver 1) or the noise (eta > 0); the public calls and dd_expand's loop are this
+// one plain step with its optional inputs: the history (solver 1), the noise (eta > 0) or both (sde_eta > 0); the public calls and dd_expand's loop are this
 static int denoise_step_call(dd_engine* E, const float* z, int step_index, const float* x0_prev, const StepNoise& sn, float* z_prev_out,
                              float* x0_out, int B, void* stream) {
   if (!E || !z || !z_prev_out) return DD_ERR_ARG;
@@ -681,6 +708,13 @@ int dd_denoise_step_n(dd_engine* E, const float* z, int step_index, const float*
   StepNoise sn;
   sn.noise = step_noise;
   return denoise_step_call(E, z, step_index, nullptr, sn, z_prev_out, x0_out, B, stream);
+}
+
+int dd_denoise_step_hn(dd_engine* E, const float* z, int step_index, const float* x0_prev, const float* step_noise, float* z_prev_out,
+                       float* x0_out, int B, void* stream) {
+  StepNoise sn;
+  sn.noise = step_noise;
+  return denoise_step_call(E, z, step_index, x0_prev, sn, z_prev_out, x0_out, B, stream);
 }
 
 int dd_decode(dd_engine* E, const float* z, float* image_out, int denormalize, int B, void* stream) {
@@ -828,6 +862,13 @@ int dd_direct_guidance_n(dd_engine* E, const float* z, const int* targets, int s
   return direct_guidance_call(E, z, targets, step_index, nullptr, sn, z_next_out, x0_out, score_out, grad_z_out, B, stream);
 }
 
+int dd_direct_guidance_hn(dd_engine* E, const float* z, const int* targets, int step_index, const float* x0_prev, const float* step_noise,
+                          float* z_next_out, float* x0_out, float* score_out, float* grad_z_out, int B, void* stream) {
+  StepNoise sn;
+  sn.noise = step_noise;
+  return direct_guidance_call(E, z, targets, step_index, x0_prev, sn, z_next_out, x0_out, score_out, grad_z_out, B, stream);
+}
+
 // direct guidance with its optional inputs, as denoise_step_call
 static int direct_guidance_call(dd_engine* E, const float* z, const int* targets, int step_index, const float* x0_prev, const StepNoise& sn,
                                 float* z_next_out, float* x0_out, float* score_out, float* grad_z_out, int B, void* stream) {
@@ -901,10 +942,10 @@ int dd_expand(dd_engine* E, const dd_expand_args* a, void* stream) {
   const int n = (int)E->timesteps.size();
   if (a->start_index < 0 || a->start_index >= n) { E->err = "start_index out of range"; return DD_ERR_ARG; }
   if (a->text_to_img && a->start_index != 0) { E->err = "text_to_img runs the whole schedule: start_index must be 0"; return DD_ERR_ARG; }
-  // eta > 0: the noise of step i of row k is generated from (seed, unit_ids[k], stream 16 + i) in either noise_mode
+  // eta > 0 or sde_eta > 0: the noise of step i of row k is generated from (seed, unit_ids[k], stream 16 + i) in either noise_mode
   StepNoise sn;
-  if (E->eta > 0.f) {
-    if (!a->unit_ids) { E->err = "this schedule was set with eta > 0: dd_expand needs unit_ids (with seed they key the noise of every step)"; return DD_ERR_ARG; }
+  if (E->eta > 0.f || E->sde_eta > 0.f) {
+    if (!a->unit_ids) { E->err = std::string("this schedule was set with ") + (E->eta > 0.f ? "eta" : "sde_eta") + " > 0: dd_expand needs unit_ids (with seed they key the noise of every step)"; return DD_ERR_ARG; }
     sn.unit_ids = a->unit_ids; sn.seed = a->seed;
   }
   const float* ch_e = a->e;

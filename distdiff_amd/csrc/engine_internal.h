@@ -273,12 +273,15 @@ struct dd_engine {
   float* step_table = nullptr;   // [n][4]: A_z, A_m, B_z, B_m of the linear step form (v_prediction / sample models, CFG rescale)
   std::vector<float> c2m;        // DPM-Solver++(2M) only: c_i of every step (host; the kernel takes it by value), empty under DDIM
   float* x0_hist = nullptr;      // DPM-Solver++(2M) only: dd_expand's history, x0 of the previous step [B,C,L,L] (in sched_allocs)
-  // eta > 0 only (dd_set_schedule_e; all empty / null under eta = 0): sigma_i of every step (host; the kernel takes it by value) and the
-  // rows the stochastic steps read in place of coef_table / step_table -- sqrt(1-a_prev) and B_z, B_m with d (sampler_step_coefs_eta).
+  // a stochastic schedule only -- eta > 0 (dd_set_schedule_e) or sde_eta > 0 (dd_set_schedule_sde); all empty / null otherwise: sigma_i of every step (host; the kernel takes it by value) and the
+  // rows the stochastic steps read in place of coef_table / step_table -- sqrt(1-a_prev) and B_z, B_m with d (sampler_step_coefs_eta /
+  // sampler_step_coefs_sde) -- and, under sde_eta > 0, c2m_sde: c_i of the stochastic second-order step (sampler_step_coef_2m_sde; host).
   // step_params() keeps pointing at the eta = 0 tables: transform guidance's chained steps and every backward stay deterministic
   std::vector<float> sigma;
   float* coef_table_eta = nullptr; float* step_table_eta = nullptr;
   float eta = 0.f;
+  std::vector<float> c2m_sde;
+  float sde_eta = 0.f;           // SDE-DPM-Solver++(2M), solver 1 only; never > 0 together with eta
   float* cot_part = nullptr; float* cot_scale = nullptr;   // fp16 build only: partials and {s, 1 / s} of the cotangent scale (launch_cot_scale)
   float* rs_part = nullptr;      // CFG rescale: block partials of the per-image reductions (scratch, consumed by the next kernel)
   dd_sampler_params sp{};

@@ -211,7 +211,10 @@ hipError_t launch_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int
 //                                block j >> 2 of (rng_seed, rng_stream, unit id of row b - rng_row0), the bits launch_philox_units writes.
 //                                The generated form steps rows [rng_row0, rng_row0 + rng_count) alone, rng_count <= DD_RNG_UNITS ids per
 //                                launch: a larger batch is several launches over row ranges in order, and the one with rng_row0 == 0
-//                                computes the statistics of phi != 0 for the whole batch.  Not with a history.
+//                                computes the statistics of phi != 0 for the whole batch.
+//   both of the two above        SDE-DPM-Solver++(2M) (forward only): coef / lin are the SDE rows (sampler_step_coefs_sde), c2m is
+//                                sampler_step_coef_2m_sde, z' = (the history step on those rows) + sigma n.  The generated form keeps its
+//                                row ranges; every launch reads and writes its own rows only, so x0 may still alias x0_prev.
 //                                With sigma == 0 or no source: the step above, nothing of this block is read.
 // ld: a multiple of 8; C <= 8; B <= 65535; anything else is hipErrorInvalidValue in front of any launch.  No atomics: bitwise deterministic.
 #define DD_RNG_UNITS 16
@@ -226,7 +229,7 @@ struct StepParams {
   const float* lin;                    // device: {A_z, A_m, B_z, B_m} (sampler_step_coefs)
   int prediction_type; float phi;      // 0 epsilon, 1 v_prediction, 2 sample; CFG rescale
   float* stats; float* part;
-  const float* noise; float sigma;     // eta > 0: explicit step noise NCHW fp32 [B, C, HW] (or null: generated) and sigma of this step
+  const float* noise; float sigma;     // eta > 0 / SDE: explicit step noise NCHW fp32 [B, C, HW] (or null: generated) and sigma of this step
   uint64_t rng_seed; int rng_stream;   // the generated form: Philox key and stream (16 + step index)
   RngUnits rng_ids; int rng_count, rng_row0;
 };
@@ -236,10 +239,19 @@ int sampler_step_coefs(int prediction_type, double a, double a_prev, float* out4
 // for a result that is not finite.  eta = 0: the four floats of sampler_step_coefs bit for bit and sigma = 0.0f.
 int sampler_step_coefs_eta(int prediction_type, double a, double a_prev, double eta, float* out5);
 float sampler_step_eta_d(double a, double a_prev, double eta);      // d of that step, rounded once: coef[4] of the division form
+// {A_z, A_m, B_z, B_m, sigma_n} of the SDE-DPM-Solver++(2M) step with s in [0, 1] (k-diffusion sample_dpmpp_2m_sde's eta; s = 1: diffusers
+// sde-dpmsolver++): h = lambda(a') - lambda(a), d = sqrt(1-a') e^(-s h) takes the place of sqrt(1-a') in B_z / B_m, sigma_n = sqrt(1-a')
+// sqrt(-expm1(-2 s h)).  a' = 1: d = sigma_n = 0; a' = a: (sqrt(1-a'), 0.0f); a = 0: (0, sqrt(1-a')).  Host, double; -1 where
+// sampler_step_coefs gives it, for s outside [0, 1] and for a result that is not finite.  s = 0: the floats of sampler_step_coefs, 0.0f.
+int sampler_step_coefs_sde(int prediction_type, double a, double a_prev, double s, float* out5);
+float sampler_step_sde_d(double a, double a_prev, double s);        // d of that step, rounded once: coef[4] of the division form
 size_t sampler_step_scratch_floats(int B, int HW);
 // c = sampler_step_coef_2m(i, n, a at step i - 1, a at step i, a at its previous timestep), host, double; exactly 0 for the first and
 // the last step and wherever it is undefined
 float sampler_step_coef_2m(int i, int n, double a_before, double a, double a_prev);
+// the SDE variant: *out = sqrt(a') (1 - e^-((1+s) h)) / (2 r), 0.0f exactly where sampler_step_coef_2m is; -1 for s outside [0, 1] (*out is
+// then not written), else 0.  s = 0: the float of sampler_step_coef_2m
+int sampler_step_coef_2m_sde(int i, int n, double a_before, double a, double a_prev, double s, float* out);
 hipError_t launch_sampler_step(const StepParams& p, hipStream_t s);
 // the generated form for a whole batch: unit_ids HOST [p.B], read before the call returns; DD_RNG_UNITS rows per launch (p.rng_ids,
 // rng_count and rng_row0 are filled here).  With sigma == 0 this is launch_sampler_step(p).

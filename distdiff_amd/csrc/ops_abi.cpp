@@ -135,6 +135,23 @@ int dd_op_sampler_step_n(const float* m2, int ld, const float* z, const float* n
   if (noise || unit_ids) { p.noise = noise; p.sigma = sigma; p.rng_seed = seed; p.rng_stream = rng_stream; }
   return (int)launch_sampler_step_units(p, unit_ids, S(st));
 }
+int dd_op_step_coefs_sde(int prediction_type, double a, double a_prev, double sde_eta, float* out5) {
+  if (!out5) return -1;
+  return sampler_step_coefs_sde(prediction_type, a, a_prev, sde_eta, out5);
+}
+int dd_op_step_coef_2m_sde(int step_index, int n_steps, double a_before, double a, double a_prev, double sde_eta, float* out) {
+  if (!out) return -1;
+  return sampler_step_coef_2m_sde(step_index, n_steps, a_before, a, a_prev, sde_eta, out);
+}
+int dd_op_sampler_step_2m_n(const float* m2, int ld, const float* z, const float* x0_prev, float c2m, const float* noise, float sigma,
+                            uint64_t seed, int rng_stream, const uint64_t* unit_ids, float* z_prev, float* x0, int B, int C, int HW,
+                            const float* coef, const float* lin, int prediction_type, float guidance_rescale, float* stats, float* part,
+                            void* st) {
+  StepParams p = step_params(m2, ld, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part);
+  p.z = z; p.x0_prev = x0_prev; p.c2m = c2m; p.z_prev = z_prev; p.x0 = x0;
+  if (noise || unit_ids) { p.noise = noise; p.sigma = sigma; p.rng_seed = seed; p.rng_stream = rng_stream; }
+  return (int)launch_sampler_step_units(p, unit_ids, S(st));
+}
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int acc, void* st) {
   return (int)launch_sumpool2x2(src, src_ld, dst, dst_ld, B, H, W, C, acc, S(st));
 }

@@ -3,7 +3,7 @@
 // One forward kernel template, one backward kernel template, one launcher each; the modes are listed at StepParams in kernels.h.
 //
 //   m  = u + s (c - u),  m^ = k_b m  (k_b = phi sigma_c / sigma_m + 1 - phi per image; 1 without rescale)
-//   x0 = A_z z + A_m m^,  z' = B_z z + B_m m^ [+ c2m (x0 - x0_prev)] [+ sigma n]
+//   x0 = A_z z + A_m m^,  z' = B_z z + B_m m^ [+ c2m (x0 - x0_prev)] [+ sigma n]      (both brackets: SDE-DPM-Solver++(2M))
 //
 // One thread per pixel: both CFG halves of the 8-wide fp32 NHWC row come in as 16-byte loads, the NCHW reads and writes are coalesced
 // along the pixels.  grid = (ceil(HW / 256), B).  No atomics: bitwise deterministic.
@@ -14,6 +14,9 @@
 // holds their bits.  Do not "simplify" a * b + c * d into an fma or the reverse: it changes the latents of every image.
 // The noise term of eta > 0 is zp = (b0 * t + b1 * m) + sigma * n: the no-history expression on the eta tables, then the product rounded,
 // then the sum rounded, no fma -- what torch gives for z'(noise = 0) + sigma * n in fp32 (tests/test_ddim_eta_gpu.py).
+// With a history and noise (SDE-DPM-Solver++(2M), on the SDE rows) it is zp = (fmaf(b0, t, b1 * m) + c2m * (x - xp)) + sigma * n: the HIST
+// expression, then the product rounded, then the sum rounded, no fma -- z' of the HIST kernel on the same rows and c, + sigma * n by torch
+// in fp32 (tests/test_dpm_sde_gpu.py).  The six instantiations without that pair are untouched by it.
 #include <cmath>
 
 #include "common.h"
@@ -33,10 +36,12 @@ __device__ __forceinline__ void load_row8(const float* p, int C, float* v) {
 // EPS: (epsilon, no rescale) in the division form on the five-float row coef = {s, sqrt a, sqrt(1-a), sqrt a', sqrt(1-a')}:
 //   x0 = (z - sqrt(1-a) m) / sqrt a,  z' = sqrt a' x0 + sqrt(1-a') m
 // otherwise the linear form on lin = {A_z, A_m, B_z, B_m} (sampler_step_coefs).  HIST adds c2m (x0 - x0_prev) and always writes x0,
-// which may alias x0_prev: each thread reads its own element before it writes it.  NOISE (never with HIST) adds sigma n on the eta rows
+// which may alias x0_prev: each thread reads its own element before it writes it.  NOISE adds sigma n on the stochastic rows (eta or SDE)
 // of coef / lin and steps rows rng_row0 + blockIdx.y: n is read from p.noise, or is lane j & 3 of Philox block j >> 2 of the row's unit,
 // j = ch * HW + pix -- one thread per pixel as before, so each thread computes the block of each of its elements (and its neighbours
 // compute it again: 4x the Philox work of rng.hip, microseconds against the UNet) and the Box-Muller of the one word pair it needs.
+// HIST with NOISE keeps the row ranges of the generated form (DD_RNG_UNITS ids per launch): a launch reads and writes the elements of
+// its own rows only -- z, x0_prev, x0, z_prev alike -- so x0 == x0_prev stays legal across the launches of one batch.
 template <bool EPS, bool HIST, bool NOISE>
 __global__ __launch_bounds__(STEP_THREADS) void sampler_step_kernel(const StepParams p) {
 #pragma clang fp contract(off)
@@ -294,6 +299,36 @@ float sampler_step_eta_d(double a, double ap, double eta) {
   eta_sigma_d(a, ap, eta, &sigma, &d);
   return (float)d;
 }
+// SDE-DPM-Solver++(2M), s in [0, 1] (k-diffusion sample_dpmpp_2m_sde's eta): with h = lambda(a') - lambda(a) the direction term keeps
+// d = sqrt(1-a') e^(-s h) and sigma_n = sqrt(1-a') sqrt(-expm1(-2 s h)) goes to fresh noise, d^2 + sigma_n^2 = 1 - a'.  The limits are
+// taken here, never computed: s = 0 and h <= 0 (a' = a) give (sqrt(1-a'), 0) -- the floats of sampler_step_coefs --, a' = 1 gives (0, 0),
+// a = 0 (h = +inf: the first trailing step of a zero-terminal-SNR table) gives (0, sqrt(1-a')).
+static void sde_sigma_d(double a, double ap, double s, double* sigma, double* d) {
+  const double sbp = sqrt(1 - ap);
+  *sigma = 0.0; *d = sbp;
+  if (!(s > 0) || !(ap < 1)) return;
+  if (!(a > 0)) { *sigma = sbp; *d = 0.0; return; }
+  const double h = 0.5 * (log(ap / (1 - ap)) - log(a / (1 - a)));
+  if (!(h > 0)) return;
+  if (!std::isfinite(h)) { *sigma = sbp; *d = 0.0; return; }
+  *d = sbp * exp(-s * h);
+  *sigma = sbp * sqrt(-expm1(-2 * s * h));
+}
+int sampler_step_coefs_sde(int prediction_type, double a, double ap, double s, float* out5) {
+  if (!(s >= 0 && s <= 1)) return -1;
+  double sigma, d;
+  sde_sigma_d(a, ap, s, &sigma, &d);
+  if (step_coefs_d(prediction_type, a, ap, d, out5)) return -1;
+  out5[4] = (float)sigma;
+  for (int k = 0; k < 5; ++k)
+    if (!std::isfinite(out5[k])) return -1;
+  return 0;
+}
+float sampler_step_sde_d(double a, double ap, double s) {
+  double sigma, d;
+  sde_sigma_d(a, ap, s, &sigma, &d);
+  return (float)d;
+}
 size_t sampler_step_scratch_floats(int B, int HW) { return (size_t)B * ((HW + STEP_THREADS - 1) / STEP_THREADS) * 8; }
 
 // c_i of the second-order step i of an n-step schedule, from alphas_cumprod at step i - 1, at step i and at its previous timestep.
@@ -301,23 +336,29 @@ size_t sampler_step_scratch_floats(int B, int HW) { return (size_t)B * ((HW + ST
 //   c = sqrt(a') (1 - e^-h) / (2 r)
 // Exactly 0 -- the step is then the first-order one -- for the first and the last step of the schedule and wherever a lambda is not
 // finite (a = 0 of a zero-terminal-SNR table, a' = 1) or c itself is not: never NaN or inf.
-float sampler_step_coef_2m(int i, int n, double a_before, double a, double ap) {
+// The SDE variant with s in [0, 1] has c = sqrt(a') (1 - e^-((1+s) h)) / (2 r), the same zeros, and at s = 0 the same double expression.
+static float coef_2m_s(int i, int n, double a_before, double a, double ap, double s) {
   if (i <= 0 || i >= n - 1) return 0.f;
   const double l0 = 0.5 * log(a_before / (1 - a_before)), l1 = 0.5 * log(a / (1 - a)), l2 = 0.5 * log(ap / (1 - ap));
   if (!std::isfinite(l0) || !std::isfinite(l1) || !std::isfinite(l2)) return 0.f;
   const double h = l2 - l1, r = (l1 - l0) / h;
-  const double c = sqrt(ap) * -expm1(-h) / (2 * r);
+  const double c = sqrt(ap) * -expm1(s > 0 ? -(1 + s) * h : -h) / (2 * r);
   return std::isfinite(c) && std::isfinite((float)c) ? (float)c : 0.f;
+}
+float sampler_step_coef_2m(int i, int n, double a_before, double a, double ap) { return coef_2m_s(i, n, a_before, a, ap, 0.0); }
+int sampler_step_coef_2m_sde(int i, int n, double a_before, double a, double ap, double s, float* out) {
+  if (!(s >= 0 && s <= 1)) return -1;
+  *out = coef_2m_s(i, n, a_before, a, ap, s);
+  return 0;
 }
 
 hipError_t launch_sampler_step(const StepParams& p, hipStream_t s) {
   const bool eps = p.prediction_type == 0 && p.phi == 0.f;
   const bool hist = p.x0_prev && p.c2m != 0.f;              // otherwise the first-order step: the history is not read
   if (!step_args_ok(p, eps) || (hist && (!p.x0 || !std::isfinite(p.c2m)))) return hipErrorInvalidValue;
-  // eta > 0: sigma != 0 and a noise source, the tensor or (rng_count > 0) the generator on rows [rng_row0, rng_row0 + rng_count)
+  // a stochastic step (eta > 0 or SDE): sigma != 0 and a noise source, the tensor or (rng_count > 0) the generator on rows [rng_row0, rng_row0 + rng_count)
   if (!std::isfinite(p.sigma) || p.rng_count < 0 || p.rng_count > DD_RNG_UNITS) return hipErrorInvalidValue;
   const bool noise = p.sigma != 0.f && (p.noise || p.rng_count > 0), generated = noise && !p.noise;
-  if (noise && hist) return hipErrorInvalidValue;
   // the kernel draws normals: stream 2 (e) is uniform in launch_philox_units and would not be its tensor here
   if (generated && (p.rng_row0 < 0 || p.rng_row0 + p.rng_count > p.B || !rng_stream_ok(p.rng_stream) || p.rng_stream == 2)) return hipErrorInvalidValue;
   const dim3 grid((p.HW + STEP_THREADS - 1) / STEP_THREADS, p.B);
@@ -329,7 +370,8 @@ hipError_t launch_sampler_step(const StepParams& p, hipStream_t s) {
     StepParams q = p;
     if (!generated) q.rng_row0 = 0;
     const dim3 rows(grid.x, generated ? p.rng_count : p.B);
-    const auto noisy = eps ? sampler_step_kernel<true, false, true> : sampler_step_kernel<false, false, true>;
+    const auto noisy = eps ? (hist ? sampler_step_kernel<true, true, true> : sampler_step_kernel<true, false, true>)
+                           : (hist ? sampler_step_kernel<false, true, true> : sampler_step_kernel<false, false, true>);
     hipLaunchKernelGGL(noisy, rows, dim3(STEP_THREADS), 0, s, q);
     return hipGetLastError();
   }

@@ -74,6 +74,9 @@ def _declare(l):
     l.dd_set_schedule.argtypes = [vp, vp, i, vp, i, f, C.POINTER(DDSamplerParams)]
     l.dd_set_schedule_s.argtypes = [vp, vp, i, vp, i, f, C.POINTER(DDSamplerParams), i]
     l.dd_set_schedule_e.argtypes = [vp, vp, i, vp, i, f, C.POINTER(DDSamplerParams), i, f]
+    l.dd_set_schedule_sde.argtypes = [vp, vp, i, vp, i, f, C.POINTER(DDSamplerParams), i, f, f]
+    l.dd_denoise_step_hn.argtypes = [vp, vp, i, vp, vp, vp, vp, i, vp]
+    l.dd_direct_guidance_hn.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, vp, i, vp]
     l.dd_denoise_step_n.argtypes = [vp, vp, i, vp, vp, vp, i, vp]
     l.dd_direct_guidance_n.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, i, vp]
     l.dd_set_prototypes.argtypes = [vp, vp, vp, i, i, i]
@@ -282,13 +285,16 @@ class Engine:
     # ---- setup -------------------------------------------------------------------------------
     def set_schedule(self, timesteps, alphas_cumprod, final_alpha_cumprod, guidance_scale=7.5, gs=1.0, ls=1.0, rho=10.0,
                      constraint_value=0.2, use_global=True, use_local=True, guidance_period=2, prediction_type="epsilon",
-                     guidance_rescale=0.0, solver="ddim", eta=0.0):
+                     guidance_rescale=0.0, solver="ddim", eta=0.0, sde_eta=0.0):
         """prediction_type: what the UNet predicts, 'epsilon' | 'v_prediction' | 'sample' (scheduler_config.json); guidance_rescale: the
         CFG rescale factor phi in [0, 1] (diffusers rescale_noise_cfg); solver: 'ddim' | 'dpmsolver++' (DPM-Solver++(2M) on the same
         timestep list: `expand` keeps its history itself, the step-level calls take it as `x0_prev`); eta in [0, 1]: stochastic DDIM
         (diffusers DDIMScheduler.step(eta=...), 'ddim' only): every plain and direct-guidance step adds sigma_i n -- `expand` generates n
         from (seed, unit id, step) itself, the step-level calls take it as `step_noise`; transform guidance's look-ahead stays
-        deterministic.  The defaults are the SD-1.x sampler; eta = 0 is the call without it, bit for bit."""
+        deterministic.  sde_eta in [0, 1]: SDE-DPM-Solver++(2M) ('dpmsolver++' and eta = 0 only; k-diffusion's eta of sample_dpmpp_2m_sde,
+        1 = diffusers sde-dpmsolver++): the second-order step with sigma' sqrt(1 - e^(-2 s h)) n added where eta's noise would be; the
+        step-level calls then take `x0_prev` and `step_noise` together.  eta and sde_eta are different functions of their argument, hence
+        two keywords.  The defaults are the SD-1.x sampler; eta = 0 / sde_eta = 0 is the call without it, bit for bit."""
         if prediction_type not in PREDICTION_TYPES:
             raise NotImplementedError("prediction_type=%r (built: %s)" % (prediction_type, ", ".join(PREDICTION_TYPES)))
         if solver not in SOLVERS:
@@ -297,8 +303,14 @@ class Engine:
         ac = np.ascontiguousarray(np.asarray(alphas_cumprod, dtype=np.float32))
         sp = DDSamplerParams(guidance_scale, gs, ls, rho, constraint_value, int(use_global), int(use_local), int(guidance_period),
                              PREDICTION_TYPES[prediction_type], float(guidance_rescale))
-        self._chk(self.L.dd_set_schedule_e(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
-                                           float(final_alpha_cumprod), C.byref(sp), SOLVERS[solver], float(eta)), "dd_set_schedule")
+        if sde_eta:
+            self._chk(self.L.dd_set_schedule_sde(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
+                                                 float(final_alpha_cumprod), C.byref(sp), SOLVERS[solver], float(eta), float(sde_eta)),
+                      "dd_set_schedule")
+        else:
+            self._chk(self.L.dd_set_schedule_e(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
+                                               float(final_alpha_cumprod), C.byref(sp), SOLVERS[solver], float(eta)), "dd_set_schedule")
+        self._sde = bool(sde_eta)          # the schedule now set takes x0_prev and step_noise together
         self.n_steps = len(ts)
         self.timesteps = [int(t) for t in ts]
 
@@ -396,16 +408,21 @@ class Engine:
 
     def denoise_step(self, z, step_index, x0_prev=None, step_noise=None):
         """-> (z', x0).  x0_prev: under solver 'dpmsolver++' the x0 this call returned for step_index - 1 on the same trajectory (the
-        second-order step); None is the first-order step.  step_noise: on a schedule set with eta > 0 the N(0,1) tensor [B,C,L,L] of this
-        step, e.g. `randn_units(seed, 16 + step_index, unit_ids, C*L*L)`; None is the eta = 0 step."""
+        second-order step); None is the first-order step.  step_noise: on a schedule set with eta > 0 or sde_eta > 0 the N(0,1) tensor
+        [B,C,L,L] of this step, e.g. `randn_units(seed, 16 + step_index, unit_ids, C*L*L)`; None is the deterministic step.  Both together
+        only on a schedule set with sde_eta > 0."""
         z = self._f(z)
         h = self._f(x0_prev) if x0_prev is not None else None
         zp, x0 = torch.empty_like(z), torch.empty_like(z)
         if step_noise is not None:
-            if h is not None:
-                raise ValueError("denoise_step: x0_prev (solver 'dpmsolver++') and step_noise (eta > 0) do not go together")
             nz = self._f(step_noise)
             assert nz.numel() == z.numel()
+            if h is not None:
+                if not getattr(self, "_sde", False):
+                    raise ValueError("denoise_step: x0_prev (solver 'dpmsolver++') and step_noise (eta > 0) do not go together")
+                self._chk(self.L.dd_denoise_step_hn(self._h, _p(z), step_index, _p(h), _p(nz), _p(zp), _p(x0), z.shape[0], _stream()),
+                          "dd_denoise_step")
+                return zp, x0
             self._chk(self.L.dd_denoise_step_n(self._h, _p(z), step_index, _p(nz), _p(zp), _p(x0), z.shape[0], _stream()), "dd_denoise_step")
             return zp, x0
         self._chk(self.L.dd_denoise_step_h(self._h, _p(z), step_index, _p(h), _p(zp), _p(x0), z.shape[0], _stream()), "dd_denoise_step")
@@ -430,10 +447,14 @@ class Engine:
         zn, x0, gz = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
         score = torch.zeros(1, device=self.device)
         if step_noise is not None:
-            if h is not None:
-                raise ValueError("direct_guidance: x0_prev (solver 'dpmsolver++') and step_noise (eta > 0) do not go together")
             nz = self._f(step_noise)
             assert nz.numel() == z.numel()
+            if h is not None:
+                if not getattr(self, "_sde", False):
+                    raise ValueError("direct_guidance: x0_prev (solver 'dpmsolver++') and step_noise (eta > 0) do not go together")
+                self._chk(self.L.dd_direct_guidance_hn(self._h, _p(z), _p(tg), step_index, _p(h), _p(nz), _p(zn), _p(x0), _p(score), _p(gz),
+                                                       z.shape[0], _stream()), "dd_direct_guidance")
+                return zn, x0, score, gz
             self._chk(self.L.dd_direct_guidance_n(self._h, _p(z), _p(tg), step_index, _p(nz), _p(zn), _p(x0), _p(score), _p(gz), z.shape[0],
                                                   _stream()), "dd_direct_guidance")
             return zn, x0, score, gz
@@ -479,8 +500,8 @@ class Engine:
         seed + unit_ids [B]: the initial noise, the offset noise (offset_noise=True), e and b of row k are generated on the device from
         (seed, unit_ids[k]) alone (`randn_units`); `noise`, `e`, `b` are then not read and may be None.
         text_to_img: the loop starts from the noise itself and runs the whole schedule (start_index must be 0); image_latents may be None.
-        generate_inputs=False (a schedule set with eta > 0): `noise`, `e`, `b` are read as without seed / unit_ids, which then key the
-        noise of the steps alone -- step i of row k from (seed, unit_ids[k], stream 16 + i).  Under eta > 0 seed and unit_ids are required."""
+        generate_inputs=False (a schedule set with eta > 0 or sde_eta > 0): `noise`, `e`, `b` are read as without seed / unit_ids, which then key the
+        noise of the steps alone -- step i of row k from (seed, unit_ids[k], stream 16 + i).  Under eta > 0 or sde_eta > 0 seed and unit_ids are required."""
         generated = seed is not None or unit_ids is not None
         if generated and (seed is None or unit_ids is None):
             raise ValueError("expand: seed and unit_ids go together")

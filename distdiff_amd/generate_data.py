@@ -42,6 +42,11 @@ plain and direct-guidance step of the main loop adds sigma_t * N(0,1), so the ex
 first latent.  The step noise is counter-based under both --noise_rng settings -- generated inside the step kernel from (--seed, unit
 id, step index) -- so it never depends on how the run is packed; under `stream` the initial noise / e / b still come from the host
 generators.  The look-ahead steps inside transform guidance stay deterministic.  Not with --sampler dpmsolver++.
+`--sde_eta S` in (0, 1] (default 0) is the per-step noise of `--sampler dpmsolver++`: SDE-DPM-Solver++(2M), k-diffusion's `eta` of
+`sample_dpmpp_2m_sde` (S = 1: diffusers `sde-dpmsolver++`).  Every step that --eta would make stochastic adds sigma' sqrt(1 - e^(-2 S h))
+* N(0,1), keyed and generated as under --eta; the second-order term stays.  --eta and --sde_eta are different functions of their
+argument (eta sqrt(var_t) against sigma' sqrt(1 - e^(-2 S h))), hence two flags: --sde_eta needs --sampler dpmsolver++ and --eta 0.  The
+last step adds noise whenever the engine's own previous-alpha rule leaves sigma_n != 0 there (no diffusers `final_sigmas_type`).
 `--act_dtype fp16` (default `bf16`) runs the UNet, VAE, text encoder and ViT guide in IEEE half instead of bf16 (three more mantissa
 bits; the fp16 build of the same kernels).  `--mixed_precision` stays accepted and ignored: the reference ignores
 it on this path too -- generate_data.py:1034-1040 sets `weight_dtype = torch.float16` whatever the flag says.
@@ -132,6 +137,10 @@ def parse_args(argv=None):
     p.add_argument("--eta", type=float, default=0.0,
                    help="stochastic DDIM, eta in [0, 1] (diffusers DDIMScheduler.step(eta=...)): sigma_t = eta * sqrt((1-a')/(1-a) (1-a/a')) of fresh "
                    "noise per step, keyed by (--seed, unit, step).  0 (default) = the reference's deterministic DDIM; 1 = DDPM-like.  --sampler ddim only")
+    p.add_argument("--sde_eta", type=float, default=0.0,
+                   help="SDE-DPM-Solver++(2M), S in [0, 1] (k-diffusion sample_dpmpp_2m_sde's eta; 1 = diffusers sde-dpmsolver++): sigma' * "
+                   "sqrt(1 - exp(-2 S h)) of fresh noise per step, keyed by (--seed, unit, step).  0 (default) = deterministic.  --sampler dpmsolver++ "
+                   "and --eta 0 only: --eta (eta * sqrt(var_t)) and --sde_eta are different functions of their argument, hence two flags")
     p.add_argument("--prediction_type", default=None, choices=["epsilon", "v_prediction", "sample"],
                    help="override scheduler_config.json's prediction_type (chiefly for --synthetic)")
     p.add_argument("--timestep_spacing", default=None, choices=["leading", "trailing", "linspace"],
@@ -166,6 +175,12 @@ def parse_args(argv=None):
         raise SystemExit("--eta must be in [0, 1]")
     if args.eta > 0.0 and args.sampler != "ddim":
         raise SystemExit("--eta > 0 is stochastic DDIM: it does not go with --sampler %s" % args.sampler)
+    if not 0.0 <= args.sde_eta <= 1.0:                    # also refuses nan
+        raise SystemExit("--sde_eta must be in [0, 1]")
+    if args.sde_eta > 0.0 and args.sampler != "dpmsolver++":
+        raise SystemExit("--sde_eta > 0 is SDE-DPM-Solver++(2M): it needs --sampler dpmsolver++")
+    if args.sde_eta > 0.0 and args.eta > 0.0:
+        raise SystemExit("--sde_eta > 0 needs --eta 0: --eta is the noise of stochastic DDIM")
     if args.act_dtype == "fp16" and args.attn_fp8:
         raise SystemExit("--act_dtype fp16 does not go with --attn_fp8: the fp16 library has no fp8 P.V attention")
     if not args.do_classifier_free_guidance:
@@ -382,7 +397,8 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
     n = len(ts)
     si = start_index(args.strength, n)
     philox, t2i = getattr(args, "noise_rng", "stream") == "philox", bool(getattr(args, "text_to_img", False))
-    eta = float(getattr(args, "eta", 0.0) or 0.0)         # > 0: every unit's counter also keys the noise of its steps, in either noise_rng
+    # --eta or --sde_eta > 0: every unit's counter also keys the noise of its steps, in either noise_rng
+    eta = max(float(getattr(args, "eta", 0.0) or 0.0), float(getattr(args, "sde_eta", 0.0) or 0.0))
     if t2i:
         log.info("--text_to_img: the loop starts from noise at t=%d (start index 0; --strength %s does not apply%s)", ts[0], args.strength,
                  ", nor does --offset_noise" if args.offset_noise else "")
@@ -614,7 +630,8 @@ def build_engine(args, device=None, distributed=False):
                      rho=args.rho, constraint_value=args.constraint_value, use_global="global_prototype" in targets,
                      use_local="local_prototype" in targets, guidance_period=args.guidance_period,
                      prediction_type=cfg.scheduler.prediction_type, guidance_rescale=args.guidance_rescale,
-                     solver=getattr(args, "sampler", "ddim"), **({"eta": args.eta} if getattr(args, "eta", 0.0) else {}))
+                     solver=getattr(args, "sampler", "ddim"), **({"eta": args.eta} if getattr(args, "eta", 0.0) else {}),
+                     **({"sde_eta": args.sde_eta} if getattr(args, "sde_eta", 0.0) else {}))
     return cfg, eng, sched
 
 

@@ -16,7 +16,8 @@
  *   dd_denoise_step        denoise_one_step (noise_scheduler.step for epsilon /   generate_data.py:109-121
  *                          v_prediction / sample models: dd_sampler_params;
  *                          dd_denoise_step_h: the DPM-Solver++(2M) step with its history;
- *                          dd_denoise_step_n: the eta > 0 step with its noise)
+ *                          dd_denoise_step_n: the eta > 0 step with its noise;
+ *                          dd_denoise_step_hn: the SDE-DPM-Solver++(2M) step with both)
  *   dd_transform_guidance  transform_guidance (+ linfball_proj)                 generate_data.py:687-732, 124-137
  *   dd_direct_guidance     direct_guidance                                      generate_data.py:735-767
  *   dd_decode              vae.decode + image_processor.postprocess             generate_data.py:1221-1228
@@ -49,7 +50,9 @@ enum dd_status { DD_OK = 0, DD_ERR_ARG = -1, DD_ERR_HIP = -2, DD_ERR_STATE = -3,
 /* Layout version of the structs and argument lists of this header and distdiff_hip_ops.h.  A caller sets dd_config.abi_version =
  * DD_ABI_VERSION (after zero-initialising the struct: every struct of this ABI must be zero-initialised, new fields are appended and
  * mean "off" at 0); dd_create refuses another value with DD_ERR_ARG, and dd_abi_version() tells what the loaded library was built
- * as.  11: dd_act_dtype() is new (the 16-bit storage format the library was compiled for), no struct changed; 10: dd_set_schedule_e (the schedule with eta in [0, 1]: stochastic DDIM), dd_denoise_step_n / dd_direct_guidance_n /
+ * as.  The version is the layout of structs and argument lists: entry points added beside the existing ones do not change it (still 11:
+ * dd_set_schedule_sde / dd_denoise_step_hn / dd_direct_guidance_hn / dd_op_step_coefs_sde / dd_op_step_coef_2m_sde /
+ * dd_op_sampler_step_2m_n, SDE-DPM-Solver++(2M), no struct and no existing argument list changed).  11: dd_act_dtype() is new (the 16-bit storage format the library was compiled for), no struct changed; 10: dd_set_schedule_e (the schedule with eta in [0, 1]: stochastic DDIM), dd_denoise_step_n / dd_direct_guidance_n /
  * dd_op_step_coefs_eta / dd_op_sampler_step_n are new, dd_randn_units takes the streams 16 + i, no struct changed; 9: dd_set_schedule_s (the schedule with a solver: 0 = DDIM, the sampler of version 8; 1 = DPM-Solver++(2M)), dd_denoise_step_h /
  * dd_direct_guidance_h / dd_op_step_coef_2m / dd_op_sampler_step_2m are new, no struct changed; 8: dd_sampler_params gained prediction_type /
  * guidance_rescale (0 = the sampler of version 7), the dd_op_sampler_step* entry points are new; 7: dd_expand_args gained seed / unit_ids / noise_mode / offset_noise / text_to_img (all 0 = the call of version 6), dd_randn_units
@@ -208,10 +211,27 @@ int dd_set_schedule_s(dd_engine* e, const int* timesteps, int n, const float* al
  * eta = 0, forward and backward.  The noise is explicit at the step level -- the step_noise argument of dd_denoise_step_n /
  * dd_direct_guidance_n -- and generated inside the step kernel by dd_expand, from (seed, unit id, stream 16 + step index) of
  * dd_randn_units: bit for bit what the explicit call gives on dd_randn_units' output, with no noise tensor in memory.
- * Refused: eta outside [0, 1] or not finite; eta > 0 with solver 1 (the SDE variant is another solver); more than 4096 steps.
+ * Refused: eta outside [0, 1] or not finite; eta > 0 with solver 1 (its per-step noise is sde_eta, below); more than 4096 steps.
  * eta travels as an argument: the layout of dd_sampler_params stays version 8's. */
 int dd_set_schedule_e(dd_engine* e, const int* timesteps, int n, const float* alphas_cumprod, int num_train_timesteps,
                       float final_alpha_cumprod, const dd_sampler_params* sp, int solver, float eta);
+/* dd_set_schedule_e with sde_eta; sde_eta 0 IS dd_set_schedule_e.  sde_eta = s in (0, 1] is SDE-DPM-Solver++(2M): k-diffusion's eta of
+ * sample_dpmpp_2m_sde; s = 1 is diffusers DPMSolverMultistepScheduler(algorithm_type="sde-dpmsolver++", solver_order=2,
+ * solver_type="midpoint", lower_order_final=True).  With lambda, h_i, r_i as in dd_set_schedule_s, x0 and eps as in dd_sampler_params:
+ *   d = sqrt(1-a') e^(-s h)    sigma_n = sqrt(1-a') sqrt(1 - e^(-2 s h))    c_sde = sqrt(a') (1 - e^(-(1+s) h)) / (2 r)
+ *   z' = sqrt(a') x0 + d eps + c_sde (x0 - x0_prev) + sigma_n n        n ~ N(0, 1) per element
+ * (d^2 + sigma_n^2 = 1 - a'; at s = 1 the first-order step is the eta = 1 DDIM step).  c_sde = 0 where c_i of dd_set_schedule_s is.
+ * a' = 1: d = sigma_n = 0; a' = a: sigma_n = 0; a = 0 (zero terminal SNR): d = 0, sigma_n = sqrt(1-a').  Where sigma_n = 0, and
+ * wherever a step is given no noise, the step is the one of dd_set_schedule_s, bit for bit.  x0 depends on neither s nor n.  The
+ * noise applies where eta's does (plain steps, the step executed again after transform guidance -- which takes noise and no history
+ * --, direct guidance's z_next), the last step included whenever the engine's own a' rule (final_alpha_cumprod) leaves sigma_n != 0
+ * there: the engine keeps that rule and does not take diffusers' final_sigmas_type.  dd_transform_guidance's chained steps stay
+ * first-order and deterministic.  eta and sde_eta are different functions of their argument (eta sqrt(var) against
+ * sqrt(1-a') sqrt(1 - e^(-2 s h))), hence two arguments.
+ * Refused (DD_ERR_ARG, the message names the argument): sde_eta outside [0, 1] or not finite; sde_eta > 0 with solver != 1 or with
+ * eta > 0; more than 4096 steps. */
+int dd_set_schedule_sde(dd_engine* e, const int* timesteps, int n, const float* alphas_cumprod, int num_train_timesteps,
+                        float final_alpha_cumprod, const dd_sampler_params* sp, int solver, float eta, float sde_eta);
 /* Pc [C,D], Pg [C,K,D] HOST fp32, already L2-normalised by the caller as the reference does */
 int dd_set_prototypes(dd_engine* e, const float* Pc, const float* Pg, int C, int K, int D);
 /* embeds: DEVICE fp32 [2B, text_len, cross_dim], negative half first */
@@ -245,11 +265,19 @@ int dd_denoise_step_n(dd_engine* e, const float* z, int step_index, const float*
                       void* stream);
 int dd_direct_guidance_n(dd_engine* e, const float* z, const int* targets, int step_index, const float* step_noise, float* z_next_out,
                          float* x0_out, float* score_out, float* grad_z_out, int B, void* stream);
+/* Both optional inputs in one call (a schedule set with sde_eta > 0: the stochastic second-order step).  Either pointer may be NULL:
+ * without x0_prev they are the _n calls, without step_noise the _h calls.  A non-NULL step_noise on a schedule with neither eta nor
+ * sde_eta, or a non-NULL x0_prev under solver 0, returns DD_ERR_STATE. */
+int dd_denoise_step_hn(dd_engine* e, const float* z, int step_index, const float* x0_prev, const float* step_noise, float* z_prev_out,
+                       float* x0_out, int B, void* stream);
+int dd_direct_guidance_hn(dd_engine* e, const float* z, const int* targets, int step_index, const float* x0_prev,
+                          const float* step_noise, float* z_next_out, float* x0_out, float* score_out, float* grad_z_out, int B,
+                          void* stream);
 int dd_decode(dd_engine* e, const float* z, float* image_out, int denormalize, int B, void* stream);
 /* Under solver 1 the loop keeps the history itself, in one buffer of the engine, for every input mode: plain and direct-guidance steps
  * read it and leave their x0 in it; the first executed step, the step executed again after transform guidance and the last step run
  * without one (first-order).
- * Under eta > 0 the loop needs unit_ids in either noise_mode (DD_ERR_ARG without): step i of row k takes its noise from
+ * Under eta > 0 or sde_eta > 0 the loop needs unit_ids in either noise_mode (DD_ERR_ARG without): step i of row k takes its noise from
  * (seed, unit_ids[k], stream 16 + i), generated inside the step kernel.  With noise_mode 0 the caller's noise / e / b are read as
  * before and seed / unit_ids key the step noise alone. */
 int dd_expand(dd_engine* e, const dd_expand_args* a, void* stream);

@@ -13,7 +13,7 @@
  *   dd_op_attention_*    scaled-dot-product attention (self, cross, VAE mid block) (:112, :701)
  *   dd_op_sampler_step*  classifier-free guidance + DDIMScheduler.step (:116-119) for every prediction type, with optional CFG rescale
  *                        and, as dd_op_sampler_step_2m, the step of DPM-Solver++(2M), as dd_op_sampler_step_n the stochastic step
- *                        of eta > 0 (all beyond the reference, which builds an
+ *                        of eta > 0, as dd_op_sampler_step_2m_n the step of SDE-DPM-Solver++(2M) (all beyond the reference, which builds an
  *                        epsilon DDIMScheduler); dd_op_cfg_ddim* are its (epsilon, no rescale) mode under their first names
  *   dd_op_bicubic*       F.interpolate(..., (224,224), 'bicubic') (:704, :745)
  *   dd_op_conv_f32       timm conv+BN(+ReLU) of image_encoder.encode_image and its input-gradient in exact fp32
@@ -147,6 +147,25 @@ int dd_op_step_coefs_eta(int prediction_type, double a, double a_prev, double et
 int dd_op_sampler_step_n(const float* m2, int ld, const float* z, const float* noise, float sigma, uint64_t seed, int rng_stream,
                          const uint64_t* unit_ids, float* z_prev, float* x0, int B, int C, int HW, const float* coef_dev,
                          const float* lin_dev, int prediction_type, float guidance_rescale, float* stats, float* part, void* stream);
+/* SDE-DPM-Solver++(2M) (dd_set_schedule_sde): history and noise in one step.  With s = sde_eta in [0, 1], h = lambda(a_prev) - lambda(a):
+ *   dd_op_step_coefs_sde(type, a, a_prev, s, out5) = {A_z, A_m, B_z, B_m, sigma_n} with d = sqrt(1 - a_prev) e^(-s h) in the place of
+ *       sqrt(1 - a_prev) (lin_dev = the first four floats; coef_dev[4] = d rounded once for the division form) and sigma_n =
+ *       sqrt(1 - a_prev) sqrt(1 - e^(-2 s h)).  a_prev = 1: d = sigma_n = 0; a_prev = a: d = sqrt(1 - a_prev), sigma_n = 0.0f; a = 0:
+ *       d = 0, sigma_n = sqrt(1 - a_prev).  -1 as dd_op_step_coefs, for s outside [0, 1] or not finite, and for a result that is not
+ *       finite; s = 0: the floats of dd_op_step_coefs and 0.0f.
+ *   dd_op_step_coef_2m_sde(i, n, a_before, a, a_prev, s, out): *out = sqrt(a_prev) (1 - e^(-(1 + s) h)) / (2 r), 0.0f exactly where
+ *       dd_op_step_coef_2m is; returns -1 for s outside [0, 1] or not finite (and for out == NULL), else 0; s = 0: the float of
+ *       dd_op_step_coef_2m.
+ *   dd_op_sampler_step_2m_n: dd_op_sampler_step_2m and dd_op_sampler_step_n in one call, z' = (fma(B_z, t, B_m m^) + c (x0 - x0_prev))
+ *       + sigma n, the product and the sum rounded separately.  With x0_prev NULL or c == 0 it is dd_op_sampler_step_n, with sigma == 0
+ *       or no noise source dd_op_sampler_step_2m, bit for bit.  x0 may be x0_prev; the generated form takes 16 rows per launch and
+ *       every launch touches its own rows only. */
+int dd_op_step_coefs_sde(int prediction_type, double a, double a_prev, double sde_eta, float* out5);
+int dd_op_step_coef_2m_sde(int step_index, int n_steps, double a_before, double a, double a_prev, double sde_eta, float* out);
+int dd_op_sampler_step_2m_n(const float* m2, int ld, const float* z, const float* x0_prev, float c, const float* noise, float sigma,
+                            uint64_t seed, int rng_stream, const uint64_t* unit_ids, float* z_prev, float* x0, int B, int C, int HW,
+                            const float* coef_dev, const float* lin_dev, int prediction_type, float guidance_rescale, float* stats,
+                            float* part, void* stream);
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int accumulate,
                      void* stream);
 int dd_op_geglu_bwd(const uint16_t* raw, int ld_raw, const uint16_t* dout, int ld_dout, uint16_t* draw, int ld_draw, int M,

@@ -5,6 +5,7 @@ through the schedule in both (guidance_step 20 of 50, 8 of 20), as scripts/exps/
 
     python tools/bench_solver.py [--out profiles/dpmpp_2m.json] [--rounds 3] [--batch 0]
     python tools/bench_solver.py --eta 1 [--out ...]      # instead: DDIM on the 50-step schedule with eta = 0 against eta = ETA
+    python tools/bench_solver.py --sde_eta 1 [--out profiles/dpmpp_2m_sde.json]   # instead: dpmsolver++ on the 20-step schedule, s = 0 / S
 
 One engine; the two settings alternate inside every round (set_schedule between them, outside the timed window); the window is a host
 clock around one `expand` of a fresh batch that ends in a device synchronise.  Reported: the median over the rounds of seconds per
@@ -13,7 +14,8 @@ after it and the decode are inside the batch time, so they are spread over the s
 two batch times follows from the executed step counts; there is no gate on it.  What this does NOT measure: image quality at 20
 against 50 steps -- the weights are synthetic.  With --eta the two settings are the script of record's DDIM loop under eta = 0 and under
 eta = ETA (stochastic DDIM: the step noise is generated inside the step kernel from (seed, unit id, step), so `expand` gets a seed and
-unit ids and still reads the batch's noise / e / b)."""
+unit ids and still reads the batch's noise / e / b).  With --sde_eta they are DPM-Solver++(2M) on the 20-step schedule under sde_eta = 0 and
+under sde_eta = S (SDE-DPM-Solver++(2M): the same generator inside the step kernel's history form)."""
 import argparse
 import json
 import os
@@ -36,8 +38,13 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="0 = the largest of 32 / 16 / 8 that fits the free HBM (bench.py's rule)")
     ap.add_argument("--config", default="sd15", choices=["sd15", "tiny"], help="tiny: a rehearsal of the script, not a measurement")
     ap.add_argument("--eta", type=float, default=None, help="time DDIM 50 under eta = 0 against eta = ETA instead of the two solvers")
+    ap.add_argument("--sde_eta", type=float, default=None, help="time dpmsolver++ 20 under sde_eta = 0 against sde_eta = S instead of the two solvers")
     a = ap.parse_args()
+    if a.eta is not None and a.sde_eta is not None:
+        raise SystemExit("--eta and --sde_eta are two measurements: one at a time")
     settings = SETTINGS if a.eta is None else [dict(SETTINGS[0], name="ddim_50_eta0", eta=0.0), dict(SETTINGS[0], name="ddim_50_eta", eta=a.eta)]
+    if a.sde_eta is not None:
+        settings = [dict(SETTINGS[1], name="dpmsolver++_20_s0", sde_eta=0.0), dict(SETTINGS[1], name="dpmsolver++_20_s", sde_eta=a.sde_eta)]
     from distdiff_amd.config import sd15_config, tiny_config
     from distdiff_amd.engine import Engine, batch_for_free_hbm
     from distdiff_amd.scheduler import DDIMSchedule
@@ -61,12 +68,12 @@ def main():
     def run(s, seed):
         ts = sched.set_timesteps(s["steps"])
         eng.set_schedule(ts, sched.alphas_cumprod, sched.final_alpha_cumprod, guidance_scale=7.5, gs=1.0, ls=1.0, rho=10.0, constraint_value=0.2,
-                         guidance_period=P, solver=s["solver"], eta=s.get("eta", 0.0))
+                         guidance_period=P, solver=s["solver"], eta=s.get("eta", 0.0), sde_eta=s.get("sde_eta", 0.0))
         lat, noise, e, b, tg = batch(seed)
         si = int((1 - STRENGTH) * len(ts))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        kw = dict(seed=seed, unit_ids=list(range(B)), generate_inputs=False) if s.get("eta") else {}
+        kw = dict(seed=seed, unit_ids=list(range(B)), generate_inputs=False) if s.get("eta") or s.get("sde_eta") else {}
         z, img, _ = eng.expand(lat, noise, e, b, tg, si, "transform_guidance", len(ts) - s["guidance_step"], P, want_image=True, **kw)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -89,9 +96,12 @@ def main():
         v, n = times[s["name"]], execd[s["name"]]
         med = statistics.median(v)
         res[s["name"]] = {"solver": s["solver"], "schedule_steps": s["steps"], "executed_steps": n, "guidance_step": s["guidance_step"],
-                          "eta": s.get("eta", 0.0), "s_per_batch": round(med, 4), "s_per_batch_min": round(min(v), 4),
+                          "eta": s.get("eta", 0.0), "sde_eta": s.get("sde_eta", 0.0), "s_per_batch": round(med, 4), "s_per_batch_min": round(min(v), 4),
                           "s_per_batch_max": round(max(v), 4), "images_per_s": round(B / med, 3), "ms_per_executed_step": round(1e3 * med / n, 2)}
-    if a.eta is None:
+    if a.sde_eta is not None:
+        res["batch_time_ratio_s_over_s0"] = round(res["dpmsolver++_20_s"]["s_per_batch"] / res["dpmsolver++_20_s0"]["s_per_batch"], 4)
+        res["not_measured"] = "image quality and diversity under sde_eta > 0: the weights are synthetic"
+    elif a.eta is None:
         res["batch_time_ratio_ddim50_over_2m20"] = round(res["ddim_50"]["s_per_batch"] / res["dpmsolver++_20"]["s_per_batch"], 3)
         res["not_measured"] = "image quality at 20 against 50 steps: the weights are synthetic"
     else:
