@@ -135,14 +135,14 @@ void guide_vae_bwd(dd_engine* E, int k, float* g_x0, hipStream_t s) {
                                  1.f / c.vae_scaling_factor, 0.f, 0, 0.f, 0.f, s, cot_inv(cs)));
 }
 
-// The sampler step on the UNet output of instance k (kernels.h: StepParams lists its modes), and its VJP
-StepParams step_params(dd_engine* E, int k, int step_index) {
+// The sampler step on the UNet output of instance k (kernels.h: StepParams lists its modes) on the given rows of the schedule, and its VJP
+StepParams step_params(dd_engine* E, int k, int step_index, const Schedule::Rows& rows) {
   const dd_config& c = E->cfg;
   const Tn& out = E->unet.t[E->unet_out];
   StepParams p{};
   p.m2 = (const float*)(E->inst[k].unet + out.off); p.ld = out.ld;
   p.B = c.max_batch; p.C = c.unet_out_channels; p.HW = c.latent_size * c.latent_size;
-  p.coef = E->coef_table + (size_t)step_index * 8; p.lin = E->step_table + (size_t)step_index * 4;
+  p.coef = rows.coef + (size_t)step_index * 8; p.lin = rows.lin + (size_t)step_index * 4;
   p.prediction_type = E->sp.prediction_type; p.phi = E->sp.guidance_rescale;
   p.stats = E->inst[k].rs_stats; p.part = E->rs_part;
   return p;
@@ -153,36 +153,38 @@ struct StepNoise {
   const float* noise = nullptr; const uint64_t* unit_ids = nullptr; uint64_t seed = 0;
   bool on() const { return noise || unit_ids; }
 };
+const StepNoise DETERMINISTIC;
 // x0_prev: x0 of step_index - 1 under DPM-Solver++(2M), or null; x0 may be null
 void sampler_step(dd_engine* E, int k, const float* z, int step_index, const float* x0_prev, float* z_prev, float* x0, hipStream_t s,
-                  const StepNoise& sn = StepNoise()) {
-  StepParams p = step_params(E, k, step_index);
+                  const StepNoise& sn) {
+  const Schedule::Rows& rows = E->sched.rows(step_index, sn.on());
+  const StepRow& row = rows.row[step_index];
+  StepParams p = step_params(E, k, step_index, rows);
   p.z = z; p.z_prev = z_prev; p.x0_prev = x0_prev;
-  // sigma = 0 (a' = 1, a' = a): d = sqrt(1-a'), the deterministic rows, c and kernel
-  const bool noisy = sn.on() && (E->eta > 0.f || E->sde_eta > 0.f) && E->sigma[step_index] != 0.f;
-  if (noisy) {
-    p.coef = E->coef_table_eta + (size_t)step_index * 8; p.lin = E->step_table_eta + (size_t)step_index * 4;
-    p.sigma = E->sigma[step_index]; p.noise = sn.noise;
+  if (row.sigma != 0.f) {           // the stochastic rows
+    p.sigma = row.sigma; p.noise = sn.noise;
     p.rng_seed = sn.seed; p.rng_stream = DD_RNG_STEP_STREAM + step_index;
   }
-  // a history comes with solver 1 alone (history_refused): under sde_eta > 0 the stochastic step takes its own c
-  p.c2m = x0_prev ? (noisy ? E->c2m_sde : E->c2m)[step_index] : 0.f;
+  // a history comes with solver 1 alone (history_refused): under sde_eta > 0 the stochastic rows carry their own c
+  p.c2m = x0_prev ? row.c2m : 0.f;
   // the second-order term needs x0 of this step: a caller that does not ask for it has it written to the instance's own buffer
   const bool second_order = x0_prev && p.c2m != 0.f;
   p.x0 = !x0 && second_order ? E->inst[k].x0 : x0;
-  HIPCHK(noisy ? launch_sampler_step_units(p, sn.unit_ids, s) : launch_sampler_step(p, s));
+  HIPCHK(launch_sampler_step_units(p, sn.unit_ids, s));      // sigma = 0: launch_sampler_step(p)
 }
+// every backward differentiates the deterministic step
 void sampler_step_bwd(dd_engine* E, int k, const Ctx& uc, int step_index, const float* g_x0, const float* g_znext, float* g_z, hipStream_t s) {
-  HIPCHK(launch_sampler_step_bwd(step_params(E, k, step_index), g_x0, g_znext, grad_ptr(uc, E->unet.t[E->unet_out]), g_z, s));
+  HIPCHK(launch_sampler_step_bwd(step_params(E, k, step_index, E->sched.det), g_x0, g_znext, grad_ptr(uc, E->unet.t[E->unet_out]), g_z, s));
 }
 // a history is the input of DPM-Solver++(2M) alone: the step-level entry points refuse it under another solver
 bool history_refused(dd_engine* E, const float* x0_prev) {
-  if (x0_prev && E->solver != 1) E->err = "x0_prev is the history of DPM-Solver++(2M): this schedule was set with solver 0 (DDIM)";
-  return x0_prev && E->solver != 1;
+  const bool refused = x0_prev && !E->sched.keeps_history();
+  if (refused) E->err = "x0_prev is the history of DPM-Solver++(2M): this schedule was set with solver 0 (DDIM)";
+  return refused;
 }
 // step noise is the input of a schedule set with eta > 0 or sde_eta > 0 alone
 bool noise_refused(dd_engine* E, const float* step_noise) {
-  const bool refused = step_noise && !(E->eta > 0.f || E->sde_eta > 0.f);
+  const bool refused = step_noise && !E->sched.stochastic();
   if (refused) E->err = "step_noise is the noise of a stochastic DDIM step: this schedule was set with eta = 0";
   return refused;
 }
@@ -191,7 +193,7 @@ bool noise_refused(dd_engine* E, const float* step_noise) {
 // history of a DPM-Solver++(2M) step, sn: the noise of a stochastic step (direct guidance); they change z_next alone, which the reverse
 // pass does not differentiate there
 void guided_forward(dd_engine* E, int k, const float* z_in, int step_index, const int* targets, int normalize, float weight,
-                    float* score, hipStream_t s, const float* x0_prev = nullptr, const StepNoise& sn = StepNoise()) {
+                    float* score, hipStream_t s, const float* x0_prev, const StepNoise& sn) {
   const dd_config& c = E->cfg;
   auto& I = E->inst[k];
   unet_fwd(E, k, z_in, step_index, s);
@@ -240,6 +242,10 @@ void set_config_defaults(dd_config& c) {
 #define DD_TRY(E, ...)                                    \
   try { __VA_ARGS__; return DD_OK; }                      \
   catch (const std::exception& ex) { (E)->err = ex.what(); return DD_ERR_HIP; }
+// the same in the middle of a function: the code goes to rc, nothing returns
+#define DD_TRY_RC(E, rc, ...)                             \
+  try { __VA_ARGS__; rc = DD_OK; }                        \
+  catch (const std::exception& ex) { (E)->err = ex.what(); rc = DD_ERR_HIP; }
 
 extern "C" {
 
@@ -482,70 +488,51 @@ int dd_set_schedule_sde(dd_engine* E, const int* timesteps, int n, const float* 
     if (!(eta >= 0.f && eta <= 1.f)) throw std::runtime_error("eta must be in [0, 1]");
     if (eta > 0.f && solver != 0) throw std::runtime_error("eta > 0 is stochastic DDIM (solver 0): the per-step noise of solver 1 is sde_eta (dd_set_schedule_sde)");
     if (eta > 0.f && n > DD_RNG_STEP_STREAMS) throw std::runtime_error("eta > 0: at most " + std::to_string(DD_RNG_STEP_STREAMS) + " steps (one noise stream per step)");
-    std::vector<float> coef((size_t)n * 8, 0.f), lin((size_t)n * 4, 0.f), c2m;
-    std::vector<float> coef_eta, lin_eta, sigma, c2m_sde; // a stochastic schedule only (c2m_sde: sde_eta > 0)
+    // A complete new schedule is built beside the engine's own and swapped in at the end: a refusal, or an allocation that fails, leaves
+    // the engine as it was.  `out` frees what it holds when this block is left -- the partial new one, or after the swap the old one
+    struct Outgoing { dd_engine* E; Schedule S; ~Outgoing() { for (void* q : S.allocs) E->dfree(q); } } out{E, {}};
+    Schedule& S = out.S;
+    auto alloc = [&](size_t bytes, bool zero) { S.allocs.push_back(E->dmalloc(bytes, zero)); return (float*)S.allocs.back(); };
+    auto upload = [&](const std::vector<float>& h) {
+      float* d = alloc(h.size() * 4, false);
+      HIPCHK(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+      return d;
+    };
+    S.solver = solver;
+    S.rule = StepRule{sp->prediction_type, sde_eta > 0.f ? 2 : eta > 0.f ? 1 : 0, sde_eta > 0.f ? sde_eta : eta};
+    const char* s_name = S.rule.noise == 2 ? "sde_eta" : "eta";
+    std::vector<float> head((size_t)n * 4);      // coef[0..3] of every step, the same under both rules
     const int ratio = num_train / n;
     for (int i = 0; i < n; ++i) {
       const int t = timesteps[i], prev = t - ratio;
       if (t < 0 || t >= num_train) throw std::runtime_error("timestep out of range");
       const double a = alphas_cumprod[t], ap = prev >= 0 ? alphas_cumprod[prev] : final_alpha;
       const double a_before = i > 0 ? alphas_cumprod[timesteps[i - 1]] : 0.0;
-      if (solver == 1) c2m.push_back(sampler_step_coef_2m(i, n, a_before, a, ap));
-      float* q = &coef[(size_t)i * 8];
-      q[0] = sp->guidance_scale; q[1] = (float)sqrt(a); q[2] = (float)sqrt(1 - a); q[3] = (float)sqrt(ap); q[4] = (float)sqrt(1 - ap);
-      if (sampler_step_coefs(sp->prediction_type, a, ap, &lin[(size_t)i * 4]))      // the division form of the step divides by sqrt(a) as well
+      float* q = &head[(size_t)i * 4];
+      q[0] = sp->guidance_scale; q[1] = (float)sqrt(a); q[2] = (float)sqrt(1 - a); q[3] = (float)sqrt(ap);
+      StepRow row;
+      if (sampler_step_row({sp->prediction_type, 0, 0.0}, i, n, a_before, a, ap, &row))      // the division form of the step divides by sqrt(a) as well
         throw std::runtime_error(sp->prediction_type == 0 ? "epsilon-prediction with alphas_cumprod = 0 at timestep " + std::to_string(t) +
                                  " (zero terminal SNR): x0 is undefined there" : "sample-prediction with alphas_cumprod = 1 at timestep " + std::to_string(t));
-      if (eta > 0.f) {
-        float o[5];
-        if (sampler_step_coefs_eta(sp->prediction_type, a, ap, eta, o)) throw std::runtime_error("eta > 0: the step at timestep " + std::to_string(t) + " has no finite sigma");
-        coef_eta.insert(coef_eta.end(), q, q + 8);
-        coef_eta[(size_t)i * 8 + 4] = sampler_step_eta_d(a, ap, eta);
-        lin_eta.insert(lin_eta.end(), o, o + 4);
-        sigma.push_back(o[4]);
+      S.det.row.push_back(row);
+      if (!S.stochastic()) continue;
+      if (sampler_step_row(S.rule, i, n, a_before, a, ap, &row))
+        throw std::runtime_error(std::string(s_name) + " > 0: the step at timestep " + std::to_string(t) + " has no finite sigma");
+      S.sto.row.push_back(row);
+    }
+    auto upload_rows = [&](Schedule::Rows& R) {
+      std::vector<float> coef((size_t)n * 8, 0.f), lin((size_t)n * 4);
+      for (int i = 0; i < n; ++i) {
+        std::copy_n(&head[(size_t)i * 4], 4, &coef[(size_t)i * 8]);
+        coef[(size_t)i * 8 + 4] = R.row[i].d;
+        std::copy_n(R.row[i].lin, 4, &lin[(size_t)i * 4]);
       }
-      if (sde_eta > 0.f) {
-        float o[5], c;
-        if (sampler_step_coefs_sde(sp->prediction_type, a, ap, sde_eta, o) || sampler_step_coef_2m_sde(i, n, a_before, a, ap, sde_eta, &c))
-          throw std::runtime_error("sde_eta > 0: the step at timestep " + std::to_string(t) + " has no finite sigma");
-        coef_eta.insert(coef_eta.end(), q, q + 8);
-        coef_eta[(size_t)i * 8 + 4] = sampler_step_sde_d(a, ap, sde_eta);
-        lin_eta.insert(lin_eta.end(), o, o + 4);
-        sigma.push_back(o[4]);
-        c2m_sde.push_back(c);
-      }
-    }
-    // every refusal is above: from here on the engine's schedule is replaced
-    E->timesteps.assign(timesteps, timesteps + n);
-    E->sp = *sp;
-    E->solver = solver;
-    HIPCHK(hipDeviceSynchronize());
-    for (void* q : E->sched_allocs) E->dfree(q);
-    E->sched_allocs.clear();
-    E->c2m = c2m;
-    E->eta = eta; E->sigma = sigma;
-    E->sde_eta = sde_eta; E->c2m_sde = c2m_sde;
-    E->coef_table_eta = nullptr; E->step_table_eta = nullptr;
-    if (eta > 0.f || sde_eta > 0.f) {
-      E->step_table_eta = (float*)E->dmalloc(lin_eta.size() * 4, false);
-      E->sched_allocs.push_back(E->step_table_eta);
-      HIPCHK(hipMemcpy(E->step_table_eta, lin_eta.data(), lin_eta.size() * 4, hipMemcpyHostToDevice));
-      E->coef_table_eta = (float*)E->dmalloc(coef_eta.size() * 4, false);
-      E->sched_allocs.push_back(E->coef_table_eta);
-      HIPCHK(hipMemcpy(E->coef_table_eta, coef_eta.data(), coef_eta.size() * 4, hipMemcpyHostToDevice));
-    }
-    E->x0_hist = nullptr;
-    if (solver == 1) {
-      E->x0_hist = (float*)E->dmalloc((size_t)c.max_batch * std::max({c.unet_in_channels, c.unet_out_channels, c.vae_latent_channels}) *
-                                      c.latent_size * c.latent_size * 4);
-      E->sched_allocs.push_back(E->x0_hist);
-    }
-    E->step_table = (float*)E->dmalloc(lin.size() * 4, false);
-    E->sched_allocs.push_back(E->step_table);
-    HIPCHK(hipMemcpy(E->step_table, lin.data(), lin.size() * 4, hipMemcpyHostToDevice));
-    E->coef_table = (float*)E->dmalloc(coef.size() * 4, false);
-    E->sched_allocs.push_back(E->coef_table);
-    HIPCHK(hipMemcpy(E->coef_table, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
+      R.coef = upload(coef); R.lin = upload(lin);
+    };
+    upload_rows(S.det);
+    if (S.stochastic()) upload_rows(S.sto);
+    if (S.keeps_history())
+      S.x0_hist = alloc((size_t)c.max_batch * std::max({c.unet_in_channels, c.unet_out_channels, c.vae_latent_channels}) * c.latent_size * c.latent_size * 4, true);
     // sinusoidal timestep embedding (diffusers Timesteps: flip_sin_to_cos, freq_shift) on host, MLP + projections on GPU (fp32)
     const int C0 = c.unet_block_out_channels[0], half = C0 / 2, TE = C0 * 4;
     std::vector<float> sinus((size_t)n * C0);
@@ -557,26 +544,27 @@ int dd_set_schedule_sde(dd_engine* E, const int* timesteps, int n, const float* 
         if (c.unet_flip_sin_to_cos) { sinus[(size_t)i * C0 + j] = cs; sinus[(size_t)i * C0 + half + j] = sn; }
         else { sinus[(size_t)i * C0 + j] = sn; sinus[(size_t)i * C0 + half + j] = cs; }
       }
-    float* d_sin = (float*)E->dmalloc(sinus.size() * 4, false);
-    HIPCHK(hipMemcpy(d_sin, sinus.data(), sinus.size() * 4, hipMemcpyHostToDevice));
-    float* d_h1 = (float*)E->dmalloc((size_t)n * TE * 4, false);
-    float* d_emb = (float*)E->dmalloc((size_t)n * TE * 4, false);
-    E->sched_allocs.push_back(d_sin); E->sched_allocs.push_back(d_h1); E->sched_allocs.push_back(d_emb);
-    E->d_emb = d_emb;
-    E->added_cond_set = false;
+    float* d_sin = upload(sinus);
+    float* d_h1 = alloc((size_t)n * TE * 4, false);
+    S.d_emb = alloc((size_t)n * TE * 4, false);
     HIPCHK(launch_linear_f32(d_sin, E->temb_w1, E->temb_b1, d_h1, n, TE, C0, 0, nullptr));
-    HIPCHK(launch_linear_f32(d_h1, E->temb_w2, E->temb_b2, d_emb, n, TE, TE, 1, nullptr));
+    HIPCHK(launch_linear_f32(d_h1, E->temb_w2, E->temb_b2, S.d_emb, n, TE, TE, 1, nullptr));
     for (ConvW* cw : E->temb_convs) {
-      cw->bias_table = (float*)E->dmalloc((size_t)n * cw->Cout * 4, false);
-      E->sched_allocs.push_back(cw->bias_table);
-      HIPCHK(launch_linear_f32(d_emb, cw->temb_w, cw->temb_b, cw->bias_table, n, cw->Cout, TE, 1, nullptr));
-      if (cw->bias) HIPCHK(launch_add_rowvec_f32(cw->bias_table, cw->bias, n, cw->Cout, nullptr));   // + conv1.bias
-      if (c.unet_add_time_dim > 0) {
-        cw->bias_table_img = (float*)E->dmalloc((size_t)n * 2 * c.max_batch * cw->Cout * 4, false);
-        E->sched_allocs.push_back(cw->bias_table_img);
-      }
+      float* table = alloc((size_t)n * cw->Cout * 4, false);
+      HIPCHK(launch_linear_f32(S.d_emb, cw->temb_w, cw->temb_b, table, n, cw->Cout, TE, 1, nullptr));
+      if (cw->bias) HIPCHK(launch_add_rowvec_f32(table, cw->bias, n, cw->Cout, nullptr));   // + conv1.bias
+      S.temb_bias.push_back({table, c.unet_add_time_dim > 0 ? alloc((size_t)n * 2 * c.max_batch * cw->Cout * 4, false) : nullptr});
     }
+    // the new tables are complete and nothing in flight reads the old ones: from here on the engine's schedule is replaced
     HIPCHK(hipDeviceSynchronize());
+    std::swap(E->sched, S);
+    E->timesteps.assign(timesteps, timesteps + n);
+    E->sp = *sp;
+    E->added_cond_set = false;
+    for (size_t k = 0; k < E->temb_convs.size(); ++k) {
+      E->temb_convs[k]->bias_table = E->sched.temb_bias[k].first;
+      E->temb_convs[k]->bias_table_img = E->sched.temb_bias[k].second;
+    }
   });
 }
 
@@ -623,7 +611,7 @@ int dd_set_added_cond(dd_engine* E, const float* text_embeds, const float* time_
     check_batch(E, B);
     const dd_config& c = E->cfg;
     if (c.unet_add_time_dim <= 0) throw std::runtime_error("this UNet has no additional conditioning (unet_add_time_dim == 0)");
-    if (!E->d_emb) throw std::runtime_error("dd_set_schedule first");
+    if (!E->sched.d_emb) throw std::runtime_error("dd_set_schedule first");
     hipStream_t s = (hipStream_t)stream;
     const int nb = 2 * B, n = (int)E->timesteps.size(), TE = c.unet_block_out_channels[0] * 4;
     const int Dt = c.unet_add_text_dim, Ds = 6 * c.unet_add_time_dim, Din = Dt + Ds;
@@ -640,7 +628,7 @@ int dd_set_added_cond(dd_engine* E, const float* text_embeds, const float* time_
     }
     HIPCHK(launch_linear_f32(cat, E->add_w1, E->add_b1, h1, nb, TE, Din, 0, s));
     HIPCHK(launch_linear_f32(h1, E->add_w2, E->add_b2, aug, nb, TE, TE, 1, s));
-    HIPCHK(launch_add_outer_f32(E->d_emb, aug, X, n, nb, TE, s));                 // emb[step, image] = time_embedding(t) + aug_emb
+    HIPCHK(launch_add_outer_f32(E->sched.d_emb, aug, X, n, nb, TE, s));                 // emb[step, image] = time_embedding(t) + aug_emb
     for (ConvW* cw : E->temb_convs) {
       HIPCHK(launch_linear_f32(X, cw->temb_w, cw->temb_b, cw->bias_table_img, n * nb, cw->Cout, TE, 1, s));
       if (cw->bias) HIPCHK(launch_add_rowvec_f32(cw->bias_table_img, cw->bias, n * nb, cw->Cout, s));
@@ -656,9 +644,9 @@ int dd_add_noise(dd_engine* E, const float* x, const float* noise, float* out, i
   DD_TRY(E, {
     if (step_index < 0 || step_index >= (int)E->timesteps.size()) throw std::runtime_error("step_index out of range");
     const dd_config& c = E->cfg;
-    // coef_table[step][1..2] = sqrt(a_t), sqrt(1-a_t)
+    // coef[step][1..2] = sqrt(a_t), sqrt(1-a_t)
     HIPCHK(launch_axpby(x, noise, out, (size_t)B * c.unet_in_channels * c.latent_size * c.latent_size,
-                        E->coef_table + (size_t)step_index * 8 + 1, (hipStream_t)stream));
+                        E->sched.det.coef + (size_t)step_index * 8 + 1, (hipStream_t)stream));
   });
 }
 
@@ -827,7 +815,8 @@ int dd_transform_guidance(dd_engine* E, const float* z, const int* targets, cons
     const float weight = 1.f / (float)E->sp.guidance_period;   // score / args.guidance_period (:719)
     for (int k = 0; k < P; ++k) {
       const float* zin = E->inst[k].z_in;
-      guided_forward(E, k, zin, first_step_index + k, targets, 0, weight, score, s);
+      // the chained look-ahead steps are first-order and deterministic under every schedule: their reverse pass differentiates them
+      guided_forward(E, k, zin, first_step_index + k, targets, 0, weight, score, s, /*x0_prev=*/nullptr, DETERMINISTIC);
       if (k + 1 < P) HIPCHK(hipMemcpyAsync(E->inst[k + 1].z_in, E->inst[k].z_next, (size_t)BC * HW * 4, hipMemcpyDeviceToDevice, s));
     }
     float* g_next = nullptr;
@@ -897,12 +886,9 @@ static int direct_guidance_call(dd_engine* E, const float* z, const int* targets
 
 // out [B, n_per_unit] of one stream of the counter-based generator; the unit ids travel in the kernel arguments, DD_RNG_UNITS per launch
 static void philox_units_enqueue(uint64_t seed, int rng_stream, const uint64_t* unit_ids, int B, int64_t n_per_unit, float* out, hipStream_t s) {
-  for (int u0 = 0; u0 < B; u0 += DD_RNG_UNITS) {
-    RngUnits ids{};
-    const int cnt = std::min(DD_RNG_UNITS, B - u0);
-    for (int k = 0; k < cnt; ++k) { ids.lo[k] = (unsigned)unit_ids[u0 + k]; ids.hi[k] = (unsigned)(unit_ids[u0 + k] >> 32); }
-    HIPCHK(launch_philox_units(ids, cnt, seed, rng_stream, n_per_unit, out + (size_t)u0 * n_per_unit, s));
-  }
+  HIPCHK(for_rng_unit_ranges(unit_ids, B, [&](const RngUnits& ids, int u0, int cnt) {
+    return launch_philox_units(ids, cnt, seed, rng_stream, n_per_unit, out + (size_t)u0 * n_per_unit, s);
+  }));
 }
 
 int dd_randn_units(dd_engine* E, uint64_t seed, int rng_stream, const uint64_t* unit_ids, int B, int64_t n_per_unit, float* out, void* stream) {
@@ -919,14 +905,11 @@ static int expand_generated_inputs(dd_engine* E, const dd_expand_args* a, float*
     if (a->text_to_img) {
       philox_units_enqueue(a->seed, 0, a->unit_ids, a->B, (int64_t)c.unet_in_channels * HW, z0, s);      // z = n * init_noise_sigma (= 1 for DDIM)
     } else {
-      for (int u0 = 0; u0 < a->B; u0 += DD_RNG_UNITS) {
-        RngUnits ids{};
-        const int cnt = std::min(DD_RNG_UNITS, a->B - u0);
-        for (int k = 0; k < cnt; ++k) { ids.lo[k] = (unsigned)a->unit_ids[u0 + k]; ids.hi[k] = (unsigned)(a->unit_ids[u0 + k] >> 32); }
+      HIPCHK(for_rng_unit_ranges(a->unit_ids, a->B, [&](const RngUnits& ids, int u0, int cnt) {
         const size_t off = (size_t)u0 * c.unet_in_channels * HW;
-        HIPCHK(launch_philox_add_noise(ids, cnt, a->seed, a->image_latents + off, z0 + off, c.unet_in_channels, HW, a->offset_noise,
-                                       E->coef_table + (size_t)a->start_index * 8 + 1, s));
-      }
+        return launch_philox_add_noise(ids, cnt, a->seed, a->image_latents + off, z0 + off, c.unet_in_channels, HW, a->offset_noise,
+                                       E->sched.det.coef + (size_t)a->start_index * 8 + 1, s);
+      }));
     }
     if (a->guidance_type == 1) {
       philox_units_enqueue(a->seed, 2, a->unit_ids, a->B, 4, E->rng_eb, s);
@@ -944,8 +927,8 @@ int dd_expand(dd_engine* E, const dd_expand_args* a, void* stream) {
   if (a->text_to_img && a->start_index != 0) { E->err = "text_to_img runs the whole schedule: start_index must be 0"; return DD_ERR_ARG; }
   // eta > 0 or sde_eta > 0: the noise of step i of row k is generated from (seed, unit_ids[k], stream 16 + i) in either noise_mode
   StepNoise sn;
-  if (E->eta > 0.f || E->sde_eta > 0.f) {
-    if (!a->unit_ids) { E->err = std::string("this schedule was set with ") + (E->eta > 0.f ? "eta" : "sde_eta") + " > 0: dd_expand needs unit_ids (with seed they key the noise of every step)"; return DD_ERR_ARG; }
+  if (E->sched.stochastic()) {
+    if (!a->unit_ids) { E->err = std::string("this schedule was set with ") + (E->sched.rule.noise == 1 ? "eta" : "sde_eta") + " > 0: dd_expand needs unit_ids (with seed they key the noise of every step)"; return DD_ERR_ARG; }
     sn.unit_ids = a->unit_ids; sn.seed = a->seed;
   }
   const float* ch_e = a->e;
@@ -957,12 +940,11 @@ int dd_expand(dd_engine* E, const dd_expand_args* a, void* stream) {
     ch_b = E->rng_eb + (size_t)a->B * 4;
   } else if (a->text_to_img) {
     // the caller's noise is the first latent (init_noise_sigma = 1): add_noise is skipped
-    rc = DD_OK;
-    try {
+    DD_TRY_RC(E, rc, {
       check_batch(E, a->B);
       const dd_config& c = E->cfg;
       HIPCHK(hipMemcpyAsync(E->f32_tmp[3], a->noise, (size_t)a->B * c.unet_in_channels * c.latent_size * c.latent_size * 4, hipMemcpyDeviceToDevice, s));
-    } catch (const std::exception& ex) { E->err = ex.what(); return DD_ERR_HIP; }
+    });
   } else {
     rc = dd_add_noise(E, a->image_latents, a->noise, E->f32_tmp[3], a->B, a->start_index, stream);
   }
@@ -971,7 +953,7 @@ int dd_expand(dd_engine* E, const dd_expand_args* a, void* stream) {
   float* nxt = E->f32_tmp[4];
   // DPM-Solver++(2M): every step leaves its x0 in the one history buffer (read and written in place); `hist` is that buffer once it
   // holds x0 of step i - 1 on the trajectory `cur` is on.  Under DDIM both stay null and the calls are those of version 8.
-  float* const keep = E->solver == 1 ? E->x0_hist : nullptr;
+  float* const keep = E->sched.keeps_history() ? E->sched.x0_hist : nullptr;
   const float* hist = nullptr;
   for (int i = a->start_index; i < n; ++i) {
     const float* h = i == n - 1 ? nullptr : hist;          // the final step is first-order
@@ -991,10 +973,11 @@ int dd_expand(dd_engine* E, const dd_expand_args* a, void* stream) {
     hist = keep;
     std::swap(cur, nxt);
   }
-  try {
+  DD_TRY_RC(E, rc, {
     const dd_config& c = E->cfg;
     HIPCHK(hipMemcpyAsync(a->z_out, cur, (size_t)a->B * c.unet_in_channels * c.latent_size * c.latent_size * 4, hipMemcpyDeviceToDevice, s));
-  } catch (const std::exception& ex) { E->err = ex.what(); return DD_ERR_HIP; }
+  });
+  if (rc) return rc;
   if (a->image_out) return dd_decode(E, cur, a->image_out, 1, a->B, stream);
   return DD_OK;
 }

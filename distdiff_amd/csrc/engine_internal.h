@@ -229,6 +229,30 @@ inline bf16_t* grad_ptr(const Ctx& c, const Tn& t) { if (g_plan_check) grad_acce
 inline float* act_f32(const Ctx& c, const Tn& t) { return (float*)act_raw(c, t); }
 inline float* grad_f32(const Ctx& c, const Tn& t) { if (g_plan_check) grad_access_check(t); return (float*)(c.grad + t.goff); }
 
+// What dd_set_schedule* builds whole and then swaps in: the rule, per step the deterministic row and (under a stochastic rule) the
+// stochastic one (kernels.h: sampler_step_row), their device tables in the layout the step kernels read, and the buffers that live
+// and die with the schedule.  An engine without a schedule holds an empty one.
+struct Schedule {
+  int solver = 0;                  // 0 DDIM, 1 DPM-Solver++(2M)
+  StepRule rule{};                 // rule.noise: 0 none, 1 eta > 0 (solver 0), 2 sde_eta > 0 (solver 1); rule.s = that eta / sde_eta
+  struct Rows {
+    std::vector<StepRow> row;      // host, one per step: the kernel takes sigma and c2m by value
+    float* coef = nullptr;         // device [n][8]: guidance_scale, sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), d, -, -, -
+    float* lin = nullptr;          // device [n][4]: A_z, A_m, B_z, B_m of the linear step form (v_prediction / sample models, CFG rescale)
+  };
+  Rows det, sto;                   // the rows of rule 0 and of `rule`; sto is empty unless stochastic()
+  float* x0_hist = nullptr;        // keeps_history() only: dd_expand's history, x0 of the previous step [B,C,L,L]
+  float* d_emb = nullptr;          // [n][TE] time_embedding(t)
+  std::vector<std::pair<float*, float*>> temb_bias;   // per entry of dd_engine::temb_convs: its bias_table and bias_table_img
+  std::vector<void*> allocs;       // every device buffer above, and the scratch the tables were computed from
+  bool stochastic() const { return rule.noise != 0; }
+  bool keeps_history() const { return solver == 1; }
+  // The rows step i reads.  want_noise: the caller has a noise source for this step -- a plain or a direct-guidance step; transform
+  // guidance's chained steps and every backward ask for `det`.  The stochastic rows answer only where they differ: sigma_i = 0 (a' = 1,
+  // a' = a) is d = sqrt(1-a'), the deterministic rows, c and kernel
+  const Rows& rows(int i, bool want_noise) const { return want_noise && stochastic() && sto.row[i].sigma != 0.f ? sto : det; }
+};
+
 }  // namespace ddi
 
 using namespace ddi;
@@ -264,28 +288,14 @@ struct dd_engine {
   float* temb_w1 = nullptr; float* temb_b1 = nullptr; float* temb_w2 = nullptr; float* temb_b2 = nullptr;
   // SDXL text_time conditioning
   float* add_w1 = nullptr; float* add_b1 = nullptr; float* add_w2 = nullptr; float* add_b2 = nullptr;
-  float* d_emb = nullptr;          // [n_steps][TE] time_embedding(t) of the current schedule
   bool added_cond_set = false;
 
-  // schedule
+  // schedule: replaced as a whole by dd_set_schedule*, with the timestep list and the sampler parameters it was built for
+  Schedule sched;
   std::vector<int> timesteps;
-  float* coef_table = nullptr;   // [n][8]: guidance_scale, sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev), -, -, -
-  float* step_table = nullptr;   // [n][4]: A_z, A_m, B_z, B_m of the linear step form (v_prediction / sample models, CFG rescale)
-  std::vector<float> c2m;        // DPM-Solver++(2M) only: c_i of every step (host; the kernel takes it by value), empty under DDIM
-  float* x0_hist = nullptr;      // DPM-Solver++(2M) only: dd_expand's history, x0 of the previous step [B,C,L,L] (in sched_allocs)
-  // a stochastic schedule only -- eta > 0 (dd_set_schedule_e) or sde_eta > 0 (dd_set_schedule_sde); all empty / null otherwise: sigma_i of every step (host; the kernel takes it by value) and the
-  // rows the stochastic steps read in place of coef_table / step_table -- sqrt(1-a_prev) and B_z, B_m with d (sampler_step_coefs_eta /
-  // sampler_step_coefs_sde) -- and, under sde_eta > 0, c2m_sde: c_i of the stochastic second-order step (sampler_step_coef_2m_sde; host).
-  // step_params() keeps pointing at the eta = 0 tables: transform guidance's chained steps and every backward stay deterministic
-  std::vector<float> sigma;
-  float* coef_table_eta = nullptr; float* step_table_eta = nullptr;
-  float eta = 0.f;
-  std::vector<float> c2m_sde;
-  float sde_eta = 0.f;           // SDE-DPM-Solver++(2M), solver 1 only; never > 0 together with eta
+  dd_sampler_params sp{};
   float* cot_part = nullptr; float* cot_scale = nullptr;   // fp16 build only: partials and {s, 1 / s} of the cotangent scale (launch_cot_scale)
   float* rs_part = nullptr;      // CFG rescale: block partials of the per-image reductions (scratch, consumed by the next kernel)
-  dd_sampler_params sp{};
-  int solver = 0;                // dd_set_schedule_s: 0 DDIM, 1 DPM-Solver++(2M)
   // prototypes
   float* Pc = nullptr; float* Pg = nullptr; int pC = 0, pK = 0, pD = 0;
 
@@ -321,7 +331,6 @@ struct dd_engine {
       if (dev_allocs[i] == p) { dev_allocs[i] = dev_allocs.back(); dev_allocs.pop_back(); break; }
     hipFree(p);
   }
-  std::vector<void*> sched_allocs;   // tables of the current schedule (replaced by the next dd_set_schedule)
   // packed weights: every weight-derived device buffer in creation order (dd_packed_bytes / dd_export_packed / dd_import_packed)
   int declared = 0;
   bool shape_only = false;           // tensors were declared (shapes only): buffers are allocated, their content arrives by import

@@ -205,15 +205,15 @@ hipError_t launch_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int
 //                                scratch of sampler_step_scratch_floats(B, HW) floats; the backward re-reads m2 of that step
 //   x0_prev != null and c2m != 0 DPM-Solver++(2M), forward only (the guidance calls differentiate x0, which does not depend on the
 //                                history): x0 is required and always written, and may alias x0_prev.  Otherwise x0_prev is not read
-//   sigma != 0 and a noise source stochastic DDIM (eta > 0; forward only): coef / lin are the eta rows (sampler_step_coefs_eta: sqrt(1-a')
+//   sigma != 0 and a noise source stochastic DDIM (eta > 0; forward only): coef / lin are the rows of rule 1 (sampler_step_row: sqrt(1-a')
 //                                becomes d) and z' gains sigma n, n ~ N(0,1) per element: read from `noise` when it is given, otherwise
 //                                generated in registers when rng_count > 0 -- element j = ch * HW + pix of row b takes lane j & 3 of Philox
 //                                block j >> 2 of (rng_seed, rng_stream, unit id of row b - rng_row0), the bits launch_philox_units writes.
 //                                The generated form steps rows [rng_row0, rng_row0 + rng_count) alone, rng_count <= DD_RNG_UNITS ids per
 //                                launch: a larger batch is several launches over row ranges in order, and the one with rng_row0 == 0
 //                                computes the statistics of phi != 0 for the whole batch.
-//   both of the two above        SDE-DPM-Solver++(2M) (forward only): coef / lin are the SDE rows (sampler_step_coefs_sde), c2m is
-//                                sampler_step_coef_2m_sde, z' = (the history step on those rows) + sigma n.  The generated form keeps its
+//   both of the two above        SDE-DPM-Solver++(2M) (forward only): coef / lin are the rows of rule 2 and c2m is their c,
+//                                z' = (the history step on those rows) + sigma n.  The generated form keeps its
 //                                row ranges; every launch reads and writes its own rows only, so x0 may still alias x0_prev.
 //                                With sigma == 0 or no source: the step above, nothing of this block is read.
 // ld: a multiple of 8; C <= 8; B <= 65535; anything else is hipErrorInvalidValue in front of any launch.  No atomics: bitwise deterministic.
@@ -222,36 +222,48 @@ struct RngUnits { unsigned lo[DD_RNG_UNITS], hi[DD_RNG_UNITS]; };
 struct StepParams {
   const float* m2; int ld;             // model output, fp32 NHWC rows [2B*HW, ld], unconditional half first
   const float* z;                      // NCHW fp32 [B, C, HW], as x0_prev, z_prev and x0
-  const float* x0_prev; float c2m;     // history and c of this step (sampler_step_coef_2m)
+  const float* x0_prev; float c2m;     // history and c of this step (StepRow::c2m)
   float* z_prev; float* x0;            // x0 may be null in a first-order step
   int B, C, HW;
   const float* coef;                   // device: {guidance_scale, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev}
-  const float* lin;                    // device: {A_z, A_m, B_z, B_m} (sampler_step_coefs)
+  const float* lin;                    // device: {A_z, A_m, B_z, B_m} (StepRow::lin)
   int prediction_type; float phi;      // 0 epsilon, 1 v_prediction, 2 sample; CFG rescale
   float* stats; float* part;
   const float* noise; float sigma;     // eta > 0 / SDE: explicit step noise NCHW fp32 [B, C, HW] (or null: generated) and sigma of this step
   uint64_t rng_seed; int rng_stream;   // the generated form: Philox key and stream (16 + step index)
   RngUnits rng_ids; int rng_count, rng_row0;
 };
-int sampler_step_coefs(int prediction_type, double a, double a_prev, float* out4);      // host; -1: unknown type or a singular step
-// {A_z, A_m, B_z, B_m, sigma} of the DDIM step with eta in [0, 1] (diffusers DDIMScheduler.step): sigma = eta sqrt((1-a')/(1-a) (1-a/a')),
-// d = sqrt(max(0, 1 - a' - sigma^2)) takes the place of sqrt(1-a') in B_z / B_m.  Host, double; -1 as above, for eta outside [0, 1] and
-// for a result that is not finite.  eta = 0: the four floats of sampler_step_coefs bit for bit and sigma = 0.0f.
-int sampler_step_coefs_eta(int prediction_type, double a, double a_prev, double eta, float* out5);
-float sampler_step_eta_d(double a, double a_prev, double eta);      // d of that step, rounded once: coef[4] of the division form
-// {A_z, A_m, B_z, B_m, sigma_n} of the SDE-DPM-Solver++(2M) step with s in [0, 1] (k-diffusion sample_dpmpp_2m_sde's eta; s = 1: diffusers
-// sde-dpmsolver++): h = lambda(a') - lambda(a), d = sqrt(1-a') e^(-s h) takes the place of sqrt(1-a') in B_z / B_m, sigma_n = sqrt(1-a')
-// sqrt(-expm1(-2 s h)).  a' = 1: d = sigma_n = 0; a' = a: (sqrt(1-a'), 0.0f); a = 0: (0, sqrt(1-a')).  Host, double; -1 where
-// sampler_step_coefs gives it, for s outside [0, 1] and for a result that is not finite.  s = 0: the floats of sampler_step_coefs, 0.0f.
-int sampler_step_coefs_sde(int prediction_type, double a, double a_prev, double s, float* out5);
-float sampler_step_sde_d(double a, double a_prev, double s);        // d of that step, rounded once: coef[4] of the division form
+// The host numbers of step i of an n-step schedule under one rule, from alphas_cumprod at step i - 1, at step i and at its previous
+// timestep; formed in double, each float rounded once.  One function states them for every mode:
+//   lin   {A_z, A_m, B_z, B_m} of the linear form, B_z / B_m on d in place of sqrt(1-a')
+//   d     what the direction term keeps of the noise level 1 - a': coef[4] of the division form.  sqrt(1-a') under rule 0
+//   sigma the scale of the fresh noise, d^2 + sigma^2 = 1 - a'.  0.0f under rule 0
+//   c2m   c of the second-order step, c = sqrt(a') (1 - e^-h') / (2 r) with h' = h (rules 0, 1) or (1 + s) h (rule 2); exactly 0 for the
+//         first and the last step and wherever it is undefined
+// rule 1 (DDIM with eta = s, diffusers DDIMScheduler.step): sigma = s sqrt((1-a')/(1-a) (1-a/a')), d = sqrt(max(0, 1 - a' - sigma^2)).
+// rule 2 (SDE-DPM-Solver++(2M), k-diffusion sample_dpmpp_2m_sde's eta = s; s = 1: diffusers sde-dpmsolver++): h = lambda(a') - lambda(a),
+// d = sqrt(1-a') e^(-s h), sigma = sqrt(1-a') sqrt(-expm1(-2 s h)); a' = 1: d = sigma = 0; a' = a: (sqrt(1-a'), 0.0f); a = 0: (0, sqrt(1-a')).
+// s = 0 under rule 1 or 2 gives the floats of rule 0 bit for bit.
+// Returns 0; -1 refused in front of the arithmetic, *out untouched: s outside [0, 1] under rule 1 or 2, then an unknown prediction type or
+// a singular step (a <= 0 for epsilon, a >= 1 for sample); -2 a row of rule 1 or 2 that is not finite, which *out then holds.  Rule 0
+// does not look: its row at a = 1e-80 is {inf, -inf, inf, -inf} with 0.
+struct StepRule { int prediction_type; int noise; double s; };      // noise: 0 none, 1 DDIM eta, 2 SDE-DPM-Solver++(2M); s = eta or sde_eta
+struct StepRow { float lin[4]; float d; float sigma; float c2m; };
+int sampler_step_row(const StepRule& r, int i, int n, double a_before, double a, double a_prev, StepRow* out);
 size_t sampler_step_scratch_floats(int B, int HW);
-// c = sampler_step_coef_2m(i, n, a at step i - 1, a at step i, a at its previous timestep), host, double; exactly 0 for the first and
-// the last step and wherever it is undefined
-float sampler_step_coef_2m(int i, int n, double a_before, double a, double a_prev);
-// the SDE variant: *out = sqrt(a') (1 - e^-((1+s) h)) / (2 r), 0.0f exactly where sampler_step_coef_2m is; -1 for s outside [0, 1] (*out is
-// then not written), else 0.  s = 0: the float of sampler_step_coef_2m
-int sampler_step_coef_2m_sde(int i, int n, double a_before, double a, double a_prev, double s, float* out);
+// HOST unit_ids[0, B) in ranges of DD_RNG_UNITS, the most one launch carries: f(ids, first row, count) per range, in order; the first
+// error ends the walk
+template <class F>
+hipError_t for_rng_unit_ranges(const uint64_t* unit_ids, int B, F f) {
+  for (int r0 = 0; r0 < B; r0 += DD_RNG_UNITS) {
+    RngUnits ids{};
+    const int cnt = B - r0 < DD_RNG_UNITS ? B - r0 : DD_RNG_UNITS;
+    for (int k = 0; k < cnt; ++k) { ids.lo[k] = (unsigned)unit_ids[r0 + k]; ids.hi[k] = (unsigned)(unit_ids[r0 + k] >> 32); }
+    const hipError_t e = f(ids, r0, cnt);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 hipError_t launch_sampler_step(const StepParams& p, hipStream_t s);
 // the generated form for a whole batch: unit_ids HOST [p.B], read before the call returns; DD_RNG_UNITS rows per launch (p.rng_ids,
 // rng_count and rng_row0 are filled here).  With sigma == 0 this is launch_sampler_step(p).

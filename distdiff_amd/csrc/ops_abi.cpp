@@ -90,6 +90,16 @@ static StepParams step_params(const float* m2, int ld, int B, int C, int HW, con
   p.phi = guidance_rescale; p.stats = const_cast<float*>(stats); p.part = part;
   return p;
 }
+// the five coefficient ops on sampler_step_row: a row refused in front of the arithmetic leaves `out` untouched, a row a stochastic rule
+// found not finite is written and refused
+static int step_row_op(const StepRule& r, double a, double a_prev, float* out, int count) {
+  StepRow row;
+  if (!out) return -1;
+  const int rc = sampler_step_row(r, 0, 0, 0.0, a, a_prev, &row);
+  if (rc == -1) return -1;
+  for (int k = 0; k < count; ++k) out[k] = k < 4 ? row.lin[k] : row.sigma;
+  return rc ? -1 : 0;
+}
 int dd_op_cfg_ddim(const float* eps2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW, const float* coef,
                    void* st) {
   return dd_op_sampler_step(eps2, ld, z, z_prev, x0, B, C, HW, coef, nullptr, 0, 0.f, nullptr, nullptr, st);
@@ -99,8 +109,7 @@ int dd_op_cfg_ddim_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_eps2
   return dd_op_sampler_step_bwd(g_x0, g_zprev, g_eps2, ld, g_z, B, C, HW, coef, nullptr, 0, 0.f, nullptr, nullptr, nullptr, st);
 }
 int dd_op_step_coefs(int prediction_type, double a, double a_prev, float* out4) {
-  if (!out4) return -1;
-  return sampler_step_coefs(prediction_type, a, a_prev, out4);
+  return step_row_op({prediction_type, 0, 0.0}, a, a_prev, out4, 4);
 }
 size_t dd_op_sampler_step_scratch_floats(int B, int HW) { return sampler_step_scratch_floats(B, HW); }
 int dd_op_sampler_step(const float* m2, int ld, const float* z, float* z_prev, float* x0, int B, int C, int HW, const float* coef,
@@ -113,40 +122,42 @@ int dd_op_sampler_step_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_
   return (int)launch_sampler_step_bwd(step_params(m2, ld, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part), g_x0, g_zprev,
                                       g_m2, g_z, S(st));
 }
+// c does not depend on the prediction type: it is asked of the v-prediction rule, which refuses no (a, a')
 float dd_op_step_coef_2m(int step_index, int n_steps, double a_before, double a, double a_prev) {
-  return sampler_step_coef_2m(step_index, n_steps, a_before, a, a_prev);
+  StepRow row;
+  sampler_step_row({1, 0, 0.0}, step_index, n_steps, a_before, a, a_prev, &row);
+  return row.c2m;
 }
 int dd_op_sampler_step_2m(const float* m2, int ld, const float* z, const float* x0_prev, float c2m, float* z_prev, float* x0, int B, int C,
                           int HW, const float* coef, const float* lin, int prediction_type, float guidance_rescale, float* stats,
                           float* part, void* st) {
-  StepParams p = step_params(m2, ld, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part);
-  p.z = z; p.x0_prev = x0_prev; p.c2m = c2m; p.z_prev = z_prev; p.x0 = x0;
-  return (int)launch_sampler_step(p, S(st));
+  return dd_op_sampler_step_2m_n(m2, ld, z, x0_prev, c2m, nullptr, 0.f, 0, 0, nullptr, z_prev, x0, B, C, HW, coef, lin, prediction_type,
+                                 guidance_rescale, stats, part, st);
 }
 int dd_op_step_coefs_eta(int prediction_type, double a, double a_prev, double eta, float* out5) {
-  if (!out5) return -1;
-  return sampler_step_coefs_eta(prediction_type, a, a_prev, eta, out5);
+  return step_row_op({prediction_type, 1, eta}, a, a_prev, out5, 5);
 }
 int dd_op_sampler_step_n(const float* m2, int ld, const float* z, const float* noise, float sigma, uint64_t seed, int rng_stream,
                          const uint64_t* unit_ids, float* z_prev, float* x0, int B, int C, int HW, const float* coef, const float* lin,
                          int prediction_type, float guidance_rescale, float* stats, float* part, void* st) {
-  StepParams p = step_params(m2, ld, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part);
-  p.z = z; p.z_prev = z_prev; p.x0 = x0;
-  if (noise || unit_ids) { p.noise = noise; p.sigma = sigma; p.rng_seed = seed; p.rng_stream = rng_stream; }
-  return (int)launch_sampler_step_units(p, unit_ids, S(st));
+  return dd_op_sampler_step_2m_n(m2, ld, z, nullptr, 0.f, noise, sigma, seed, rng_stream, unit_ids, z_prev, x0, B, C, HW, coef, lin,
+                                 prediction_type, guidance_rescale, stats, part, st);
 }
 int dd_op_step_coefs_sde(int prediction_type, double a, double a_prev, double sde_eta, float* out5) {
-  if (!out5) return -1;
-  return sampler_step_coefs_sde(prediction_type, a, a_prev, sde_eta, out5);
+  return step_row_op({prediction_type, 2, sde_eta}, a, a_prev, out5, 5);
 }
 int dd_op_step_coef_2m_sde(int step_index, int n_steps, double a_before, double a, double a_prev, double sde_eta, float* out) {
-  if (!out) return -1;
-  return sampler_step_coef_2m_sde(step_index, n_steps, a_before, a, a_prev, sde_eta, out);
+  StepRow row;
+  if (!out || sampler_step_row({1, 2, sde_eta}, step_index, n_steps, a_before, a, a_prev, &row) == -1) return -1;
+  *out = row.c2m;
+  return 0;
 }
 int dd_op_sampler_step_2m_n(const float* m2, int ld, const float* z, const float* x0_prev, float c2m, const float* noise, float sigma,
                             uint64_t seed, int rng_stream, const uint64_t* unit_ids, float* z_prev, float* x0, int B, int C, int HW,
                             const float* coef, const float* lin, int prediction_type, float guidance_rescale, float* stats, float* part,
                             void* st) {
+  // the general forward op, which the other three call: the optional history (x0_prev, c2m) and the optional noise (the tensor, or seed /
+  // stream / unit_ids for the generated form; with neither, sigma stays 0 and the launch is launch_sampler_step's deterministic one)
   StepParams p = step_params(m2, ld, B, C, HW, coef, lin, prediction_type, guidance_rescale, stats, part);
   p.z = z; p.x0_prev = x0_prev; p.c2m = c2m; p.z_prev = z_prev; p.x0 = x0;
   if (noise || unit_ids) { p.noise = noise; p.sigma = sigma; p.rng_seed = seed; p.rng_stream = rng_stream; }

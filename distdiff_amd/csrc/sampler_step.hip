@@ -275,33 +275,17 @@ static int step_coefs_d(int prediction_type, double a, double ap, double sbp, fl
   out4[0] = (float)Az; out4[1] = (float)Am; out4[2] = (float)Bz; out4[3] = (float)Bm;
   return 0;
 }
-int sampler_step_coefs(int prediction_type, double a, double ap, float* out4) { return step_coefs_d(prediction_type, a, ap, sqrt(1 - ap), out4); }
 // eta in [0, 1]: the direction term keeps d = sqrt(max(0, 1 - a' - sigma^2)) of the noise level 1 - a' and sigma^2 goes to fresh noise.
 // The max is needed: at a = 0 (the first trailing step of a zero-terminal-SNR table) eta = 1 gives 1 - a' - sigma^2 ~ 1e-16 of either
-// sign.  eta = 0 takes sigma = 0 without evaluating the variance: d is then sqrt(1 - a') and the floats are those of sampler_step_coefs.
+// sign.  eta = 0 takes sigma = 0 without evaluating the variance: d is then sqrt(1 - a') and the floats are those of rule 0.
 static void eta_sigma_d(double a, double ap, double eta, double* sigma, double* d) {
   *sigma = eta > 0 ? eta * sqrt((1 - ap) / (1 - a) * (1 - a / ap)) : 0.0;
   const double d2 = 1 - ap - *sigma * *sigma;
   *d = sqrt(d2 > 0 ? d2 : 0.0);
 }
-int sampler_step_coefs_eta(int prediction_type, double a, double ap, double eta, float* out5) {
-  if (!(eta >= 0 && eta <= 1)) return -1;
-  double sigma, d;
-  eta_sigma_d(a, ap, eta, &sigma, &d);
-  if (step_coefs_d(prediction_type, a, ap, d, out5)) return -1;
-  out5[4] = (float)sigma;
-  for (int k = 0; k < 5; ++k)
-    if (!std::isfinite(out5[k])) return -1;
-  return 0;
-}
-float sampler_step_eta_d(double a, double ap, double eta) {
-  double sigma, d;
-  eta_sigma_d(a, ap, eta, &sigma, &d);
-  return (float)d;
-}
 // SDE-DPM-Solver++(2M), s in [0, 1] (k-diffusion sample_dpmpp_2m_sde's eta): with h = lambda(a') - lambda(a) the direction term keeps
 // d = sqrt(1-a') e^(-s h) and sigma_n = sqrt(1-a') sqrt(-expm1(-2 s h)) goes to fresh noise, d^2 + sigma_n^2 = 1 - a'.  The limits are
-// taken here, never computed: s = 0 and h <= 0 (a' = a) give (sqrt(1-a'), 0) -- the floats of sampler_step_coefs --, a' = 1 gives (0, 0),
+// taken here, never computed: s = 0 and h <= 0 (a' = a) give (sqrt(1-a'), 0) -- the floats of rule 0 --, a' = 1 gives (0, 0),
 // a = 0 (h = +inf: the first trailing step of a zero-terminal-SNR table) gives (0, sqrt(1-a')).
 static void sde_sigma_d(double a, double ap, double s, double* sigma, double* d) {
   const double sbp = sqrt(1 - ap);
@@ -313,21 +297,6 @@ static void sde_sigma_d(double a, double ap, double s, double* sigma, double* d)
   if (!std::isfinite(h)) { *sigma = sbp; *d = 0.0; return; }
   *d = sbp * exp(-s * h);
   *sigma = sbp * sqrt(-expm1(-2 * s * h));
-}
-int sampler_step_coefs_sde(int prediction_type, double a, double ap, double s, float* out5) {
-  if (!(s >= 0 && s <= 1)) return -1;
-  double sigma, d;
-  sde_sigma_d(a, ap, s, &sigma, &d);
-  if (step_coefs_d(prediction_type, a, ap, d, out5)) return -1;
-  out5[4] = (float)sigma;
-  for (int k = 0; k < 5; ++k)
-    if (!std::isfinite(out5[k])) return -1;
-  return 0;
-}
-float sampler_step_sde_d(double a, double ap, double s) {
-  double sigma, d;
-  sde_sigma_d(a, ap, s, &sigma, &d);
-  return (float)d;
 }
 size_t sampler_step_scratch_floats(int B, int HW) { return (size_t)B * ((HW + STEP_THREADS - 1) / STEP_THREADS) * 8; }
 
@@ -345,10 +314,20 @@ static float coef_2m_s(int i, int n, double a_before, double a, double ap, doubl
   const double c = sqrt(ap) * -expm1(s > 0 ? -(1 + s) * h : -h) / (2 * r);
   return std::isfinite(c) && std::isfinite((float)c) ? (float)c : 0.f;
 }
-float sampler_step_coef_2m(int i, int n, double a_before, double a, double ap) { return coef_2m_s(i, n, a_before, a, ap, 0.0); }
-int sampler_step_coef_2m_sde(int i, int n, double a_before, double a, double ap, double s, float* out) {
-  if (!(s >= 0 && s <= 1)) return -1;
-  *out = coef_2m_s(i, n, a_before, a, ap, s);
+// the row of one step under one rule (kernels.h).  The order is part of the contract: the range of s, then (sigma, d) of the rule, then
+// the type and the singular steps inside step_coefs_d, and only then the first write to *out
+int sampler_step_row(const StepRule& r, int i, int n, double a_before, double a, double ap, StepRow* out) {
+  if (r.noise < 0 || r.noise > 2 || (r.noise && !(r.s >= 0 && r.s <= 1))) return -1;
+  double sigma = 0.0, d = sqrt(1 - ap);
+  if (r.noise == 1) eta_sigma_d(a, ap, r.s, &sigma, &d);
+  if (r.noise == 2) sde_sigma_d(a, ap, r.s, &sigma, &d);
+  if (step_coefs_d(r.prediction_type, a, ap, d, out->lin)) return -1;
+  out->d = (float)d; out->sigma = (float)sigma;
+  out->c2m = coef_2m_s(i, n, a_before, a, ap, r.noise == 2 ? r.s : 0.0);
+  // the deterministic rule does not look (a = 1e-80 gives an infinite row with 0): a schedule that refused it would be another schedule
+  if (r.noise)
+    for (const float v : {out->lin[0], out->lin[1], out->lin[2], out->lin[3], out->sigma})
+      if (!std::isfinite(v)) return -2;
   return 0;
 }
 
@@ -384,14 +363,11 @@ hipError_t launch_sampler_step(const StepParams& p, hipStream_t s) {
 hipError_t launch_sampler_step_units(const StepParams& p, const uint64_t* unit_ids, hipStream_t s) {
   if (p.sigma == 0.f || p.noise) return launch_sampler_step(p, s);
   if (!unit_ids) return hipErrorInvalidValue;
-  StepParams q = p;
-  for (int r0 = 0; r0 < p.B; r0 += DD_RNG_UNITS) {
-    q.rng_row0 = r0; q.rng_count = p.B - r0 < DD_RNG_UNITS ? p.B - r0 : DD_RNG_UNITS;
-    for (int k = 0; k < q.rng_count; ++k) { q.rng_ids.lo[k] = (unsigned)unit_ids[r0 + k]; q.rng_ids.hi[k] = (unsigned)(unit_ids[r0 + k] >> 32); }
-    const hipError_t e = launch_sampler_step(q, s);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_rng_unit_ranges(unit_ids, p.B, [&](const RngUnits& ids, int r0, int cnt) {
+    StepParams q = p;
+    q.rng_ids = ids; q.rng_row0 = r0; q.rng_count = cnt;
+    return launch_sampler_step(q, s);
+  });
 }
 
 hipError_t launch_sampler_step_bwd(const StepParams& p, const float* g_x0, const float* g_zprev, bf16_t* g_m2, float* g_z, hipStream_t s) {

@@ -303,13 +303,9 @@ class Engine:
         ac = np.ascontiguousarray(np.asarray(alphas_cumprod, dtype=np.float32))
         sp = DDSamplerParams(guidance_scale, gs, ls, rho, constraint_value, int(use_global), int(use_local), int(guidance_period),
                              PREDICTION_TYPES[prediction_type], float(guidance_rescale))
-        if sde_eta:
-            self._chk(self.L.dd_set_schedule_sde(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
-                                                 float(final_alpha_cumprod), C.byref(sp), SOLVERS[solver], float(eta), float(sde_eta)),
-                      "dd_set_schedule")
-        else:
-            self._chk(self.L.dd_set_schedule_e(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
-                                               float(final_alpha_cumprod), C.byref(sp), SOLVERS[solver], float(eta)), "dd_set_schedule")
+        self._chk(self.L.dd_set_schedule_sde(self._h, ts.ctypes.data_as(vp), len(ts), ac.ctypes.data_as(vp), len(ac),
+                                             float(final_alpha_cumprod), C.byref(sp), SOLVERS[solver], float(eta), float(sde_eta)),
+                  "dd_set_schedule")
         self._sde = bool(sde_eta)          # the schedule now set takes x0_prev and step_noise together
         self.n_steps = len(ts)
         self.timesteps = [int(t) for t in ts]
@@ -413,20 +409,20 @@ class Engine:
         only on a schedule set with sde_eta > 0."""
         z = self._f(z)
         h = self._f(x0_prev) if x0_prev is not None else None
+        nz = self._step_noise(z, h, step_noise, "denoise_step")
         zp, x0 = torch.empty_like(z), torch.empty_like(z)
-        if step_noise is not None:
-            nz = self._f(step_noise)
-            assert nz.numel() == z.numel()
-            if h is not None:
-                if not getattr(self, "_sde", False):
-                    raise ValueError("denoise_step: x0_prev (solver 'dpmsolver++') and step_noise (eta > 0) do not go together")
-                self._chk(self.L.dd_denoise_step_hn(self._h, _p(z), step_index, _p(h), _p(nz), _p(zp), _p(x0), z.shape[0], _stream()),
-                          "dd_denoise_step")
-                return zp, x0
-            self._chk(self.L.dd_denoise_step_n(self._h, _p(z), step_index, _p(nz), _p(zp), _p(x0), z.shape[0], _stream()), "dd_denoise_step")
-            return zp, x0
-        self._chk(self.L.dd_denoise_step_h(self._h, _p(z), step_index, _p(h), _p(zp), _p(x0), z.shape[0], _stream()), "dd_denoise_step")
+        self._chk(self.L.dd_denoise_step_hn(self._h, _p(z), step_index, _p(h), _p(nz), _p(zp), _p(x0), z.shape[0], _stream()), "dd_denoise_step")
         return zp, x0
+
+    def _step_noise(self, z, h, step_noise, who):
+        """The optional noise of a step-level call as a device tensor or None; with a history it needs a schedule set with sde_eta > 0."""
+        if step_noise is None:
+            return None
+        nz = self._f(step_noise)
+        assert nz.numel() == z.numel()
+        if h is not None and not getattr(self, "_sde", False):
+            raise ValueError("%s: x0_prev (solver 'dpmsolver++') and step_noise (eta > 0) do not go together" % who)
+        return nz
 
     def transform_guidance(self, z, targets, e, b, first_step_index, P):
         z, e, b = self._f(z), self._f(e).reshape(-1), self._f(b).reshape(-1)
@@ -444,22 +440,11 @@ class Engine:
         z = self._f(z)
         h = self._f(x0_prev) if x0_prev is not None else None
         tg = targets.to(self.device, torch.int32).contiguous()
+        nz = self._step_noise(z, h, step_noise, "direct_guidance")
         zn, x0, gz = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
         score = torch.zeros(1, device=self.device)
-        if step_noise is not None:
-            nz = self._f(step_noise)
-            assert nz.numel() == z.numel()
-            if h is not None:
-                if not getattr(self, "_sde", False):
-                    raise ValueError("direct_guidance: x0_prev (solver 'dpmsolver++') and step_noise (eta > 0) do not go together")
-                self._chk(self.L.dd_direct_guidance_hn(self._h, _p(z), _p(tg), step_index, _p(h), _p(nz), _p(zn), _p(x0), _p(score), _p(gz),
-                                                       z.shape[0], _stream()), "dd_direct_guidance")
-                return zn, x0, score, gz
-            self._chk(self.L.dd_direct_guidance_n(self._h, _p(z), _p(tg), step_index, _p(nz), _p(zn), _p(x0), _p(score), _p(gz), z.shape[0],
-                                                  _stream()), "dd_direct_guidance")
-            return zn, x0, score, gz
-        self._chk(self.L.dd_direct_guidance_h(self._h, _p(z), _p(tg), step_index, _p(h), _p(zn), _p(x0), _p(score), _p(gz), z.shape[0],
-                                              _stream()), "dd_direct_guidance")
+        self._chk(self.L.dd_direct_guidance_hn(self._h, _p(z), _p(tg), step_index, _p(h), _p(nz), _p(zn), _p(x0), _p(score), _p(gz),
+                                               z.shape[0], _stream()), "dd_direct_guidance")
         return zn, x0, score, gz
 
     def decode(self, z, denormalize=True):
