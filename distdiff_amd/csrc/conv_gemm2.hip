@@ -12,8 +12,8 @@
 //     unconditional and every counter scalar (see the notes at the loop: both matter to what the compiler emits).
 //   * Persistent: each workgroup walks a list of (tile, K-split) work items with the loader running ahead into the next item; items are
 //     dealt to XCDs in contiguous chunks (blocks b, b+8, ... share an L2) with n-tiles fastest.
-//   * Epilogue: paired output columns -> 16-byte residual loads / stores; a batched form (FE) for short items, the generic
-//     Epi::apply form for deep / split-K items (its instantiation has the faster K loop).
+//   * Epilogue: paired output columns -> 16-byte residual loads / stores; a batched form (FE), the generic Epi::apply form otherwise.
+//   * BigTile describes a tile (sizes, LDS layout) for kernel and launcher alike; run_big_form lists the (FE, FM, ST) instantiations.
 #include "common.h"
 #include "conv_dispatch.h"
 #include "conv_epilogue.h"
@@ -38,28 +38,39 @@ __device__ __forceinline__ void trace_stamp(int& n, int tag) {
 // ST: epilogue extras, each its own instantiation (the code of the plain kernels -- above all the register allocation of their K
 // loop -- stays exactly what it was without them): 1 = CF_STATS (GroupNorm partials), 2 = CF_ROWSTATS (LayerNorm row partials),
 // 3 = CF_LNFOLD (this GEMM consumes the raw input of a LayerNorm folded into its weights; c1 arrives through a second LDS ring).
-template <int WM, int WN, int TM, int TN, int NS, bool FE, int FM, int ST>
-__global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void conv_gemm_big_kernel(ConvGemmParams p) {
-  constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-  constexpr int NW = WM * WN;   // 8 waves (one workgroup per CU) or 4 waves (two workgroups per CU, <= 256 VGPRs each)
-  constexpr int NT = NW * 64;
-  constexpr int RPT = NW * 8;   // tile rows per full staging pass: NT threads x 16 B = RPT rows of 128 B
-  constexpr int AV = BM / RPT;  // A passes (all full)
-  constexpr int BV = (BN + RPT - 1) / RPT;          // W passes; the last one may be a half pass (32 rows, lanes 0-31 of every wave)
-  constexpr bool B_HALF = (BN % RPT) == RPT / 2;
+template <int WM, int WN, int TM, int TN, int NS, int ST>
+struct BigTile {   // the tile description: sizes, staging passes and the LDS layout, read by the kernel and by the launcher (launch_big)
+  static constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
+  static constexpr int NW = WM * WN;   // 8 waves (one workgroup per CU) or 4 waves (two workgroups per CU, <= 256 VGPRs each)
+  static constexpr int NT = NW * 64;
+  static constexpr int RPT = NW * 8;   // tile rows per full staging pass: NT threads x 16 B = RPT rows of 128 B
+  static constexpr int AV = BM / RPT;  // A passes (all full)
+  static constexpr int BV = (BN + RPT - 1) / RPT;   // W passes; the last one may be a half pass (32 rows, lanes 0-31 of every wave)
+  static constexpr bool B_HALF = (BN % RPT) == RPT / 2;
   static_assert((NW == 8 || NW == 4) && BM % RPT == 0 && (BN % RPT == 0 || B_HALF) && (NS == 2 || NS == 3), "bad tile");
-  constexpr int BUF_BYTES = (BM + BN) * 128;
-  constexpr int DMA_PER_STAGE = AV + BV;
+  static constexpr int BUF_BYTES = (BM + BN) * 128;
+  static constexpr int DMA_PER_STAGE = AV + BV;
+  static constexpr int TAPS_OFF = NS * BUF_BYTES;   // behind the NS stages: per-tap tables (<= 32 taps: packed (dy,dx) and byte offsets)
   // bias of the n-tile of an item: one 1 KB LDS-DMA piece issued when the loader reaches the item (a ring of three: the loader is
   // at most two items ahead of the epilogue), read from LDS by the batched epilogue -- a global load there costs an exposed L2 / HBM
   // latency per item (tools/conv_trace.py: 3 us of epilogue on a 5-step item, half of it the bias wait)
-  constexpr int BIAS_OFF = NS * BUF_BYTES + 256;
+  static constexpr int BIAS_OFF = TAPS_OFF + 256;
   // ST == 3: column sums of the LayerNorm-folded weights and the (mean, rstd) of the item's BM = 128 rows (1 KB each) arrive the same
   // way; two slots each: with K >= 192 (three K-steps per item, checked by the host) the two-stage loader reaches item w + 2 only
   // after the epilogue of item w has run
-  constexpr int C1_OFF = BIAS_OFF + 3 * 1024;
-  constexpr int LNS_OFF = C1_OFF + 2 * 1024;
+  static constexpr int C1_OFF = BIAS_OFF + 3 * 1024;
+  static constexpr int LNS_OFF = C1_OFF + 2 * 1024;
+  static constexpr int LDS_BYTES = ST == 3 ? LNS_OFF + 2 * 1024 : C1_OFF;
   static_assert(ST != 3 || (NS == 2 && BM == 128), "LayerNorm-fold form: two-stage 128-row tiles only");
+  static_assert(LDS_BYTES <= 163840, "LDS budget");
+};
+
+template <int WM, int WN, int TM, int TN, int NS, bool FE, int FM, int ST>
+__global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void conv_gemm_big_kernel(ConvGemmParams p) {
+  using T = BigTile<WM, WN, TM, TN, NS, ST>;
+  constexpr int BM = T::BM, BN = T::BN, NW = T::NW, NT = T::NT, RPT = T::RPT, AV = T::AV, BV = T::BV, BUF_BYTES = T::BUF_BYTES;
+  constexpr int DMA_PER_STAGE = T::DMA_PER_STAGE, BIAS_OFF = T::BIAS_OFF, C1_OFF = T::C1_OFF, LNS_OFF = T::LNS_OFF;
+  constexpr bool B_HALF = T::B_HALF;
   int l_slot2 = 0, c_slot2 = 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -103,10 +114,10 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void conv_gemm
   const int r0 = tid >> 3;                    // tile row of staging pass 0
   const int rh = wave * 4 + (lane >> 3);      // row inside a half pass (lanes 0-31 only)
   const int jh = ps ^ (rh & 7);
-  constexpr bool fast = FM == 1;   // the host picks FM == 1 exactly when Cin % 64 == 0, shift == 0 and ntaps <= 32 (run_big_fe)
+  constexpr bool fast = FM == 1;   // the host picks FM == 1 exactly when Cin % 64 == 0, shift == 0 and ntaps <= 32 (run_big_form)
   // the per-tap offset table lives in LDS: a global load inside the pipeline would force s_waitcnt vmcnt(0)
   // (vmcnt retires in order) and drain the in-flight DMA stages
-  int* taps = (int*)(smem + NS * BUF_BYTES);
+  int* taps = (int*)(smem + T::TAPS_OFF);
   // 1x1 / linear layers (one tap, same-size output: the packers give them the centre tap): no tap table at all -- its global load
   // is an HBM-latency wait plus three barriers in front of the first DMA of every workgroup, and these are the short kernels
   const bool pointwise = fast && p.ntaps == 1 && p.stride == 1 && p.H == p.Ho && p.W == p.Wo;
@@ -680,52 +691,40 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void conv_gemm
 #endif
 }
 
-template <int WM, int WN, int TM, int TN, int NS, bool FE, int FM, int ST>
-hipError_t run_big_fe3(const ConvGemmParams& p, hipStream_t stream) {
-  constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-  constexpr int lds = NS * (BM + BN) * 128 + 256 + (ST == 3 ? 7 : 3) * 1024;   // + per-tap tables (<= 32 taps: packed (dy,dx) and byte offsets), bias (+ c1) ring
-  static_assert(lds <= 163840, "LDS budget");
+template <int CFG, bool FE, int FM, int ST>
+hipError_t launch_big(const ConvGemmParams& p, hipStream_t stream) {
+  constexpr BigForm f = BIG_FORMS[CFG];
+  using T = BigTile<f.wm, f.wn, f.tm, f.tn, f.ns, ST>;
+  constexpr auto kernel = conv_gemm_big_kernel<f.wm, f.wn, f.tm, f.tn, f.ns, FE, FM, ST>;
   static bool attr = false;
-  if (!attr) { hipFuncSetAttribute((const void*)conv_gemm_big_kernel<WM, WN, TM, TN, NS, FE, FM, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
-  const int W = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.ksplit;
-  constexpr int WGS = 256 * ((WM * WN == 4) ? 2 : 1);   // persistent: one 8-wave or two 4-wave workgroups per CU
-  int G = W < WGS ? (W + 7) / 8 * 8 : WGS;
-  hipLaunchKernelGGL((conv_gemm_big_kernel<WM, WN, TM, TN, NS, FE, FM, ST>), dim3(G), dim3(WM * WN * 64), lds, stream, p);
+  if (!attr) { hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES); attr = true; }
+  const int W = ((p.M + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN) * p.ksplit;
+  constexpr int WGS = 256 * (T::NW == 4 ? 2 : 1);   // persistent: one 8-wave or two 4-wave workgroups per CU
+  hipLaunchKernelGGL(kernel, dim3(W < WGS ? (W + 7) / 8 * 8 : WGS), dim3(T::NT), T::LDS_BYTES, stream, p);
   return hipGetLastError();
 }
-template <int WM, int WN, int TM, int TN, int NS, bool FE, int FM>
-hipError_t run_big_fe2(const ConvGemmParams& p, hipStream_t stream) {
-  // the LayerNorm forms only exist for the batched epilogue of the two-workgroup (shallow-K, pointwise) tiles
-  if constexpr (WM * WN == 4 && FE && FM == 1) {
-    if ((p.flags & CF_LNFOLD) && p.K >= 192 && !(p.M & 1)) return run_big_fe3<WM, WN, TM, TN, NS, FE, FM, 3>(p, stream);
-    if (p.flags & CF_ROWSTATS) return run_big_fe3<WM, WN, TM, TN, NS, FE, FM, 2>(p, stream);
-  }
-  return (p.flags & CF_STATS) ? run_big_fe3<WM, WN, TM, TN, NS, FE, FM, 1>(p, stream) : run_big_fe3<WM, WN, TM, TN, NS, FE, FM, 0>(p, stream);
-}
-
-template <int WM, int WN, int TM, int TN, int NS, bool FE>
-hipError_t run_big_fe(const ConvGemmParams& p, hipStream_t stream) {
-  // the fast staging path addresses the input through 32-bit BYTE offsets of a buffer resource (plus the tap bias): inputs of
-  // 3.75 GB and more take the general path (32-bit ELEMENT offsets; launch_conv_gemm rejects inputs beyond those)
-  const size_t x_bytes = (size_t)p.B * p.H * p.W * (size_t)p.x_ld * 2;
-  const bool fast = (p.cin & 63) == 0 && p.shift == 0 && p.ntaps <= 32 && x_bytes < 0xF0000000ull;
-  return fast ? run_big_fe2<WM, WN, TM, TN, NS, FE, 1>(p, stream) : run_big_fe2<WM, WN, TM, TN, NS, FE, 0>(p, stream);
-}
-template <int WM, int WN, int TM, int TN, int NS>
-hipError_t run_big(const ConvGemmParams& p, hipStream_t stream) {
-  // Two instantiations per tile.  The batched epilogue (FE: bias from the LDS ring, all residual loads issued together, 16-byte
-  // stores) saves ~15 us per work item over the generic one; its instantiation used to run the K loop ~0.18 us per K-step slower
-  // (register allocation), which made the generic form the better one beyond ~100 K-steps per item.  With the bias staged through
-  // LDS the batched form wins at every depth (same-device tools/ab_ops.sh, 32-image batch: limit 60 -> 1975 ms of conv, 100 -> 1949,
-  // none -> 1936), so only split-K items (fp32 partial stores, no epilogue work) take the generic instantiation.
-  // split-K items only store fp32 partials (same code in both instantiations): take the faster loop
-  return p.ksplit == 1 ? run_big_fe<WM, WN, TM, TN, NS, true>(p, stream) : run_big_fe<WM, WN, TM, TN, NS, false>(p, stream);
-}
-
+// The one dispatcher of tile form CFG.  Instantiations: (FE, FM) x ST in {0, 1} (8); two-workgroup forms add (FE, fast) x ST in {2, 3}.
+//   FE  The batched epilogue (bias from the LDS ring, all residual loads issued together, 16-byte stores) saves ~15 us per work item over
+//       the generic one and, with the bias staged through LDS, wins at every depth (same-device tools/ab_ops.sh, 32-image batch: a limit
+//       of 60 K-steps -> 1975 ms of conv, 100 -> 1949, none -> 1936).  Only split-K items take the generic instantiation: they store
+//       fp32 partials (same code in both) and its K loop is ~0.18 us per K-step faster (register allocation).
+//   FM  The fast staging path addresses the input through 32-bit BYTE offsets of a buffer resource (plus the tap bias): inputs of
+//       3.75 GB and more take the general path (32-bit ELEMENT offsets; launch_conv_gemm rejects inputs beyond those).  The LayerNorm
+//       forms (ST 2, 3) only exist for the batched epilogue of the two-workgroup (shallow-K, pointwise) tiles on that path.
 template <int CFG>
 hipError_t run_big_form(const ConvGemmParams& p, hipStream_t stream) {
-  constexpr BigForm f = BIG_FORMS[CFG];
-  return run_big<f.wm, f.wn, f.tm, f.tn, f.ns>(p, stream);
+  const bool fe = p.ksplit == 1;
+  const size_t x_bytes = (size_t)p.B * p.H * p.W * (size_t)p.x_ld * 2;
+  const bool fast = (p.cin & 63) == 0 && p.shift == 0 && p.ntaps <= 32 && x_bytes < 0xF0000000ull;
+  const bool st = (p.flags & CF_STATS) != 0;
+  if constexpr (BIG_FORMS[CFG].wm * BIG_FORMS[CFG].wn == 4) {
+    if (fe && fast && (p.flags & CF_LNFOLD) && p.K >= 192 && !(p.M & 1)) return launch_big<CFG, true, 1, 3>(p, stream);
+    if (fe && fast && (p.flags & CF_ROWSTATS)) return launch_big<CFG, true, 1, 2>(p, stream);
+  }
+  if (fe) return fast ? (st ? launch_big<CFG, true, 1, 1>(p, stream) : launch_big<CFG, true, 1, 0>(p, stream))
+                      : (st ? launch_big<CFG, true, 0, 1>(p, stream) : launch_big<CFG, true, 0, 0>(p, stream));
+  return fast ? (st ? launch_big<CFG, false, 1, 1>(p, stream) : launch_big<CFG, false, 1, 0>(p, stream))
+              : (st ? launch_big<CFG, false, 0, 1>(p, stream) : launch_big<CFG, false, 0, 0>(p, stream));
 }
 
 }  // namespace
