@@ -135,6 +135,7 @@ OPS_SYMBOLS = [
     "dd_op_step_coef_2m", "dd_op_sampler_step_2m", "dd_op_step_coefs_eta", "dd_op_sampler_step_n",
     "dd_op_step_coefs_sde", "dd_op_step_coef_2m_sde", "dd_op_sampler_step_2m_n",
     "dd_debug_tensor", "dd_debug_num_tensors", "dd_debug_fusion_plan", "dd_debug_set_image", "dd_debug_set_images",
+    "dd_debug_plan_only", "dd_debug_plan_dump",
 ]
 ENGINE_SYMBOLS = [
     "dd_abi_version", "dd_act_dtype", "dd_create", "dd_destroy", "dd_last_error", "dd_load_tensor", "dd_finalize_weights", "dd_set_prototypes",

@@ -9,22 +9,20 @@
 #include "engine_internal.h"
 
 namespace {
-// ---------------------------------------------------------------------------------------------------
-// sampler drivers
-// ---------------------------------------------------------------------------------------------------
-struct Run {
-  dd_engine* E; hipStream_t s;
-  Ctx ctx(const Program& P, char* act) {
-    Ctx c; c.act = act; c.grad = E->grad_slab; c.tr = E->tr_slab; c.tr_stride = P.tr_max; c.scratch_partial = E->scratch_partial; c.partial_cap = E->partial_cap;
-    c.scratch_tmp = E->scratch_tmp; c.tmp_cap = E->tmp_cap; c.tap1x1 = E->tap1x1; c.gn_scratch = E->gn_scratch; c.rowpart = E->rowpart; c.s = s; c.cross_kv = &E->cross_kv; c.flops = &E->flops; c.prof = &E->prof;
-    return c;
-  }
-};
+// ---- sampler drivers ----
+// execution context of program P on the activation slab `act`; of prog[p] on its slab of instance k
+Ctx make_ctx(dd_engine* E, const Program& P, char* act, hipStream_t s) {
+  Ctx c; c.act = act; c.grad = E->grad_slab; c.tr = E->tr_slab; c.tr_stride = P.tr_max; c.scratch_partial = E->scratch_partial; c.partial_cap = E->partial_cap;
+  c.scratch_tmp = E->scratch_tmp; c.tmp_cap = E->tmp_cap; c.tap1x1 = E->tap1x1; c.gn_scratch = E->gn_scratch; c.rowpart = E->rowpart; c.s = s; c.cross_kv = &E->cross_kv; c.flops = &E->flops; c.prof = &E->prof;
+  return c;
+}
+Ctx make_ctx(dd_engine* E, int p, int k, hipStream_t s) { return make_ctx(E, E->prog[p], E->inst[k].act[p], s); }
 
-void check_batch(dd_engine* E, int B) {
+void check_batch(dd_engine* E, int B, bool need_grad = false) {
   if (B != E->cfg.max_batch) throw std::runtime_error("this engine was built for batch " + std::to_string(E->cfg.max_batch) +
                                                       " (static shapes); got B=" + std::to_string(B));
   if (!E->finalized) throw std::runtime_error("dd_finalize_weights has not been called");
+  if (need_grad && !E->cfg.enable_grad) throw std::runtime_error("engine created with enable_grad=0");
 }
 
 // Cotangent scale of the fp16 build (common.h: CotScale).  cot_normalise computes {s, 1 / s} from the fp32 cotangent(s) in front of a
@@ -45,8 +43,7 @@ inline const float* cot_inv(const float* cs) { return cs ? cs + 1 : nullptr; }
 // UNet forward on instance k: z fp32 NCHW -> eps2 fp32 NHWC [2B*HW, ld] inside the slab
 void unet_fwd(dd_engine* E, int k, const float* z, int step_index, hipStream_t s, bool stash = true) {
   const dd_config& c = E->cfg;
-  Run r{E, s};
-  Ctx ctx = r.ctx(E->unet, E->inst[k].unet);
+  Ctx ctx = make_ctx(E, dd_engine::UNET, k, s);
   ctx.step_index = step_index;
   ctx.stash = stash;
   if (c.unet_add_time_dim > 0) {
@@ -61,8 +58,7 @@ void unet_fwd(dd_engine* E, int k, const float* z, int step_index, hipStream_t s
 
 void vae_fwd(dd_engine* E, int k, const float* x0, hipStream_t s) {
   const dd_config& c = E->cfg;
-  Run r{E, s};
-  Ctx ctx = r.ctx(E->vae, E->inst[k].vae);
+  Ctx ctx = make_ctx(E, dd_engine::VAE, k, s);
   const Tn& in = E->vae.t[E->vae_in];
   HIPCHK(launch_nchw_f32_to_nhwc_bf16(x0, act_ptr(ctx, in), c.max_batch, c.vae_latent_channels, c.latent_size, c.latent_size, in.ld,
                                       in.ld, 0, 1.f / c.vae_scaling_factor, s));
@@ -95,9 +91,8 @@ const float* guide_features_grad_in(dd_engine* E, const Ctx& gc, const float* gf
 // guide forward from the decoded image of instance k (bicubic -> guide network -> features) -> feat [B, D]
 void guide_fwd_from_image(dd_engine* E, int k, hipStream_t s) {
   const dd_config& c = E->cfg;
-  Run r{E, s};
-  Ctx gc = r.ctx(E->guide, E->inst[k].guide);
-  Ctx vc = r.ctx(E->vae, E->inst[k].vae);
+  Ctx gc = make_ctx(E, dd_engine::GUIDE, k, s);
+  Ctx vc = make_ctx(E, dd_engine::VAE, k, s);
   const Tn& img = E->vae.t[E->vae_out];
   const Tn& gin = E->guide.t[E->guide_in];
   // the decoder's conv_out stores the image in fp32: image, bicubic resize and the whole guide stay fp32
@@ -114,12 +109,9 @@ void guide_fwd_from_image(dd_engine* E, int k, hipStream_t s) {
 // reverse of guide_fwd_from_image + vae_fwd: gfeat -> g_x0 (fp32 NCHW)
 void guide_vae_bwd(dd_engine* E, int k, float* g_x0, hipStream_t s) {
   const dd_config& c = E->cfg;
-  Run r{E, s};
-  Ctx gc = r.ctx(E->guide, E->inst[k].guide);
-  Ctx vc = r.ctx(E->vae, E->inst[k].vae);
-  const Tn& f = E->guide.t[E->guide_feat];
+  Ctx gc = make_ctx(E, dd_engine::GUIDE, k, s);
+  Ctx vc = make_ctx(E, dd_engine::VAE, k, s);
   // GAP^T; the ReLU mask of the last bottleneck is applied by that conv op's backward
-  (void)f;
   const float* gcs = guide_features_grad_in(E, gc, E->inst[k].gfeat, s);
   run_bwd(E->guide, gc);
   const Tn& gin = E->guide.t[E->guide_in];
@@ -140,7 +132,7 @@ StepParams step_params(dd_engine* E, int k, int step_index, const Schedule::Rows
   const dd_config& c = E->cfg;
   const Tn& out = E->unet.t[E->unet_out];
   StepParams p{};
-  p.m2 = (const float*)(E->inst[k].unet + out.off); p.ld = out.ld;
+  p.m2 = (const float*)(E->inst[k].act[dd_engine::UNET] + out.off); p.ld = out.ld;
   p.B = c.max_batch; p.C = c.unet_out_channels; p.HW = c.latent_size * c.latent_size;
   p.coef = rows.coef + (size_t)step_index * 8; p.lin = rows.lin + (size_t)step_index * 4;
   p.prediction_type = E->sp.prediction_type; p.phi = E->sp.guidance_rescale;
@@ -209,9 +201,8 @@ void guided_forward(dd_engine* E, int k, const float* z_in, int step_index, cons
 void guided_backward(dd_engine* E, int k, int step_index, float* g_znext, float* g_z_out, float* g_x0_tmp, hipStream_t s) {
   const dd_config& c = E->cfg;
   const int HW = c.latent_size * c.latent_size;
-  Run r{E, s};
   guide_vae_bwd(E, k, g_x0_tmp, s);
-  Ctx uc = r.ctx(E->unet, E->inst[k].unet);
+  Ctx uc = make_ctx(E, dd_engine::UNET, k, s);
   uc.step_index = step_index;
   // The UNet's reverse program is entered through the sampler step's VJP, which also writes the direct part of g_z: the fp16 build
   // scales both of its fp32 inputs, so that g_z_out carries the scale until the UNet's part has been added, and unscales it at the end
@@ -236,16 +227,14 @@ void set_config_defaults(dd_config& c) {
 
 }  // namespace
 
-// =====================================================================================================
-// C ABI
-// =====================================================================================================
-#define DD_TRY(E, ...)                                    \
-  try { __VA_ARGS__; return DD_OK; }                      \
-  catch (const std::exception& ex) { (E)->err = ex.what(); return DD_ERR_HIP; }
-// the same in the middle of a function: the code goes to rc, nothing returns
-#define DD_TRY_RC(E, rc, ...)                             \
-  try { __VA_ARGS__; rc = DD_OK; }                        \
+// ==== C ABI ====
+// The body of an entry point that launches or copies, its status to rc: an exception becomes DD_ERR_HIP with its message, and an engine
+// that only plans (dd_debug_plan_only) refuses with DD_ERR_STATE.  DD_TRY: the same as the rest of the function
+#define DD_TRY_RC(E, rc, ...)                                                                                                        \
+  if ((E)->plan_only) { (E)->err = "this engine only plans (dd_debug_plan_only): it owns no device memory"; rc = DD_ERR_STATE; }   \
+  else try { __VA_ARGS__; rc = DD_OK; }                                                                                            \
   catch (const std::exception& ex) { (E)->err = ex.what(); rc = DD_ERR_HIP; }
+#define DD_TRY(E, ...) { int _rc; DD_TRY_RC(E, _rc, __VA_ARGS__) return _rc; }
 
 extern "C" {
 
@@ -271,7 +260,7 @@ int dd_create(const dd_config* cfg, dd_engine** out) {
     return DD_ERR_ARG;
   }
 #endif
-  dd_engine* e = new dd_engine();
+  dd_engine* e = new dd_engine();      // reads the plan switches (PlanSwitches)
   e->cfg = *cfg;
   set_config_defaults(e->cfg);
   *out = e;
@@ -280,7 +269,7 @@ int dd_create(const dd_config* cfg, dd_engine** out) {
 
 void dd_destroy(dd_engine* e) {
   if (!e) return;
-  for (void* p : e->dev_allocs) hipFree(p);
+  if (!e->plan_only) for (void* p : e->dev_allocs) hipFree(p);
   delete e;
 }
 
@@ -345,7 +334,7 @@ int dd_finalize_weights(dd_engine* E) {
   if (E->finalized) { E->err = "already finalized"; return DD_ERR_STATE; }
   if (E->declared && E->declared != (int)E->raw.size()) { E->err = "dd_declare_tensor and dd_load_tensor cannot be mixed"; return DD_ERR_STATE; }
   E->shape_only = E->declared > 0;
-  DD_TRY(E, {
+  try {      // not DD_TRY: this is what an engine that only plans is for
     const dd_config& c = E->cfg;
     // the sampler step reads the UNet output as one 8-wide fp32 row per pixel (kernels.h: StepParams)
     if (c.unet_out_channels > 8) throw std::runtime_error("unet_out_channels " + std::to_string(c.unet_out_channels) + " > 8: the sampler step takes at most 8");
@@ -380,11 +369,8 @@ int dd_finalize_weights(dd_engine* E) {
     E->inst.resize(P);
     for (int k = 0; k < P; ++k) {
       auto& I = E->inst[k];
-      I.unet = (char*)E->dmalloc(E->unet.act_bytes);
-      if (k == 0 || c.enable_grad) {
-        I.vae = (char*)E->dmalloc(E->vae.act_bytes);
-        I.guide = (char*)E->dmalloc(E->guide.act_bytes);
-      }
+      for (int p = dd_engine::UNET; p <= dd_engine::GUIDE; ++p)
+        if (p == dd_engine::UNET || k == 0 || c.enable_grad) I.act[p] = (char*)E->dmalloc(E->prog[p].act_bytes);
       I.z_in = (float*)E->dmalloc(zbytes); I.z_next = (float*)E->dmalloc(zbytes); I.x0 = (float*)E->dmalloc(zbytes);
       I.feat = (float*)E->dmalloc((size_t)B * guide_feat_dim(c) * 4);
       I.gfeat = (float*)E->dmalloc((size_t)B * guide_feat_dim(c) * 4);
@@ -399,7 +385,14 @@ int dd_finalize_weights(dd_engine* E) {
       E->cot_scale = (float*)E->dmalloc(2 * 4);
     }
 #endif
-    E->tr_slab = (char*)E->dmalloc(2 * std::max({E->unet.tr_max, E->vae.tr_max, E->guide.tr_max, E->venc.tr_max, E->text.tr_max, E->text2.tr_max, (size_t)256}));
+    // what the programs share is sized for the largest of them
+    size_t tr_max = 256;
+    E->partial_cap = (size_t)1 << 20; E->tmp_cap = 256;
+    for (const Program& P : E->prog) {
+      tr_max = std::max(tr_max, P.tr_max); E->partial_cap = std::max(E->partial_cap, P.scratch_partial);
+      E->tmp_cap = std::max(E->tmp_cap, P.scratch_tmp);
+    }
+    E->tr_slab = (char*)E->dmalloc(2 * tr_max);
     if (c.enable_grad) {
       // UNet gradients alone; VAE and guide gradients live side by side (bicubic^T bridges them)
       const size_t g = std::max(E->unet.grad_bytes, E->vae.grad_bytes + E->guide.grad_bytes);
@@ -407,17 +400,15 @@ int dd_finalize_weights(dd_engine* E) {
       for (auto& t : E->guide.t) t.goff += E->vae.grad_bytes;
     }
     // encoder programs run before the loop: the image encoder borrows the decoder slab of instance 0 when it fits
-    if (have_venc) E->venc_slab = E->venc.act_bytes <= E->vae.act_bytes ? E->inst[0].vae : (char*)E->dmalloc(E->venc.act_bytes);
-    if (have_text) E->text_slab = (char*)E->dmalloc(E->text.act_bytes);
-    if (have_text2) E->text2_slab = (char*)E->dmalloc(E->text2.act_bytes);
-    E->partial_cap = std::max({E->unet.scratch_partial, E->vae.scratch_partial, E->guide.scratch_partial, E->venc.scratch_partial,
-                               E->text.scratch_partial, E->text2.scratch_partial, (size_t)1 << 20});
+    if (have_venc) E->venc_slab = E->venc.act_bytes <= E->vae.act_bytes ? E->inst[0].act[dd_engine::VAE] : (char*)E->dmalloc(E->venc.act_bytes);
+    const bool have_tower[2] = {have_text, have_text2};
+    for (int w = 0; w < 2; ++w)
+      if (have_tower[w]) E->tower[w].slab = (char*)E->dmalloc(E->prog[dd_engine::TEXT + w].act_bytes);
     E->scratch_partial = (char*)E->dmalloc(E->partial_cap, false);
-    E->tmp_cap = std::max({E->unet.scratch_tmp, E->vae.scratch_tmp, E->guide.scratch_tmp, E->venc.scratch_tmp, E->text.scratch_tmp, E->text2.scratch_tmp, (size_t)256});
     {
       const int tap = (32 << 6) | 32;
       E->tap1x1 = (int*)E->dmalloc(sizeof(int), false);
-      HIPCHK(hipMemcpy(E->tap1x1, &tap, sizeof(int), hipMemcpyHostToDevice));
+      if (!E->plan_only) HIPCHK(hipMemcpy(E->tap1x1, &tap, sizeof(int), hipMemcpyHostToDevice));
     }
     E->scratch_tmp = (char*)E->dmalloc(E->tmp_cap);
     const int maxG = std::max(c.unet_groups, c.vae_groups);
@@ -436,21 +427,21 @@ int dd_finalize_weights(dd_engine* E) {
       bf16_t* v = (bf16_t*)E->dmalloc((size_t)2 * B * c.text_len * sl.C * 2);
       E->cross_kv.push_back({k, v});
     }
-    HIPCHK(hipDeviceSynchronize());
+    if (!E->plan_only) HIPCHK(hipDeviceSynchronize());
     // the statistics fusions of every program, asked of the launcher's planner on the context its forward runs get
     {
-      Run r{E, nullptr};
-      Ctx uc = r.ctx(E->unet, E->inst[0].unet);
-      if (c.unet_add_time_dim > 0) uc.img_bias = 2 * c.max_batch;
-      resolve_fusions(E->unet, uc);
-      resolve_fusions(E->vae, r.ctx(E->vae, E->inst[0].vae));
-      resolve_fusions(E->guide, r.ctx(E->guide, E->inst[0].guide));
-      if (have_venc) resolve_fusions(E->venc, r.ctx(E->venc, E->venc_slab));
-      if (have_text) resolve_fusions(E->text, r.ctx(E->text, E->text_slab));
-      if (have_text2) resolve_fusions(E->text2, r.ctx(E->text2, E->text2_slab));
+      const auto& I = E->inst[0];
+      char* const slab[dd_engine::NPROG] = {I.act[0], I.act[1], I.act[2], E->venc_slab, E->tower[0].slab, E->tower[1].slab};
+      for (int p = 0; p < dd_engine::NPROG; ++p) {
+        if (E->prog[p].ops.empty()) continue;      // not built
+        Ctx pc = make_ctx(E, E->prog[p], slab[p], nullptr);
+        if (p == dd_engine::UNET && c.unet_add_time_dim > 0) pc.img_bias = 2 * c.max_batch;
+        resolve_fusions(E->prog[p], pc);
+      }
     }
     E->finalized = true;
-  });
+  } catch (const std::exception& ex) { E->err = ex.what(); return DD_ERR_HIP; }
+  return DD_OK;
 }
 
 int dd_set_schedule(dd_engine* E, const int* timesteps, int n, const float* alphas_cumprod, int num_train, float final_alpha,
@@ -591,12 +582,14 @@ int dd_set_prompt(dd_engine* E, const float* embeds, int B, void* stream) {
     HIPCHK(launch_nchw_f32_to_nhwc_bf16(embeds, E->ctx_bf16, rows, c.unet_cross_dim, 1, 1, ld, ld, 0, 1.f, s));
     for (size_t i = 0; i < E->cross_slots.size(); ++i) {
       auto& sl = E->cross_slots[i];
-      for (int which = 0; which < 2; ++which) {
-        ConvW* w = which ? sl.wv : sl.wk;
+      ConvW* const proj[2] = {sl.wk, sl.wv};
+      bf16_t* const kv[2] = {E->cross_kv[i].first, E->cross_kv[i].second};
+      for (int j = 0; j < 2; ++j) {
+        ConvW* w = proj[j];
         ConvGemmParams p; memset(&p, 0, sizeof p);
         p.alpha = 1.f; p.partial = (float*)E->scratch_partial;
         p.x = E->ctx_bf16; p.x_ld = ld; p.w = w->w_fwd; p.taptab = w->tap_fwd;
-        p.y = which ? E->cross_kv[i].second : E->cross_kv[i].first; p.y_ld = sl.C;
+        p.y = kv[j]; p.y_ld = sl.C;
         p.B = 1; p.H = rows; p.W = 1; p.Ho = rows; p.Wo = 1; p.stride = 1;
         p.cin = w->sf.cin; p.ntaps = w->sf.ntaps; p.M = rows; p.N = w->sf.N; p.K = w->sf.K;
         HIPCHK(launch_conv_gemm(p, E->partial_cap, s));
@@ -658,7 +651,7 @@ int dd_unet_forward(dd_engine* E, const float* z, int step_index, float* eps2_ou
     hipStream_t s = (hipStream_t)stream;
     unet_fwd(E, 0, z, step_index, s);
     const Tn& out = E->unet.t[E->unet_out];
-    HIPCHK(launch_nhwc_to_nchw_f32(E->inst[0].unet + out.off, 1, eps2_out, 2 * B, c.unet_out_channels, c.latent_size, c.latent_size, out.ld,
+    HIPCHK(launch_nhwc_to_nchw_f32(E->inst[0].act[dd_engine::UNET] + out.off, 1, eps2_out, 2 * B, c.unet_out_channels, c.latent_size, c.latent_size, out.ld,
                                    1.f, 0.f, 0, 0.f, 0.f, s));
   });
 }
@@ -713,7 +706,7 @@ int dd_decode(dd_engine* E, const float* z, float* image_out, int denormalize, i
     hipStream_t s = (hipStream_t)stream;
     vae_fwd(E, 0, z, s);
     const Tn& img = E->vae.t[E->vae_out];
-    HIPCHK(launch_nhwc_to_nchw_f32(E->inst[0].vae + img.off, 1, image_out, B, c.vae_out_channels, img.H, img.W, img.ld,
+    HIPCHK(launch_nhwc_to_nchw_f32(E->inst[0].act[dd_engine::VAE] + img.off, 1, image_out, B, c.vae_out_channels, img.H, img.W, img.ld,
                                    denormalize ? 0.5f : 1.f, denormalize ? 0.5f : 0.f, denormalize, 0.f, 1.f, s));
   });
 }
@@ -725,8 +718,7 @@ int dd_vae_encode(dd_engine* E, const float* images, const float* noise, float* 
     if (!E->venc_slab) throw std::runtime_error("no VAE encoder weights were loaded (vae/encoder.* keys)");
     const dd_config& c = E->cfg;
     hipStream_t s = (hipStream_t)stream;
-    Run r{E, s};
-    Ctx ctx = r.ctx(E->venc, E->venc_slab);
+    Ctx ctx = make_ctx(E, E->venc, E->venc_slab, s);
     ctx.stash = false;
     const Tn& in = E->venc.t[E->venc_in];
     HIPCHK(launch_nchw_f32_to_nhwc_bf16(images, act_ptr(ctx, in), B, c.vae_out_channels, in.H, in.W, in.ld, in.ld, 0, 1.f, s));
@@ -741,44 +733,39 @@ int dd_text_encode_tower(dd_engine* E, int which, const int* input_ids, float* h
   if (!E || !input_ids || (!hidden_out && !pooled_out) || which < 0 || which > 1) return DD_ERR_ARG;
   DD_TRY(E, {
     if (!E->finalized) throw std::runtime_error("dd_finalize_weights has not been called");
-    char* slab = which ? E->text2_slab : E->text_slab;
-    if (!slab) throw std::runtime_error(which ? "no second text tower was loaded (text2/text_model.* keys)" : "no text encoder weights were loaded (text/text_model.* keys)");
+    const dd_engine::TextTower& tw = E->tower[which];
+    const char* const missing[2] = {"no text encoder weights were loaded (text/text_model.* keys)", "no second text tower was loaded (text2/text_model.* keys)"};
+    if (!tw.slab) throw std::runtime_error(missing[which]);
     if (n < 1 || n > E->text_batch) throw std::runtime_error("dd_text_encode: n must be in [1, 2*max_batch]");
-    if (pooled_out && (!which || !E->text2_proj_w)) throw std::runtime_error("pooled text embeddings come from the second tower's text_projection (text2/text_projection.weight)");
+    if (pooled_out && (which != 1 || !tw.proj_w)) throw std::runtime_error("pooled text embeddings come from the second tower's text_projection (text2/text_projection.weight)");
     const dd_config& c = E->cfg;
     hipStream_t s = (hipStream_t)stream;
-    Program& P = which ? E->text2 : E->text;
-    const int T = c.text_len, Cc = which ? E->text2_hidden : E->text_hidden;
+    const Program& P = E->prog[dd_engine::TEXT + which];
+    const int T = c.text_len, Cc = tw.hidden;
     HIPCHK(hipMemsetAsync(E->text_ids, 0, (size_t)E->text_batch * T * 4, s));
     HIPCHK(hipMemcpyAsync(E->text_ids, input_ids, (size_t)n * T * 4, hipMemcpyDeviceToDevice, s));
-    Run r{E, s};
-    Ctx ctx = r.ctx(P, slab);
+    Ctx ctx = make_ctx(E, P, tw.slab, s);
     ctx.stash = false;
-    const Tn& in = P.t[which ? E->text2_in : E->text_in];
-    HIPCHK(launch_clip_embed(E->text_ids, which ? E->tok_emb2 : E->tok_emb, which ? E->pos_emb2 : E->pos_emb, act_ptr(ctx, in), in.ld, in.rows, T, Cc,
-                             which ? E->text2_vocab : E->text_vocab, s));
+    const Tn& in = P.t[tw.in];
+    HIPCHK(launch_clip_embed(E->text_ids, tw.tok_emb, tw.pos_emb, act_ptr(ctx, in), in.ld, in.rows, T, Cc, tw.vocab, s));
     run_fwd(P, ctx);
     if (hidden_out) {
-      const Tn& o = P.t[which ? E->text2_out : E->text_out];
+      const Tn& o = P.t[tw.out];
       HIPCHK(launch_rows_bf16_to_f32(act_ptr(ctx, o), o.ld, hidden_out, n * T, Cc, s));
     }
     if (pooled_out) {
-      const Tn& f = P.t[E->text2_final];
-      HIPCHK(launch_clip_pool_project(E->text_ids, act_ptr(ctx, f), f.ld, E->text2_proj_w, pooled_out, n, T, Cc, E->text2_proj, s));
+      const Tn& f = P.t[tw.fin];
+      HIPCHK(launch_clip_pool_project(E->text_ids, act_ptr(ctx, f), f.ld, tw.proj_w, pooled_out, n, T, Cc, tw.proj, s));
     }
   });
 }
 
 int dd_text_encode(dd_engine* E, const int* input_ids, float* embeds_out, int n, void* stream) {
   if (!E || !input_ids || !embeds_out) return DD_ERR_ARG;
-  if (E->text2_slab) { E->err = "this model has two text towers: use dd_text_encode_tower"; return DD_ERR_STATE; }
+  if (E->tower[1].slab) { E->err = "this model has two text towers: use dd_text_encode_tower"; return DD_ERR_STATE; }
   return dd_text_encode_tower(E, 0, input_ids, embeds_out, nullptr, n, stream);
 }
 
-int dd_guide_encode_pooled(dd_engine* E, const float* images, float* feats, int B, int use_max, void* stream);
-int dd_guide_encode(dd_engine* E, const float* images, float* feats, int B, void* stream) {
-  return dd_guide_encode_pooled(E, images, feats, B, 0, stream);
-}
 int dd_guide_encode_pooled(dd_engine* E, const float* images, float* feats, int B, int use_max, void* stream) {
   if (!E || !images || !feats) return DD_ERR_ARG;
   DD_TRY(E, {
@@ -786,8 +773,7 @@ int dd_guide_encode_pooled(dd_engine* E, const float* images, float* feats, int 
     if (use_max && E->cfg.guide_kind == 1) throw std::runtime_error("the ViT guide has no spatial pooling (encode_image = the projected class token)");
     const dd_config& c = E->cfg;
     hipStream_t s = (hipStream_t)stream;
-    Run r{E, s};
-    Ctx gc = r.ctx(E->guide, E->inst[0].guide);
+    Ctx gc = make_ctx(E, dd_engine::GUIDE, 0, s);
     const Tn& gin = E->guide.t[E->guide_in];
     HIPCHK(launch_nchw_to_nhwc_f32(images, act_f32(gc, gin), B, 3, gin.H, gin.W, gin.ld, gin.ld, s));
     run_fwd(E->guide, gc);
@@ -795,13 +781,16 @@ int dd_guide_encode_pooled(dd_engine* E, const float* images, float* feats, int 
   });
 }
 
+int dd_guide_encode(dd_engine* E, const float* images, float* feats, int B, void* stream) {
+  return dd_guide_encode_pooled(E, images, feats, B, 0, stream);
+}
+
 int dd_transform_guidance(dd_engine* E, const float* z, const int* targets, const float* ch_e, const float* ch_b, int first_step_index,
                           int P, float* z_out, float* score_out, float* grad_eb_out, int B, void* stream) {
   if (!E || !z || !targets || !ch_e || !ch_b || !z_out || P < 1) return DD_ERR_ARG;
   DD_TRY(E, {
-    check_batch(E, B);
+    check_batch(E, B, /*need_grad=*/true);
     const dd_config& c = E->cfg;
-    if (!c.enable_grad) throw std::runtime_error("engine created with enable_grad=0");
     if (P > (int)E->inst.size()) throw std::runtime_error("guidance period exceeds max_guidance_period");
     if (first_step_index < 0 || first_step_index + P > (int)E->timesteps.size()) throw std::runtime_error("guide steps out of range");
     if ((E->sp.use_global && !E->Pc) || (E->sp.use_local && !E->Pg)) throw std::runtime_error("prototypes not set");
@@ -864,9 +853,8 @@ static int direct_guidance_call(dd_engine* E, const float* z, const int* targets
   if (!E || !z || !targets || !z_next_out) return DD_ERR_ARG;
   if (history_refused(E, x0_prev) || noise_refused(E, sn.noise)) return DD_ERR_STATE;
   DD_TRY(E, {
-    check_batch(E, B);
+    check_batch(E, B, /*need_grad=*/true);
     const dd_config& c = E->cfg;
-    if (!c.enable_grad) throw std::runtime_error("engine created with enable_grad=0");
     if (step_index < 0 || step_index >= (int)E->timesteps.size()) throw std::runtime_error("step_index out of range");
     if ((E->sp.use_global && !E->Pc) || (E->sp.use_local && !E->Pg)) throw std::runtime_error("prototypes not set");
     hipStream_t s = (hipStream_t)stream;
@@ -1006,14 +994,12 @@ int dd_get_image_scores(dd_engine* E, float* scores_out, int B, void* stream) {
 int dd_unet_vjp(dd_engine* E, const float* z, int step_index, const float* g_eps2, float* g_z_out, int B, void* stream) {
   if (!E || !z || !g_eps2 || !g_z_out) return DD_ERR_ARG;
   DD_TRY(E, {
-    check_batch(E, B);
+    check_batch(E, B, /*need_grad=*/true);
     const dd_config& c = E->cfg;
-    if (!c.enable_grad) throw std::runtime_error("engine created with enable_grad=0");
     hipStream_t s = (hipStream_t)stream;
     const int HW = c.latent_size * c.latent_size;
     unet_fwd(E, 0, z, step_index, s);
-    Run r{E, s};
-    Ctx uc = r.ctx(E->unet, E->inst[0].unet);
+    Ctx uc = make_ctx(E, dd_engine::UNET, 0, s);
     uc.step_index = step_index;
     const Tn& out = E->unet.t[E->unet_out];
     const float* cs = cot_normalise(E, g_eps2, (size_t)2 * B * c.unet_out_channels, HW, HW, s);
@@ -1028,13 +1014,11 @@ int dd_unet_vjp(dd_engine* E, const float* z, int step_index, const float* g_eps
 int dd_decode_vjp(dd_engine* E, const float* z, const float* g_image, float* g_z_out, int B, void* stream) {
   if (!E || !z || !g_image || !g_z_out) return DD_ERR_ARG;
   DD_TRY(E, {
-    check_batch(E, B);
+    check_batch(E, B, /*need_grad=*/true);
     const dd_config& c = E->cfg;
-    if (!c.enable_grad) throw std::runtime_error("engine created with enable_grad=0");
     hipStream_t s = (hipStream_t)stream;
     vae_fwd(E, 0, z, s);
-    Run r{E, s};
-    Ctx vc = r.ctx(E->vae, E->inst[0].vae);
+    Ctx vc = make_ctx(E, dd_engine::VAE, 0, s);
     const Tn& img = E->vae.t[E->vae_out];
     const float* cs = cot_normalise(E, g_image, (size_t)B * c.vae_out_channels, img.H * img.W, img.H * img.W, s);
     HIPCHK(launch_nchw_f32_to_nhwc_bf16(g_image, grad_ptr(vc, img), B, c.vae_out_channels, img.H, img.W, img.ld, img.ld, 0, 1.f, s, cs));
@@ -1048,12 +1032,10 @@ int dd_decode_vjp(dd_engine* E, const float* z, const float* g_image, float* g_z
 int dd_guide_vjp(dd_engine* E, const float* images, const float* g_feats, float* g_images_out, int B, void* stream) {
   if (!E || !images || !g_feats || !g_images_out) return DD_ERR_ARG;
   DD_TRY(E, {
-    check_batch(E, B);
+    check_batch(E, B, /*need_grad=*/true);
     const dd_config& c = E->cfg;
-    if (!c.enable_grad) throw std::runtime_error("engine created with enable_grad=0");
     hipStream_t s = (hipStream_t)stream;
-    Run r{E, s};
-    Ctx gc = r.ctx(E->guide, E->inst[0].guide);
+    Ctx gc = make_ctx(E, dd_engine::GUIDE, 0, s);
     const Tn& gin = E->guide.t[E->guide_in];
     HIPCHK(launch_nchw_to_nhwc_f32(images, act_f32(gc, gin), B, 3, gin.H, gin.W, gin.ld, gin.ld, s));
     run_fwd(E->guide, gc);
@@ -1096,7 +1078,7 @@ int dd_debug_tensor(dd_engine* E, int prog_inst, int idx, int want_grad, float* 
   const int prog = prog_inst & 15, k = prog_inst >> 4;   // bits 4.. select the instance (chained guided step) of an activation
   if (!E || prog < 0 || prog > 2 || k < 0 || k >= (int)E->inst.size()) return DD_ERR_ARG;
   DD_TRY(E, {
-    Program& P = prog == 0 ? E->unet : prog == 1 ? E->vae : E->guide;
+    const Program& P = E->prog[prog];
     if (idx < 0) idx += (int)P.t.size();   // negative: from the end (-1 = the program's output tensor)
     if (idx < 0 || idx >= (int)P.t.size()) throw std::runtime_error("tensor index out of range");
     const Tn& t = P.t[idx];
@@ -1104,12 +1086,11 @@ int dd_debug_tensor(dd_engine* E, int prog_inst, int idx, int want_grad, float* 
     if (!host_out) return DD_OK;
     // the gradient slab is packed by liveness: after a run only the pinned ranges (program inputs / outputs, padded tensors) still hold
     // the tensor's own gradient -- an intermediate's range may have been reused by another tensor since
-    if (want_grad && t.grad && !(t.glo < 0 && t.ghi >= (int)P.ops.size()) && !getenv("DD_NO_GRAD_REUSE"))
+    if (want_grad && t.grad && !(t.glo < 0 && t.ghi >= (int)P.ops.size()) && !E->sw.no_grad_reuse)
       throw std::runtime_error("gradient of an intermediate tensor: its range of the liveness-packed slab is reused during the reverse run "
                                "(build the engine with DD_NO_GRAD_REUSE=1 to read it)");
     HIPCHK(hipDeviceSynchronize());
-    const dd_engine::Inst& I = E->inst[k];
-    char* slab = prog == 0 ? I.unet : prog == 1 ? I.vae : I.guide;
+    char* slab = E->inst[k].act[prog];
     if (!want_grad && !slab) throw std::runtime_error("this instance has no slab for that program");
     char* base = want_grad ? E->grad_slab + t.goff : t.transient ? E->tr_slab + (size_t)t.tr_slot * P.tr_max : slab + t.off;
     const size_t n = (size_t)t.rows * t.ld;
@@ -1134,7 +1115,7 @@ int dd_debug_set_image(dd_engine* E, const float* image) { return dd_debug_set_i
 int dd_debug_fusion_plan(dd_engine* E, int prog, int* out, int cap) {
   if (!E || prog < 0 || prog > 3 || (cap > 0 && !out)) return DD_ERR_ARG;
   if (!E->finalized) { E->err = "finalize first"; return DD_ERR_STATE; }
-  const Program& P = prog == 0 ? E->unet : prog == 1 ? E->vae : prog == 2 ? E->guide : E->venc;
+  const Program& P = E->prog[prog];
   for (int i = 0; i < (int)P.ops.size() && i < cap; ++i) {
     const Op& op = P.ops[i];
     out[4 * i] = op.kind;
@@ -1146,7 +1127,44 @@ int dd_debug_fusion_plan(dd_engine* E, int prog, int* out, int cap) {
 }
 int dd_debug_num_tensors(dd_engine* E, int prog) {
   if (!E || prog < 0 || prog > 2) return DD_ERR_ARG;
-  return (int)(prog == 0 ? E->unet : prog == 1 ? E->vae : E->guide).t.size();
+  return (int)E->prog[prog].t.size();
+}
+
+// ---- the plans as data (tests/test_engine_plans.py; field order: include/distdiff_hip_ops.h) ----
+int dd_debug_plan_only(dd_engine* E) {
+  if (!E) return DD_ERR_ARG;
+  if (E->finalized) { E->err = "dd_debug_plan_only after dd_finalize_weights"; return DD_ERR_STATE; }
+  E->plan_only = true;
+  return DD_OK;
+}
+int dd_debug_plan_dump(dd_engine* E, int prog, int64_t* out, int cap) {
+  if (!E || prog < 0 || prog > dd_engine::NPROG || (cap > 0 && !out)) return DD_ERR_ARG;
+  if (!E->finalized) { E->err = "finalize first"; return DD_ERR_STATE; }
+  int n = 0;
+  auto put = [&](auto... v) { ((n < cap ? (void)(out[n] = (int64_t)v) : (void)0, ++n), ...); };
+  if (prog == dd_engine::NPROG) {      // the engine record
+    put(E->total_bytes, E->partial_cap, E->tmp_cap, E->packed.size());
+    for (auto& p : E->packed) put(p.second);
+    return n;
+  }
+  const Program& P = E->prog[prog];
+  auto index_of = [](const auto& owned, const void* p) {
+    for (size_t i = 0; i < owned.size(); ++i) if (owned[i].get() == p) return (int)i;
+    return -1;
+  };
+  put(P.t.size(), P.ops.size(), P.act_bytes, P.grad_bytes, P.scratch_partial, P.scratch_tmp, P.scratch_rowpart, P.tr_max, P.tr_count);
+  for (const Tn& t : P.t) put(t.off, t.goff, t.parent, t.rows, t.C, t.ld, t.B, t.H, t.W, t.f32, t.grad, t.gf32, t.transient, t.tr_slot, t.glo, t.ghi);
+  for (const Op& o : P.ops) {
+    uint64_t h = 1469598103934665603ull;      // FNV-1a over the producer list
+    for (int pi : o.producers) h = (h ^ (uint64_t)(uint32_t)pi) * 1099511628211ull;
+    uint32_t eps; memcpy(&eps, &o.eps, 4);
+    int64_t flops; memcpy(&flops, &o.flops, 8);
+    put(o.kind, o.x, o.y, o.res, o.raw, o.q, o.k, o.v, o.x2, index_of(E->convs, o.cw), index_of(E->norms, o.nw), o.stride, o.up, o.relu, o.out_f32,
+        o.use_table, o.G, o.silu, eps, o.heads, o.D, o.Nq, o.Nk, o.cross_slot, o.causal, o.act_kind, o.pv_fp8, o.q_prescaled, o.patch, o.sel_stride,
+        o.stats_off, o.fused, o.x_acc, o.res_acc, o.x2_acc, o.res_alias, o.part, o.part_off, o.part_ld, o.producers.size(), h, o.gn_fused, o.ln_fold,
+        o.x_fwd, o.ln_stats_off, o.rowstat_from, o.rowstat_emit, o.rowstat_ld, o.row_spans, flops);
+  }
+  return n;
 }
 
 // output stage (generate_data.py:1227-1234): [B,3,H,W] fp32 in [0,1] -> uint8 HWC with torchvision.save_image's quantisation

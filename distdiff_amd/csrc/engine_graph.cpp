@@ -4,30 +4,33 @@
 
 namespace ddi {
 
-// ---------------------------------------------------------------------------------------------------
-// program builder helpers
-// ---------------------------------------------------------------------------------------------------
+// ---- program builder helpers ----
+// What Builder::conv takes beside input and weights.  up: the 2x nearest upsample in front of the conv is fused; res: tensor added in the
+// epilogue; relu: 1 ReLU, 2 ReLU6; out_f32: fp32 output rows; use_table: the bias is the per-timestep table (resnet conv1 + time_emb_proj)
+struct ConvOpt { int stride = 1, up = 0, res = -1, relu = 0, out_f32 = 0, use_table = 0; };
+
 struct Builder {
   dd_engine* E;
   Program& P;
   int full_batch = 0;      // UNet: 2B when the CFG halves share their prefix (the program starts on B images), else 0
   Builder(dd_engine* e, Program& p) : E(e), P(p) {}
+  int push(const Op& op) { P.ops.push_back(op); return op.y; }
 
-  // y = epilogue(conv(x)) ; returns y (allocated unless `y_into` >= 0)
-  int conv(int x, ConvW* w, int stride = 1, int up = 0, int res = -1, int relu = 0, int out_f32 = 0, int use_table = 0,
-           int y_into = -1, bool keep_raw = true) {
+  // y = epilogue(conv(x)) ; returns y
+  int conv(int x, ConvW* w, const ConvOpt& o = {}) {
+    const int stride = o.stride, up = o.up, out_f32 = o.out_f32;
     const Tn& tx = P.t[x];
     const int Hl = tx.H << up, Wl = tx.W << up;
     const int Ho = (Hl + 2 * w->pad + w->pad_br - w->KH) / stride + 1, Wo = (Wl + 2 * w->pad + w->pad_br - w->KW) / stride + 1;
     const int Cy = w->geglu ? w->Cout / 2 : w->Cout;
     // the output of a GEGLU projection only feeds ff.net.2 (its VJP reads the stashed pre-activations): transient
-    int y = y_into >= 0 ? y_into : (w->geglu && !out_f32) ? P.transient(tx.B, Ho, Wo, Cy) : P.tensor(tx.B, Ho, Wo, Cy, true, out_f32 != 0);
-    Op op; op.kind = OP_CONV; op.x = x; op.y = y; op.res = res; op.cw = w; op.stride = stride; op.up = up; op.relu = relu;
-    op.out_f32 = out_f32; op.use_table = use_table;
-    if (w->geglu && P.want_grad && keep_raw) op.raw = P.tensor(tx.B, Ho, Wo, w->Cout, false);
+    int y = (w->geglu && !out_f32) ? P.transient(tx.B, Ho, Wo, Cy) : P.tensor(tx.B, Ho, Wo, Cy, true, out_f32 != 0);
+    Op op; op.kind = OP_CONV; op.x = x; op.y = y; op.res = o.res; op.cw = w; op.stride = stride; op.up = up; op.relu = o.relu;
+    op.out_f32 = out_f32; op.use_table = o.use_table;
+    if (w->geglu && P.want_grad) op.raw = P.tensor(tx.B, Ho, Wo, w->Cout, false);
     const size_t M = (size_t)tx.B * Ho * Wo;
     op.flops = 2.0 * M * w->Cout * (w->Cin / w->groups) * w->KH * w->KW;
-    if (w->f32) { P.ops.push_back(op); return y; }   // fp32 kernel: no split-K, no scratch
+    if (w->f32) return push(op);   // fp32 kernel: no split-K, no scratch
     const int split = conv_gemm_pick_split((int)M, w->sf.N, w->sf.K);
     P.scratch_partial = std::max(P.scratch_partial, (size_t)split * M * w->sf.N * 4);
     if (P.want_grad) {
@@ -39,16 +42,14 @@ struct Builder {
       if (w->geglu) tmp += rup_sz(M * w->Cout * 2, 256);
       P.scratch_tmp = std::max(P.scratch_tmp, tmp);
     }
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   int gn(int x, NormW* w, int G, float eps, int silu) {
     const Tn& tx = P.t[x];
     int y = P.transient(tx.B, tx.H, tx.W, tx.C);      // consumed by the convolution that follows, never by a reverse program
     Op op; op.kind = OP_GN; op.x = x; op.y = y; op.nw = w; op.G = G; op.eps = eps; op.silu = silu;
     op.stats_off = P.fp32_block((size_t)tx.B * G * 2);
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   // The LayerNorm and the linear just built (the last two ops) become one: the linear's forward packing already holds gamma o W
   // (make_conv(..., ln)), it reads the LayerNorm's input with CF_LNFOLD and the LayerNorm op only produces (mean, rstd) -- taken from
@@ -60,7 +61,7 @@ struct Builder {
     Op& c = P.ops[ci]; Op& l = P.ops[li];
     c.ln_fold = true; c.x_fwd = l.x; c.ln_stats_off = l.stats_off;
     l.ln_fold = true;
-    if (li >= 1 && !getenv("DD_NO_LN_ROWSTATS")) {
+    if (li >= 1 && !E->sw.no_ln_rowstats) {
       Op& pr = P.ops[li - 1];
       const Tn& tx = P.t[l.x];
       if (pr.kind == OP_CONV && pr.y == l.x && !pr.cw->geglu && !pr.cw->f32 && !pr.out_f32 && !pr.relu && pr.cw->KH == 1 && pr.cw->KW == 1 &&
@@ -78,8 +79,7 @@ struct Builder {
     int y = keep ? P.tensor(tx.B, tx.H, tx.W, tx.C) : P.transient(tx.B, tx.H, tx.W, tx.C);
     Op op; op.kind = OP_LN; op.x = x; op.y = y; op.nw = w; op.eps = eps;
     op.stats_off = P.fp32_block((size_t)tx.rows * 2);
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   // self attention: q,k,v are views ; cross attention: k,v come from slot (constant, no grad)
   int attn(int q, int k, int v, int heads, int Nq, int Nk, int cross_slot, int causal = 0, int q_prescaled = 0) {
@@ -92,8 +92,7 @@ struct Builder {
     P.scratch_tmp = std::max(P.scratch_tmp, attention_scratch_bytes(tq.B, heads, Nq, Nk, op.D, causal != 0, cross_slot >= 0, P.want_grad));
     op.stats_off = P.fp32_block((size_t)tq.B * heads * Nq * 2);  // lse + delta
     op.flops = 4.0 * tq.B * heads * (double)Nq * Nk * op.D;
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   // torch.cat([a, b], dim=1) of the UNet's skip connections.  No copy: the output buffer is allocated here and BOTH operands are re-homed
   // into it as column views (row stride = Ca + Cb), so their producers -- convolutions running long before, on the down path, for the
@@ -104,12 +103,9 @@ struct Builder {
     Op op; op.kind = OP_CONCAT; op.x = a; op.x2 = b; op.y = y;
     auto movable = [&](int id) {
       const Tn& t = P.t[id];
-      if (t.parent != id || t.f32 || P.f32 || t.transient || (t.C & 7)) return false;
-      for (size_t k = 0; k < P.t.size(); ++k)
-        if ((int)k != id && P.t[k].parent == id) return false;     // it has views of its own (their offsets would go stale)
-      return true;
+      return t.parent == id && !t.f32 && !P.f32 && !t.transient && !(t.C & 7) && !P.has_views(id);     // views of its own: their offsets would go stale
     };
-    if (a != b && movable(a) && movable(b) && !getenv("DD_NO_CONCAT_FUSION")) {
+    if (a != b && movable(a) && movable(b) && !E->sw.no_concat_fusion) {
       const Tn ty = P.t[y];
       int c0 = 0;
       for (int id : {a, b}) {
@@ -119,15 +115,13 @@ struct Builder {
       }
       op.fused = true;
     }
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   int act(int x, int kind) {   // text encoder MLP (forward only), ViT guide MLP (with backward)
     const Tn& tx = P.t[x];
     int y = P.transient(tx.B, tx.H, tx.W, tx.C);
     Op op; op.kind = OP_ACT; op.x = x; op.y = y; op.act_kind = kind;
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   // ViT guide: image [B,S,S,3] fp32 -> patch rows [B*(S/p)^2, 3*p*p]
   int patchify(int x, int p) {
@@ -135,42 +129,37 @@ struct Builder {
     const int g = tx.H / p;
     int y = P.tensor(tx.B, g * g, 1, tx.C * p * p);
     Op op; op.kind = OP_PATCHIFY; op.x = x; op.y = y; op.patch = p;
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   // class token + positional embedding (nw->gamma = class_embedding [W], nw->beta = positional_embedding [(np+1)*W])
   int vit_embed(int x, NormW* emb) {
     const Tn& tx = P.t[x];
     int y = P.tensor(tx.B, tx.H + 1, 1, tx.C);
     Op op; op.kind = OP_VITEMBED; op.x = x; op.y = y; op.nw = emb;
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   // cat[x, x] along the batch: the point where the two classifier-free-guidance halves stop being identical (build_unet)
   int dup(int x) {
     const Tn& tx = P.t[x];
     int y = P.tensor(2 * tx.B, tx.H, tx.W, tx.C);
     Op op; op.kind = OP_DUP; op.x = x; op.y = y;
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   int select_first(int x) {     // the class token of every image
     const Tn& tx = P.t[x];
     int y = P.tensor(tx.B, 1, 1, tx.C);
     Op op; op.kind = OP_SELECT; op.x = x; op.y = y; op.sel_stride = tx.H * tx.W;
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
   int maxpool(int x) {
     const Tn& tx = P.t[x];
     int y = P.tensor(tx.B, tx.H / 2, tx.W / 2, tx.C);
     Op op; op.kind = OP_MAXPOOL; op.x = x; op.y = y;
-    P.ops.push_back(op);
-    return y;
+    return push(op);
   }
 };
 
-void plan_grad_memory(Program& P);
+static void plan_grad_memory(Program& P);
 // decide, for every op input, whether its gradient contribution is the first write (assign) or an accumulation
 void plan_backward(Program& P) {
   std::vector<int> state(P.t.size(), 0);       // per parent: 0 none, 1 partial (views), 2 full
@@ -201,19 +190,13 @@ void plan_backward(Program& P) {
           // accumulate into it) instead of being copied.
           Tn& r = P.t[op.res]; const Tn& y = P.t[op.y];
           if (!op.res_acc && r.grad && r.parent == op.res && y.parent == op.y && r.ld == y.ld && r.C == y.C && r.rows == y.rows &&
-              !getenv("DD_NO_GRAD_ALIAS")) {
-            bool has_views = false;
-            for (size_t k = 0; k < P.t.size(); ++k)
-              if ((int)k != op.res && P.t[k].parent == op.res) has_views = true;
-            if (!has_views) { r.goff = y.goff; op.res_alias = true; }
+              !P.sw->no_grad_alias && !P.has_views(op.res)) {
+            r.goff = y.goff; op.res_alias = true;
           }
         }
         op.x_acc = mark(op.x);
         break;
-      case OP_GN: case OP_LN: case OP_MAXPOOL:
-        op.x_acc = mark(op.x);
-        break;
-      case OP_ACT: case OP_PATCHIFY: case OP_VITEMBED: case OP_SELECT: case OP_DUP:
+      case OP_GN: case OP_LN: case OP_MAXPOOL: case OP_ACT: case OP_PATCHIFY: case OP_VITEMBED: case OP_SELECT: case OP_DUP:
         op.x_acc = mark(op.x);
         break;
       case OP_ATTN:
@@ -245,8 +228,8 @@ void plan_backward(Program& P) {
 // and tensors with padding columns (which some kernels never write and others read: they must stay zero) keep a range of their own.
 // 32 images of the bench workload: the gradient slab shrinks from 65.9 GB to 13.2 GB (UNet 38.7 -> 1.9, VAE decoder 64.4 -> 13.0, guide 1.47 ->
 // 0.22 GB); results are bit-identical (tests/test_engine_gpu.py::test_gradient_slab_by_liveness_is_bitwise_identical).
-void plan_grad_memory(Program& P) {
-  if (!P.want_grad || getenv("DD_NO_GRAD_REUSE")) return;
+static void plan_grad_memory(Program& P) {
+  if (!P.want_grad || P.sw->no_grad_reuse) return;
   const int nt = (int)P.t.size(), nops = (int)P.ops.size();
   std::vector<int> cls(nt);
   for (int i = 0; i < nt; ++i) cls[i] = P.t[i].parent;                 // views -> their base (one level by construction)
@@ -266,7 +249,7 @@ void plan_grad_memory(Program& P) {
   for (int i = 0; i < nops; ++i) {
     const Op& op = P.ops[i];
     if (op.y >= 0) { has_prod[op.y] = 1; touch(op.y, i); }
-    for (int id : {op.x, op.res, op.q, op.k, op.v, op.x2})
+    for (int id : op.operands())
       if (id >= 0) { touch(id, i); has_cons[id] = 1; }
   }
   for (int i = 0; i < nt; ++i) {
@@ -323,10 +306,11 @@ void plan_grad_memory(Program& P) {
 
 // Transient tensors (Tn::transient) share two ping-pong buffers: legal only if every reader of one runs before the next tensor that
 // takes the same buffer is produced, and no reverse program reads it.  Checked once per program at build time.
-void check_transients(const Program& P) {
+static void check_transients(const Program& P) {
   auto reads = [&](const Op& o, int id) {
-    auto is = [&](int t) { return t >= 0 && (t == id || P.t[t].parent == id); };
-    return is(o.x) || is(o.res) || is(o.q) || is(o.k) || is(o.v) || is(o.x2);
+    for (int t : o.operands())
+      if (t >= 0 && (t == id || P.t[t].parent == id)) return true;
+    return false;
   };
   for (size_t id = 0; id < P.t.size(); ++id) {
     if (!P.t[id].transient) continue;
@@ -343,8 +327,7 @@ void check_transients(const Program& P) {
       if (!reads(o, (int)id)) continue;
       if ((int)oi <= prod || (int)oi > next_same_slot) throw std::runtime_error("transient tensor is read after its buffer was reused");
       // activations a reverse program reads must be stashed, not transient
-      const bool bwd_reads = (o.kind == OP_GN || o.kind == OP_LN || o.kind == OP_MAXPOOL || o.kind == OP_ACT || o.kind == OP_ATTN) ||
-                             (o.kind == OP_CONV && o.res == (int)id && false);
+      const bool bwd_reads = o.kind == OP_GN || o.kind == OP_LN || o.kind == OP_MAXPOOL || o.kind == OP_ACT || o.kind == OP_ATTN;
       if (P.want_grad && bwd_reads) throw std::runtime_error("transient tensor is an input a reverse program reads");
     }
     if (P.want_grad)
@@ -358,9 +341,8 @@ void check_transients(const Program& P) {
 // partial (mean, M2) from their epilogue registers and the GroupNorm merges them.  Whether a convolution can do that depends on the
 // kernel the launcher picks for its shape (conv_gemm_can_emit_stats), which needs the engine's scratch sizes: this pass only sets up
 // the buffers and the producer lists (the candidates), resolve_fusions takes the decision once at finalize.
-void plan_gn_stats(Program& P) {
-  check_transients(P);
-  if (P.f32 || getenv("DD_NO_GN_FUSION")) return;
+static void plan_gn_stats(Program& P) {
+  if (P.f32 || P.sw->no_gn_fusion) return;
   std::unordered_map<int, size_t> root_part;
   for (size_t gi = 0; gi < P.ops.size(); ++gi) {
     if (P.ops[gi].kind != OP_GN) continue;
@@ -395,10 +377,19 @@ void plan_gn_stats(Program& P) {
   }
 }
 
+// every builder ends here, in this order: the transient check, the backward plan (programs with a reverse run), the statistics candidates
+static void finish_program(Program& P) {
+  check_transients(P);
+  if (P.want_grad) plan_backward(P);
+  plan_gn_stats(P);
+}
 
-// ---------------------------------------------------------------------------------------------------
-// model builders (topology: SURVEY.md section 8a rows A2, A4, A7)
-// ---------------------------------------------------------------------------------------------------
+// ---- model builders (topology: SURVEY.md section 8a rows A2, A4, A7) ----
+static std::string name(const char* fmt, int i, int j = 0) {      // a state-dict key with one or two indices
+  char buf[128];
+  snprintf(buf, sizeof buf, fmt, i, j);
+  return buf;
+}
 int build_resnet(Builder& b, const std::string& model, const std::string& p, int x, int G, float eps, bool temb) {
   dd_engine* E = b.E;
   NormW* n1 = make_norm(E, model, p + ".norm1");
@@ -414,11 +405,11 @@ int build_resnet(Builder& b, const std::string& model, const std::string& p, int
     E->temb_convs.push_back(c1);
   }
   int h = b.gn(x, n1, G, eps, 1);
-  h = b.conv(h, c1, 1, 0, -1, 0, 0, temb ? 1 : 0);
+  h = b.conv(h, c1, {.use_table = temb ? 1 : 0});
   h = b.gn(h, n2, G, eps, 1);
   int sc = x;
   if (E->has(model, p + ".conv_shortcut.weight")) sc = b.conv(x, make_conv(E, model, p + ".conv_shortcut", 0));
-  return b.conv(h, c2, 1, 0, sc);
+  return b.conv(h, c2, {.res = sc});
 }
 
 // diffusers Transformer2DModel: GroupNorm -> proj_in -> `depth` BasicTransformerBlocks -> proj_out + residual.  proj_in / proj_out are
@@ -430,13 +421,11 @@ int build_transformer(Builder& b, const std::string& p, int x, int heads, int G,
   const int C = P.t[x].C, HW = P.t[x].H * P.t[x].W;
   int h = b.gn(x, make_norm(E, m, p + ".norm"), G, 1e-6f, 0);
   h = b.conv(h, make_conv(E, m, p + ".proj_in", 0));
-  char tb[32];
   for (int d = 0; d < depth; ++d) {
-    snprintf(tb, sizeof tb, ".transformer_blocks.%d", d);
-    const std::string t = p + tb;
+    const std::string t = p + name(".transformer_blocks.%d", d);
     // self attention (fused QKV projection, no bias)
     // the three LayerNorms of a block are folded into the linear each of them feeds (Builder::fold_ln; DD_NO_LN_FOLD=1 builds the plain graph)
-    const bool fold = ln_fold_enabled();
+    const bool fold = ln_fold_enabled(E);
     // the softmax scale 1/sqrt(d) * log2(e) lives in the to_q rows: the attention forward exponentiates the MFMA results as they are
     const float qscale = 1.4426950408889634f / sqrtf((float)(C / heads));
     int n = b.ln(h, make_norm(E, m, t + ".norm1"), 1e-5f);
@@ -447,7 +436,7 @@ int build_transformer(Builder& b, const std::string& p, int x, int heads, int G,
     const int fp8 = E->cfg.unet_attn_fp8 && C / heads == 64;      // BASELINE configs[4]: fp8 P.V for the d = 64 heads (SDXL)
     int a = b.attn(q, k, v, heads, HW, HW, -1, 0, 1);
     P.ops.back().pv_fp8 = fp8;
-    h = b.conv(a, make_conv(E, m, t + ".attn1.to_out.0", 0), 1, 0, h);
+    h = b.conv(a, make_conv(E, m, t + ".attn1.to_out.0", 0), {.res = h});
     // cross attention: K,V of the text embeddings are computed once per prompt (dd_set_prompt)
     n = b.ln(h, make_norm(E, m, t + ".norm2"), 1e-5f);
     int q2 = b.conv(n, make_conv(E, m, t + ".attn2.to_q", 0, false, false, fold ? t + ".norm2" : "", C, qscale));
@@ -466,14 +455,27 @@ int build_transformer(Builder& b, const std::string& p, int x, int heads, int G,
     E->cross_slots.push_back(slot);
     a = b.attn(q2, -1, -1, heads, HW, E->cfg.text_len, (int)E->cross_slots.size() - 1, 0, 1);
     P.ops.back().pv_fp8 = fp8;
-    h = b.conv(a, make_conv(E, m, t + ".attn2.to_out.0", 0), 1, 0, h);
+    h = b.conv(a, make_conv(E, m, t + ".attn2.to_out.0", 0), {.res = h});
     // GEGLU feed-forward
     n = b.ln(h, make_norm(E, m, t + ".norm3"), 1e-5f);
     int ff = b.conv(n, make_conv(E, m, t + ".ff.net.0.proj", 0, true, true, fold ? t + ".norm3" : ""));
     if (fold) b.fold_ln();
-    h = b.conv(ff, make_conv(E, m, t + ".ff.net.2", 0), 1, 0, h);
+    h = b.conv(ff, make_conv(E, m, t + ".ff.net.2", 0), {.res = h});
   }
-  return b.conv(h, make_conv(E, m, p + ".proj_out", 0), 1, 0, x);
+  return b.conv(h, make_conv(E, m, p + ".proj_out", 0), {.res = x});
+}
+
+// the single-head attention of the AutoencoderKL mid block (decoder and encoder): GroupNorm -> fused QKV -> attention -> to_out + h
+static int build_vae_attention(Builder& b, const std::string& a, int h, int G, float eps) {
+  dd_engine* E = b.E;
+  Program& P = b.P;
+  const std::string m = "vae";
+  const int C = P.t[h].C, HW = P.t[h].H * P.t[h].W;
+  int n = b.gn(h, make_norm(E, m, a + ".group_norm"), G, eps, 0);
+  int qkv = b.conv(n, make_conv_cat(E, m, {a + ".to_q", a + ".to_k", a + ".to_v"}, true));
+  int q = P.view(qkv, 0, C), k = P.view(qkv, C, C), v = P.view(qkv, 2 * C, C);
+  int o = b.attn(q, k, v, 1, HW, HW, -1);
+  return b.conv(o, make_conv(E, m, a + ".to_out.0", 0), {.res = h});
 }
 
 void build_unet(dd_engine* E) {
@@ -489,22 +491,19 @@ void build_unet(dd_engine* E) {
   // classifier-free guidance runs the UNet on cat[z, z] (generate_data.py:110-112): until the first cross-attention the two halves are
   // bit-for-bit the same computation, so the program starts on B images and duplicates at that point (build_transformer).  Not with
   // SDXL's text_time conditioning, whose time embedding already differs per half.
-  const bool share = c.unet_add_time_dim == 0 && !getenv("DD_NO_CFG_SHARE");
+  const bool share = c.unet_add_time_dim == 0 && !E->sw.no_cfg_share;
   b.full_batch = share ? B2 : 0;
   E->unet_in = P.tensor(share ? c.max_batch : B2, L, L, c.unet_in_channels);
   int h = b.conv(E->unet_in, make_conv(E, m, "conv_in", 1));
   std::vector<int> skips{h};
-  char buf[128];
   for (int i = 0; i < nl; ++i) {
     for (int j = 0; j < c.unet_layers_per_block; ++j) {
-      snprintf(buf, sizeof buf, "down_blocks.%d.resnets.%d", i, j);
-      h = build_resnet(b, m, buf, h, G, eps, true);
-      if (c.unet_down_attn[i]) { snprintf(buf, sizeof buf, "down_blocks.%d.attentions.%d", i, j); h = build_transformer(b, buf, h, heads_of(i), G, depth_of(i)); }
+      h = build_resnet(b, m, name("down_blocks.%d.resnets.%d", i, j), h, G, eps, true);
+      if (c.unet_down_attn[i]) { h = build_transformer(b, name("down_blocks.%d.attentions.%d", i, j), h, heads_of(i), G, depth_of(i)); }
       skips.push_back(h);
     }
     if (i < nl - 1) {
-      snprintf(buf, sizeof buf, "down_blocks.%d.downsamplers.0.conv", i);
-      h = b.conv(h, make_conv(E, m, buf, 1), 2);
+      h = b.conv(h, make_conv(E, m, name("down_blocks.%d.downsamplers.0.conv", i), 1), {.stride = 2});
       skips.push_back(h);
     }
   }
@@ -516,20 +515,17 @@ void build_unet(dd_engine* E) {
       int sk = skips.back(); skips.pop_back();
       if (P.t[sk].B != P.t[h].B) sk = b.dup(sk);      // a skip from the shared CFG prefix
       h = b.concat(h, sk);
-      snprintf(buf, sizeof buf, "up_blocks.%d.resnets.%d", i, j);
-      h = build_resnet(b, m, buf, h, G, eps, true);
-      if (c.unet_up_attn[i]) { snprintf(buf, sizeof buf, "up_blocks.%d.attentions.%d", i, j); h = build_transformer(b, buf, h, heads_of(nl - 1 - i), G, depth_of(nl - 1 - i)); }
+      h = build_resnet(b, m, name("up_blocks.%d.resnets.%d", i, j), h, G, eps, true);
+      if (c.unet_up_attn[i]) { h = build_transformer(b, name("up_blocks.%d.attentions.%d", i, j), h, heads_of(nl - 1 - i), G, depth_of(nl - 1 - i)); }
     }
     if (i < nl - 1) {
-      snprintf(buf, sizeof buf, "up_blocks.%d.upsamplers.0.conv", i);
-      h = b.conv(h, make_conv(E, m, buf, 1), 1, 1);
+      h = b.conv(h, make_conv(E, m, name("up_blocks.%d.upsamplers.0.conv", i), 1), {.up = 1});
     }
   }
   if (P.t[h].B != B2) throw std::runtime_error("UNet without any cross-attention: the CFG halves never part");
   h = b.gn(h, make_norm(E, m, "conv_norm_out"), G, eps, 1);
-  E->unet_out = b.conv(h, make_conv(E, m, "conv_out", 1), 1, 0, -1, 0, 1);
-  if (P.want_grad) plan_backward(P);
-  plan_gn_stats(P);
+  E->unet_out = b.conv(h, make_conv(E, m, "conv_out", 1), {.out_f32 = 1});
+  finish_program(P);
 }
 
 void build_vae(dd_engine* E) {
@@ -544,32 +540,20 @@ void build_vae(dd_engine* E) {
   int h = b.conv(E->vae_in, make_conv(E, m, "post_quant_conv", 0));
   h = b.conv(h, make_conv(E, m, "decoder.conv_in", 1));
   h = build_resnet(b, m, "decoder.mid_block.resnets.0", h, G, eps, false);
-  {
-    const std::string a = "decoder.mid_block.attentions.0";
-    const int C = P.t[h].C, HW = P.t[h].H * P.t[h].W;
-    int n = b.gn(h, make_norm(E, m, a + ".group_norm"), G, eps, 0);
-    int qkv = b.conv(n, make_conv_cat(E, m, {a + ".to_q", a + ".to_k", a + ".to_v"}, true));
-    int q = P.view(qkv, 0, C), k = P.view(qkv, C, C), v = P.view(qkv, 2 * C, C);
-    int o = b.attn(q, k, v, 1, HW, HW, -1);
-    h = b.conv(o, make_conv(E, m, a + ".to_out.0", 0), 1, 0, h);
-  }
+  h = build_vae_attention(b, "decoder.mid_block.attentions.0", h, G, eps);
   h = build_resnet(b, m, "decoder.mid_block.resnets.1", h, G, eps, false);
-  char buf[128];
   for (int i = 0; i < nl; ++i) {
     for (int j = 0; j < c.vae_layers_per_block + 1; ++j) {
-      snprintf(buf, sizeof buf, "decoder.up_blocks.%d.resnets.%d", i, j);
-      h = build_resnet(b, m, buf, h, G, eps, false);
+      h = build_resnet(b, m, name("decoder.up_blocks.%d.resnets.%d", i, j), h, G, eps, false);
     }
     if (i < nl - 1) {
-      snprintf(buf, sizeof buf, "decoder.up_blocks.%d.upsamplers.0.conv", i);
-      h = b.conv(h, make_conv(E, m, buf, 1), 1, 1);
+      h = b.conv(h, make_conv(E, m, name("decoder.up_blocks.%d.upsamplers.0.conv", i), 1), {.up = 1});
     }
   }
   h = b.gn(h, make_norm(E, m, "decoder.conv_norm_out"), G, eps, 1);
   // the image leaves the decoder in fp32 (no bf16 rounding in front of the guide's ReLU masks or the uint8 quantisation)
-  E->vae_out = b.conv(h, make_conv(E, m, "decoder.conv_out", 1), 1, 0, -1, 0, /*out_f32=*/1);
-  if (P.want_grad) plan_backward(P);
-  plan_gn_stats(P);
+  E->vae_out = b.conv(h, make_conv(E, m, "decoder.conv_out", 1), {.out_f32 = 1});
+  finish_program(P);
 }
 
 // f-2: AutoencoderKL.encode (dataloader.py:808) -- Encoder: conv_in, DownEncoderBlock2D x levels (resnets +
@@ -585,47 +569,40 @@ void build_vae_encoder(dd_engine* E) {
   const std::string m = "vae";
   E->venc_in = P.tensor(B, S, S, c.vae_out_channels);
   int h = b.conv(E->venc_in, make_conv(E, m, "encoder.conv_in", 1));
-  char buf[128];
   for (int i = 0; i < nl; ++i) {
     for (int j = 0; j < c.vae_layers_per_block; ++j) {
-      snprintf(buf, sizeof buf, "encoder.down_blocks.%d.resnets.%d", i, j);
-      h = build_resnet(b, m, buf, h, G, eps, false);
+      h = build_resnet(b, m, name("encoder.down_blocks.%d.resnets.%d", i, j), h, G, eps, false);
     }
     if (i < nl - 1) {
-      snprintf(buf, sizeof buf, "encoder.down_blocks.%d.downsamplers.0.conv", i);
-      ConvW* w = make_conv(E, m, buf, 0);
+      ConvW* w = make_conv(E, m, name("encoder.down_blocks.%d.downsamplers.0.conv", i), 0);
       w->pad_br = 1;
-      h = b.conv(h, w, 2);
+      h = b.conv(h, w, {.stride = 2});
     }
   }
   h = build_resnet(b, m, "encoder.mid_block.resnets.0", h, G, eps, false);
-  {
-    const std::string a = "encoder.mid_block.attentions.0";
-    const int C = P.t[h].C, HW = P.t[h].H * P.t[h].W;
-    int n = b.gn(h, make_norm(E, m, a + ".group_norm"), G, eps, 0);
-    int qkv = b.conv(n, make_conv_cat(E, m, {a + ".to_q", a + ".to_k", a + ".to_v"}, true));
-    int q = P.view(qkv, 0, C), k = P.view(qkv, C, C), v = P.view(qkv, 2 * C, C);
-    int o = b.attn(q, k, v, 1, HW, HW, -1);
-    h = b.conv(o, make_conv(E, m, a + ".to_out.0", 0), 1, 0, h);
-  }
+  h = build_vae_attention(b, "encoder.mid_block.attentions.0", h, G, eps);
   h = build_resnet(b, m, "encoder.mid_block.resnets.1", h, G, eps, false);
   h = b.gn(h, make_norm(E, m, "encoder.conv_norm_out"), G, eps, 1);
   h = b.conv(h, make_conv(E, m, "encoder.conv_out", 1));
-  E->venc_out = b.conv(h, make_conv(E, m, "quant_conv", 0), 1, 0, -1, 0, /*out_f32=*/1);
-  plan_gn_stats(P);
+  E->venc_out = b.conv(h, make_conv(E, m, "quant_conv", 0), {.out_f32 = 1});
+  finish_program(P);
 }
 
 // f-2: CLIPTextModel (transformers; dataloader.py:633-646 `text_encoder(input_ids)[0]`): token + position embeddings, pre-LN
 // transformer layers with causal self-attention and a quick_gelu (or erf-GELU) MLP, final LayerNorm.  Forward only.
-// which = 1: the second tower of an SDXL-style model ("text2", CLIPTextModelWithProjection).  text_hidden_layer = -2: the program output
+// w = 1: the second tower of an SDXL-style model ("text2", CLIPTextModelWithProjection).  text_hidden_layer = -2: the program output
 // is hidden_states[-2] (the input of the last layer, no final LayerNorm) as StableDiffusionXLPipeline.encode_prompt reads both towers;
 // the second tower also keeps final_layer_norm(last layer) for its pooled head (dd_text_encode_tower).
-void build_text_encoder(dd_engine* E, int which) {
+void build_text_encoder(dd_engine* E, int w) {
   const dd_config& c = E->cfg;
-  Program& P = which ? E->text2 : E->text;
+  Program& P = E->prog[dd_engine::TEXT + w];
+  dd_engine::TextTower& tw = E->tower[w];
   P.want_grad = false;
   Builder b(E, P);
-  const std::string m = which ? "text2" : "text", tm = "text_model.";
+  // what dd_config says per tower
+  const int cfg_heads[2] = {c.text_heads > 0 ? c.text_heads : 12, c.text2_heads > 0 ? c.text2_heads : 20}, cfg_act[2] = {c.text_act, c.text2_act};
+  const float cfg_eps[2] = {c.text_eps, c.text2_eps};
+  const std::string models[2] = {"text", "text2"}, m = models[w], tm = "text_model.";
   const HostTensor& tok = E->get(m, tm + "embeddings.token_embedding.weight");
   const HostTensor& pos = E->get(m, tm + "embeddings.position_embedding.weight");
   const int vocab = (int)tok.shape[0], C = (int)tok.shape[1];
@@ -633,55 +610,45 @@ void build_text_encoder(dd_engine* E, int which) {
   const bool two = E->has("text2", tm + "embeddings.token_embedding.weight");
   if (!two && C != c.unet_cross_dim) throw std::runtime_error("text encoder width != UNet cross_attention_dim");
   if (c.text_hidden_layer != 0 && c.text_hidden_layer != -2) throw std::runtime_error("text_hidden_layer must be 0 (last_hidden_state) or -2");
-  const int heads = which ? (c.text2_heads > 0 ? c.text2_heads : 20) : (c.text_heads > 0 ? c.text_heads : 12);
-  if (C % heads) throw std::runtime_error("text hidden size is not divisible by its head count");
-  float* te = (float*)E->wupload(tok.data.data(), tok.numel() * 4);
-  float* pe = (float*)E->wupload(pos.data.data(), pos.numel() * 4);
+  if (C % cfg_heads[w]) throw std::runtime_error("text hidden size is not divisible by its head count");
+  tw.tok_emb = (float*)E->wupload(tok.data.data(), tok.numel() * 4);
+  tw.pos_emb = (float*)E->wupload(pos.data.data(), pos.numel() * 4);
   const int Bt = 2 * c.max_batch, T = c.text_len;
-  const float eps0 = which ? c.text2_eps : c.text_eps, eps = eps0 > 0.f ? eps0 : 1e-5f;
-  const int act = which ? c.text2_act : c.text_act;
+  const float eps = cfg_eps[w] > 0.f ? cfg_eps[w] : 1e-5f;
   if (!E->text_ids) { E->text_batch = Bt; E->text_ids = (int*)E->dmalloc((size_t)Bt * T * 4); }
   int x = P.tensor(Bt, T, 1, C);
-  const int in = x;
+  tw.in = x; tw.vocab = vocab; tw.hidden = C;
   int layers = 0;
-  char buf[160];
   for (;; ++layers) {
-    snprintf(buf, sizeof buf, "%sencoder.layers.%d.layer_norm1.weight", tm.c_str(), layers);
-    if (!E->has(m, buf)) break;
+    if (!E->has(m, tm + name("encoder.layers.%d.layer_norm1.weight", layers))) break;
   }
   if (layers < 2 && c.text_hidden_layer == -2) throw std::runtime_error("text_hidden_layer = -2 needs at least two layers");
   int penultimate = -1;
   for (int l = 0; l < layers; ++l) {
     if (l == layers - 1) penultimate = x;
-    snprintf(buf, sizeof buf, "%sencoder.layers.%d", tm.c_str(), l);
-    const std::string p = buf;
+    const std::string p = tm + name("encoder.layers.%d", l);
     int h = b.ln(x, make_norm(E, m, p + ".layer_norm1"), eps);
     int qkv = b.conv(h, make_conv_cat(E, m, {p + ".self_attn.q_proj", p + ".self_attn.k_proj", p + ".self_attn.v_proj"}, true));
     int q = P.view(qkv, 0, C), k = P.view(qkv, C, C), v = P.view(qkv, 2 * C, C);
-    int o = b.attn(q, k, v, heads, T, T, -1, /*causal=*/1);
-    x = b.conv(o, make_conv(E, m, p + ".self_attn.out_proj", 0), 1, 0, x);
+    int o = b.attn(q, k, v, cfg_heads[w], T, T, -1, /*causal=*/1);
+    x = b.conv(o, make_conv(E, m, p + ".self_attn.out_proj", 0), {.res = x});
     h = b.ln(x, make_norm(E, m, p + ".layer_norm2"), eps);
     h = b.conv(h, make_conv(E, m, p + ".mlp.fc1", 0));
-    h = b.act(h, act);
-    x = b.conv(h, make_conv(E, m, p + ".mlp.fc2", 0), 1, 0, x);
+    h = b.act(h, cfg_act[w]);
+    x = b.conv(h, make_conv(E, m, p + ".mlp.fc2", 0), {.res = x});
   }
-  const int fin = b.ln(x, make_norm(E, m, tm + "final_layer_norm"), eps, /*keep=*/true);
-  const int out = c.text_hidden_layer == -2 ? penultimate : fin;
-  if (which) {
-    E->text2_in = in; E->text2_out = out; E->text2_final = fin;
-    E->tok_emb2 = te; E->pos_emb2 = pe; E->text2_vocab = vocab; E->text2_hidden = C;
+  tw.fin = b.ln(x, make_norm(E, m, tm + "final_layer_norm"), eps, /*keep=*/true);
+  tw.out = c.text_hidden_layer == -2 ? penultimate : tw.fin;
+  if (w == 1) {      // the pooled head
     if (E->has(m, "text_projection.weight")) {
       const HostTensor& pw = E->get(m, "text_projection.weight");
       if ((int)pw.shape[1] != C) throw std::runtime_error("text2 text_projection width != hidden size");
-      E->text2_proj = (int)pw.shape[0];
-      E->text2_proj_w = (float*)E->wupload(pw.data.data(), pw.numel() * 4);
+      tw.proj = (int)pw.shape[0];
+      tw.proj_w = (float*)E->wupload(pw.data.data(), pw.numel() * 4);
     }
-    if (E->text_hidden + C != c.unet_cross_dim) throw std::runtime_error("text + text2 widths != UNet cross_attention_dim");
-  } else {
-    E->text_in = in; E->text_out = out;
-    E->tok_emb = te; E->pos_emb = pe; E->text_vocab = vocab; E->text_hidden = C;
+    if (E->tower[0].hidden + C != c.unet_cross_dim) throw std::runtime_error("text + text2 widths != UNet cross_attention_dim");
   }
-  check_transients(P);
+  finish_program(P);
 }
 
 void build_guide(dd_engine* E) {
@@ -696,24 +663,21 @@ void build_guide(dd_engine* E) {
   E->guide_in = P.tensor(B, S, S, 3);
   // timm ResNet family (model_utils.py:47-79): widths, groups (ResNeXt) and the bottleneck width (Wide-ResNet) come from the
   // weight shapes of the state dict
-  int h = b.conv(E->guide_in, make_conv_bn(E, m, "conv1", "bn1", 3, eps, 3), 2, 0, -1, 1);
+  int h = b.conv(E->guide_in, make_conv_bn(E, m, "conv1", "bn1", 3, eps, 3), {.stride = 2, .relu = 1});
   h = b.maxpool(h);
-  char buf[128];
   for (int li = 0; li < c.guide_stages; ++li)
     for (int bi = 0; bi < c.guide_blocks[li]; ++bi) {
       const int stride = (bi == 0 && li > 0) ? 2 : 1;
-      snprintf(buf, sizeof buf, "layer%d.%d", li + 1, bi);
-      const std::string p = buf;
-      int o = b.conv(h, make_conv_bn(E, m, p + ".conv1", p + ".bn1", 0, eps, P.t[h].C), 1, 0, -1, 1);
-      o = b.conv(o, make_conv_bn(E, m, p + ".conv2", p + ".bn2", 1, eps, P.t[o].C), stride, 0, -1, 1);
+      const std::string p = name("layer%d.%d", li + 1, bi);
+      int o = b.conv(h, make_conv_bn(E, m, p + ".conv1", p + ".bn1", 0, eps, P.t[h].C), {.relu = 1});
+      o = b.conv(o, make_conv_bn(E, m, p + ".conv2", p + ".bn2", 1, eps, P.t[o].C), {.stride = stride, .relu = 1});
       int sc = h;
       if (E->has(m, p + ".downsample.0.weight"))
-        sc = b.conv(h, make_conv_bn(E, m, p + ".downsample.0", p + ".downsample.1", 0, eps, P.t[h].C), stride);
-      h = b.conv(o, make_conv_bn(E, m, p + ".conv3", p + ".bn3", 0, eps, P.t[o].C), 1, 0, sc, 1);
+        sc = b.conv(h, make_conv_bn(E, m, p + ".downsample.0", p + ".downsample.1", 0, eps, P.t[h].C), {.stride = stride});
+      h = b.conv(o, make_conv_bn(E, m, p + ".conv3", p + ".bn3", 0, eps, P.t[o].C), {.res = sc, .relu = 1});
     }
   E->guide_feat = h;
-  if (P.want_grad) plan_backward(P);
-  plan_gn_stats(P);
+  finish_program(P);
 }
 
 // timm mobilenetv2_100 (model_utils.py:64-71) forward_features: conv_stem/bn1/ReLU6 -> blocks (stage 0: DepthwiseSeparableConv = conv_dw, bn1,
@@ -730,33 +694,30 @@ void build_guide_mbv2(dd_engine* E) {
   const int B = c.max_batch, S = c.guide_input_size;
   const float eps = c.guide_bn_eps;
   E->guide_in = P.tensor(B, S, S, 3);
-  int h = b.conv(E->guide_in, make_conv_bn(E, m, "conv_stem", "bn1", 1, eps, 3), 2, 0, -1, /*relu6=*/2);
-  char buf[128];
+  int h = b.conv(E->guide_in, make_conv_bn(E, m, "conv_stem", "bn1", 1, eps, 3), {.stride = 2, .relu = 2});
   for (int s = 0; s < c.guide_stages; ++s)
     for (int bi = 0; bi < c.guide_blocks[s]; ++bi) {
       const int stride = bi == 0 ? c.guide_strides[s] : 1;
-      snprintf(buf, sizeof buf, "blocks.%d.%d", s, bi);
-      const std::string p = buf;
+      const std::string p = name("blocks.%d.%d", s, bi);
       const int x = h;
       int o;
       if (E->has(m, p + ".conv_pwl.weight")) {
-        o = b.conv(x, make_conv_bn(E, m, p + ".conv_pw", p + ".bn1", 0, eps, P.t[x].C), 1, 0, -1, 2);
-        o = b.conv(o, make_conv_bn(E, m, p + ".conv_dw", p + ".bn2", 1, eps, P.t[o].C), stride, 0, -1, 2);
+        o = b.conv(x, make_conv_bn(E, m, p + ".conv_pw", p + ".bn1", 0, eps, P.t[x].C), {.relu = 2});
+        o = b.conv(o, make_conv_bn(E, m, p + ".conv_dw", p + ".bn2", 1, eps, P.t[o].C), {.stride = stride, .relu = 2});
         const HostTensor& wl = E->get(m, p + ".conv_pwl.weight");
         const bool skip = stride == 1 && (int)wl.shape[0] == P.t[x].C;
-        h = b.conv(o, make_conv_bn(E, m, p + ".conv_pwl", p + ".bn3", 0, eps, P.t[o].C), 1, 0, skip ? x : -1, 0);
+        h = b.conv(o, make_conv_bn(E, m, p + ".conv_pwl", p + ".bn3", 0, eps, P.t[o].C), {.res = skip ? x : -1});
       } else {
-        o = b.conv(x, make_conv_bn(E, m, p + ".conv_dw", p + ".bn1", 1, eps, P.t[x].C), stride, 0, -1, 2);
+        o = b.conv(x, make_conv_bn(E, m, p + ".conv_dw", p + ".bn1", 1, eps, P.t[x].C), {.stride = stride, .relu = 2});
         const HostTensor& wp = E->get(m, p + ".conv_pw.weight");
         const bool skip = stride == 1 && (int)wp.shape[0] == P.t[x].C;
-        h = b.conv(o, make_conv_bn(E, m, p + ".conv_pw", p + ".bn2", 0, eps, P.t[o].C), 1, 0, skip ? x : -1, 0);
+        h = b.conv(o, make_conv_bn(E, m, p + ".conv_pw", p + ".bn2", 0, eps, P.t[o].C), {.res = skip ? x : -1});
       }
     }
-  h = b.conv(h, make_conv_bn(E, m, "conv_head", "bn2", 0, eps, P.t[h].C), 1, 0, -1, 2);
+  h = b.conv(h, make_conv_bn(E, m, "conv_head", "bn2", 0, eps, P.t[h].C), {.relu = 2});
   E->guide_feat = h;
-  if (P.t[h].C != guide_feat_dim_decl(c)) throw std::runtime_error("mobilenetv2 guide: conv_head width != guide_feature_dim");
-  if (P.want_grad) plan_backward(P);
-  plan_gn_stats(P);
+  if (P.t[h].C != guide_feat_dim(c)) throw std::runtime_error("mobilenetv2 guide: conv_head width != guide_feature_dim");
+  finish_program(P);
 }
 
 // open_clip VisionTransformer (the image tower behind `image_encoder.encode_image` when --arch open_clip_vit_b32, the reference's default
@@ -794,11 +755,9 @@ void build_guide_vit(dd_engine* E) {
   }
   const float eps = 1e-5f;
   int x = b.ln(h, make_norm(E, m, v + "ln_pre"), eps, /*keep=*/true);   // the residual stream
-  char buf[160];
   const int N = np + 1;
   for (int l = 0;; ++l) {
-    snprintf(buf, sizeof buf, "%stransformer.resblocks.%d", v.c_str(), l);
-    const std::string r = buf;
+    const std::string r = v + name("transformer.resblocks.%d", l);
     if (!E->has(m, r + ".ln_1.weight")) break;
     int n = b.ln(x, make_norm(E, m, r + ".ln_1"), eps);
     const HostTensor& iw = E->get(m, r + ".attn.in_proj_weight");
@@ -806,11 +765,11 @@ void build_guide_vit(dd_engine* E) {
     int qkv = b.conv(n, make_conv_raw(E, iw.data.data(), ib.data.data(), true, 3 * W, W, 1, 1, 0, false, c.enable_grad != 0));
     int q = P.view(qkv, 0, W), k = P.view(qkv, W, W), vv = P.view(qkv, 2 * W, W);
     int a = b.attn(q, k, vv, heads, N, N, -1);
-    x = b.conv(a, make_conv(E, m, r + ".attn.out_proj", 0), 1, 0, x);
+    x = b.conv(a, make_conv(E, m, r + ".attn.out_proj", 0), {.res = x});
     n = b.ln(x, make_norm(E, m, r + ".ln_2"), eps);
     int f = b.conv(n, make_conv(E, m, r + ".mlp.c_fc", 0));
     f = b.act(f, c.guide_vit_act);
-    x = b.conv(f, make_conv(E, m, r + ".mlp.c_proj", 0), 1, 0, x);
+    x = b.conv(f, make_conv(E, m, r + ".mlp.c_proj", 0), {.res = x});
   }
   int cls = b.select_first(x);
   cls = b.ln(cls, make_norm(E, m, v + "ln_post"), eps);
@@ -823,10 +782,9 @@ void build_guide_vit(dd_engine* E) {
     for (int d = 0; d < D; ++d)
       for (int k = 0; k < W; ++k) pt[(size_t)d * W + k] = pr.data[(size_t)k * D + d];
   }
-  E->guide_feat = b.conv(cls, make_conv_raw(E, pt.data(), nullptr, false, D, W, 1, 1, 0, false, c.enable_grad != 0), 1, 0, -1, 0, /*out_f32=*/1);
+  E->guide_feat = b.conv(cls, make_conv_raw(E, pt.data(), nullptr, false, D, W, 1, 1, 0, false, c.enable_grad != 0), {.out_f32 = 1});
   if (D != c.guide_feature_dim) throw std::runtime_error("ViT guide: projection dim != guide_feature_dim");
-  if (P.want_grad) plan_backward(P);
-  plan_gn_stats(P);
+  finish_program(P);
 }
 
 

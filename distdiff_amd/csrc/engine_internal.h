@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <array>
 #include <functional>
 #include <memory>
 #include <string>
@@ -40,17 +41,18 @@ struct HostTensor {
   size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
 };
 
-template <class T>
-T* dev_upload(const std::vector<T>& h) {
-  T* d = nullptr;
-  HIPCHK(hipMalloc((void**)&d, std::max<size_t>(h.size() * sizeof(T), 16)));
-  if (!h.empty()) HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return d;
-}
+// The plan switches (DD_NO_<NAME>=1 plans without that step: same-binary A/B), read once per engine in dd_create: an engine is planned,
+// run and inspected as it was built, whatever the environment says later
+struct PlanSwitches {
+  bool no_ln_fold, no_ln_rowstats, no_gn_fusion, no_concat_fusion, no_grad_alias, no_transient, no_cfg_share, no_grad_reuse;
+  static PlanSwitches from_env() {
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    return {on("DD_NO_LN_FOLD"), on("DD_NO_LN_ROWSTATS"), on("DD_NO_GN_FUSION"), on("DD_NO_CONCAT_FUSION"), on("DD_NO_GRAD_ALIAS"),
+            on("DD_NO_TRANSIENT"), on("DD_NO_CFG_SHARE"), on("DD_NO_GRAD_REUSE")};
+  }
+};
 
-// ---------------------------------------------------------------------------------------------------
-// weights
-// ---------------------------------------------------------------------------------------------------
+// ---- weights ----
 struct ConvW {
   int Cout = 0, Cin = 0, KH = 1, KW = 1, pad = 0;
   int pad_br = 0;              // extra zero rows/cols at the bottom/right only (AutoencoderKL encoder downsample: F.pad (0,1,0,1))
@@ -70,9 +72,7 @@ struct ConvW {
 };
 struct NormW { float* gamma = nullptr; float* beta = nullptr; int C = 0; };
 
-// ---------------------------------------------------------------------------------------------------
-// op graph
-// ---------------------------------------------------------------------------------------------------
+// ---- op graph ----
 struct Tn {              // activation tensor or channel view
   size_t off = 0;        // byte offset in the activation slab
   size_t goff = 0;       // byte offset in the gradient slab
@@ -126,6 +126,8 @@ struct Op {
   int rowstat_from = -1; bool rowstat_emit = false; int rowstat_ld = 0;
   int row_spans = 0;
   double flops = 0;
+  // the tensors the op reads, in the one order operands are listed in (-1: none)
+  std::array<int, 6> operands() const { return {x, res, q, k, v, x2}; }
 };
 
 struct Program {   // built and planned once (engine_graph.cpp, resolve_fusions); run_fwd / run_bwd only read it, every instance slab shares it
@@ -138,8 +140,9 @@ struct Program {   // built and planned once (engine_graph.cpp, resolve_fusions)
   size_t scratch_rowpart = 0;          // bytes of the shared row-partial buffer (producer GEMM -> LayerNorm statistics, adjacent ops)
   size_t tr_max = 0;     // bytes of one transient ping-pong buffer
   int tr_count = 0;
+  const PlanSwitches* sw = nullptr;    // the engine's
   int transient(int B, int H, int W, int C, bool grad = true) {
-    if (f32 || getenv("DD_NO_TRANSIENT")) return tensor(B, H, W, C, grad);
+    if (f32 || sw->no_transient) return tensor(B, H, W, C, grad);
     const size_t save = act_bytes;
     const int id = tensor(B, H, W, C, grad);
     tr_max = std::max(tr_max, act_bytes - save);
@@ -165,6 +168,11 @@ struct Program {   // built and planned once (engine_graph.cpp, resolve_fusions)
     n.off += (size_t)c0 * 2; n.goff += (size_t)c0 * 2; n.C = C; n.parent = t[base].parent;
     t.push_back(n);
     return (int)t.size() - 1;
+  }
+  bool has_views(int id) const {       // another tensor is a column view of this one
+    for (size_t k = 0; k < t.size(); ++k)
+      if ((int)k != id && t[k].parent == id) return true;
+    return false;
   }
   size_t fp32_block(size_t count) {
     const size_t o = act_bytes;
@@ -267,19 +275,24 @@ struct dd_engine {
   std::vector<std::unique_ptr<NormW>> norms;
   std::vector<void*> dev_allocs;
 
-  Program unet, vae, guide;
-  int unet_in = -1, unet_out = -1, vae_in = -1, vae_out = -1, guide_in = -1, guide_feat = -1;
-  // f-2: the stage before the loop (built when the weights are present)
-  Program venc, text, text2;
-  int venc_in = -1, venc_out = -1, text_in = -1, text_out = -1;
-  char* venc_slab = nullptr; char* text_slab = nullptr;
-  float* tok_emb = nullptr; float* pos_emb = nullptr; int text_vocab = 0, text_hidden = 0, text_batch = 0;
-  int* text_ids = nullptr;
-  // second tower of a two-tower model (SDXL): its own program / slab, plus the pooled head (final LayerNorm output + text_projection)
-  int text2_in = -1, text2_out = -1, text2_final = -1;
-  char* text2_slab = nullptr;
-  float* tok_emb2 = nullptr; float* pos_emb2 = nullptr; int text2_vocab = 0, text2_hidden = 0, text2_proj = 0;
-  float* text2_proj_w = nullptr;                      // [proj][hidden] fp32
+  PlanSwitches sw = PlanSwitches::from_env();
+  // the programs: the loop's three, then the stage before the loop (f-2; built when the weights are present, else empty)
+  enum { UNET = 0, VAE = 1, GUIDE = 2, VENC = 3, TEXT = 4, NPROG = 6 };
+  Program prog[NPROG];
+  Program &unet = prog[UNET], &vae = prog[VAE], &guide = prog[GUIDE], &venc = prog[VENC];
+  int unet_in = -1, unet_out = -1, vae_in = -1, vae_out = -1, guide_in = -1, guide_feat = -1, venc_in = -1, venc_out = -1;
+  char* venc_slab = nullptr;
+  // What a CLIP text tower has beside prog[TEXT + w].  tower[1]: the second tower of a two-tower model (SDXL), which also keeps its
+  // final LayerNorm output and text_projection for the pooled head
+  struct TextTower {
+    int in = -1, out = -1, fin = -1;
+    char* slab = nullptr;
+    float* tok_emb = nullptr; float* pos_emb = nullptr; int vocab = 0, hidden = 0;
+    int proj = 0; float* proj_w = nullptr;            // [proj][hidden] fp32
+  };
+  TextTower tower[2];
+  int text_batch = 0; int* text_ids = nullptr;
+  dd_engine() { for (Program& P : prog) P.sw = &sw; }
   struct CrossSlot { ConvW* wk; ConvW* wv; int C; };
   std::vector<CrossSlot> cross_slots;
   std::vector<std::pair<bf16_t*, bf16_t*>> cross_kv;  // device K,V [2B*text_len, C] per slot
@@ -301,8 +314,7 @@ struct dd_engine {
 
   // instance slabs: [0 .. P-1]; each holds UNet | VAE | guide activations + small fp32 state
   struct Inst {
-    char* unet = nullptr; char* vae = nullptr; char* guide = nullptr;
-    float* eps2 = nullptr;  // view into unet slab (conv_out fp32 output)
+    char* act[3] = {nullptr, nullptr, nullptr};   // activation slabs of prog[UNET], prog[VAE], prog[GUIDE]
     float* z_in = nullptr; float* z_next = nullptr; float* x0 = nullptr; float* feat = nullptr; float* gfeat = nullptr;
     float* rs_stats = nullptr;   // CFG rescale: [B][8] per-image statistics of this step's forward, read again by its backward
   };
@@ -333,12 +345,14 @@ struct dd_engine {
   }
   // packed weights: every weight-derived device buffer in creation order (dd_packed_bytes / dd_export_packed / dd_import_packed)
   int declared = 0;
+  // dd_debug_plan_only: the plans are built and dumped without a device -- dmalloc hands out fake, never dereferenced addresses
+  bool plan_only = false; size_t fake_next = (size_t)1 << 20;
   bool shape_only = false;           // tensors were declared (shapes only): buffers are allocated, their content arrives by import
   std::vector<std::pair<char*, size_t>> packed;
   void* wupload(const void* host, size_t bytes) {
     void* d = dmalloc(bytes, false);
     packed.push_back({(char*)d, bytes});
-    if (!shape_only && bytes) {
+    if (!shape_only && !plan_only && bytes) {
       if (!host) throw std::runtime_error("internal: weight upload without host data");
       hipError_t e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
       if (e != hipSuccess) throw std::runtime_error(std::string("weight upload failed: ") + hipGetErrorString(e));
@@ -348,6 +362,7 @@ struct dd_engine {
   void* dmalloc(size_t bytes, bool zero = true) {
     void* p = nullptr;
     bytes = std::max<size_t>(bytes, 256);
+    if (plan_only) { p = (void*)fake_next; fake_next += rup_sz(bytes, 256); total_bytes += bytes; return p; }
     hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) throw std::runtime_error("hipMalloc of " + std::to_string(bytes) + " bytes failed: " + hipGetErrorString(e));
     if (zero) HIPCHK(hipMemset(p, 0, bytes));
@@ -364,15 +379,9 @@ struct dd_engine {
 };
 
 namespace ddi {
-
-inline int guide_feat_dim_decl(const dd_config& c) {
+inline int guide_feat_dim(const dd_config& c) {
   return c.guide_feature_dim > 0 ? c.guide_feature_dim : c.guide_planes[c.guide_stages - 1] * c.guide_expansion;
 }
-
-inline int guide_feat_dim(const dd_config& c) { return guide_feat_dim_decl(c); }
-}  // namespace ddi
-
-namespace ddi {
 // engine_weights.cpp
 ConvW* make_conv_f32(dd_engine* E, const float* w, const float* bias, int Cout, int Cin, int KH, int KW, int pad, int groups, bool need_bwd);
 // qrows / qscale: output rows [0, qrows) (weights and bias, forward and input-gradient packings) are multiplied by qscale before the bf16
@@ -386,12 +395,12 @@ ConvW* make_conv_cat(dd_engine* E, const std::string& model, const std::vector<s
                      int qrows = 0, float qscale = 1.f);
 ConvW* make_conv_bn(dd_engine* E, const std::string& model, const std::string& conv, const std::string& bn, int pad, float eps, int cin_total);
 NormW* make_norm(dd_engine* E, const std::string& model, const std::string& prefix);
-bool ln_fold_enabled();
+inline bool ln_fold_enabled(const dd_engine* E) { return !E->sw.no_ln_fold; }
 // engine_graph.cpp
 void build_unet(dd_engine* E);
 void build_vae(dd_engine* E);
 void build_vae_encoder(dd_engine* E);
-void build_text_encoder(dd_engine* E, int which = 0);
+void build_text_encoder(dd_engine* E, int w);      // tower w = 0 | 1
 void build_guide(dd_engine* E);
 void build_guide_mbv2(dd_engine* E);
 void build_guide_vit(dd_engine* E);

@@ -3,9 +3,7 @@
 
 namespace ddi {
 
-// ---------------------------------------------------------------------------------------------------
-// weight construction
-// ---------------------------------------------------------------------------------------------------
+// ---- weight construction ----
 // Every device buffer that holds weight-derived data goes through E->wupload(): it is registered, in creation order, in the engine's
 // packed-weight list (dd_packed_bytes / dd_export_packed / dd_import_packed), and an engine that only knows the tensor SHAPES
 // (dd_declare_tensor: a rank that will receive the packed buffers over RCCL) allocates it without packing anything on the host.
@@ -101,8 +99,6 @@ ConvW* make_conv_raw(dd_engine* E, const float* w_in, const float* bias_in, bool
   E->convs.push_back(std::move(cw));
   return E->convs.back().get();
 }
-
-bool ln_fold_enabled() { static const bool on = !getenv("DD_NO_LN_FOLD"); return on; }
 
 // ln: prefix of the LayerNorm to fold into this linear ("" = none)
 ConvW* make_conv(dd_engine* E, const std::string& model, const std::string& prefix, int pad, bool geglu, bool has_bias, const std::string& ln,

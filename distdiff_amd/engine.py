@@ -108,6 +108,8 @@ def _declare(l):
     l.dd_debug_tensor.argtypes = [vp, i, i, i, vp, vp]
     l.dd_debug_num_tensors.argtypes = [vp, i]
     l.dd_debug_fusion_plan.argtypes = [vp, i, vp, i]
+    l.dd_debug_plan_only.argtypes = [vp]
+    l.dd_debug_plan_dump.argtypes = [vp, i, vp, i]
     l.dd_debug_set_image.argtypes = [vp, vp]
     l.dd_debug_set_images.argtypes = [vp, vp, i]
     l.dd_workspace_bytes.argtypes = [vp]

@@ -236,6 +236,20 @@ int dd_debug_num_tensors(struct dd_engine* e, int prog);
  *       LayerNorm: spans it reads from the linear in front of it, 0 folded with its own statistics pass, -1 not folded
  *   [3] reserved, 0 */
 int dd_debug_fusion_plan(struct dd_engine* e, int prog, int* out, int cap);
+/* The plans without a device.  dd_debug_plan_only, before dd_finalize_weights: from then on the engine allocates fake, never
+ * dereferenced addresses (still counted by dd_workspace_bytes), uploads and copies nothing, frees nothing in dd_destroy, and every entry
+ * point that would launch or copy returns DD_ERR_STATE: dd_finalize_weights builds and plans every program on a machine without a GPU.
+ * dd_debug_plan_dump, after dd_finalize_weights (of any engine): the plans of program prog = 0 unet / 1 vae / 2 guide / 3 vae encoder /
+ * 4 text / 5 text2 (a program that was not built is empty) as int64 words; writes min(cap, words) and returns the word count (< 0: dd_status).
+ *   program: tensors, ops, act_bytes, grad_bytes, scratch_partial, scratch_tmp, scratch_rowpart, tr_max, tr_count
+ *   then per tensor (16): off, goff, parent, rows, C, ld, B, H, W, f32, grad, gf32, transient, tr_slot, glo, ghi
+ *   then per op (50): kind, x, y, res, raw, q, k, v, x2, cw, nw (index into the engine's convs / norms, -1 none), stride, up, relu,
+ *     out_f32, use_table, G, silu, eps (float bits), heads, D, Nq, Nk, cross_slot, causal, act_kind, pv_fp8, q_prescaled, patch, sel_stride,
+ *     stats_off, fused, x_acc, res_acc, x2_acc, res_alias, part, part_off, part_ld, producers (count), producers (FNV-1a hash), gn_fused,
+ *     ln_fold, x_fwd, ln_stats_off, rowstat_from, rowstat_emit, rowstat_ld, row_spans, flops (double bits)
+ * prog = 6, the engine: total_bytes, partial_cap, tmp_cap, packed buffers, then the size of every packed weight buffer in order */
+int dd_debug_plan_only(struct dd_engine* e);
+int dd_debug_plan_dump(struct dd_engine* e, int prog, int64_t* out, int cap);
 /* parity-test hook: evaluate the guide network of every later guided forward AT these images (DEVICE fp32 [count][B,3,8L,8L], the
  * decoder's output range, caller-owned; chained guided step k reads image min(k, count-1)) instead of the decoder's own output;
  * gradients still flow through the decoder.  The input-gradient of the ReLU / max-pool guide is piecewise constant in the image, so

@@ -547,3 +547,55 @@ def test_fusion_plan_is_fixed_at_finalize(hip_lib):
     assert ("gn", 0) in seen or ("gn", -1) in seen, seen
     assert "ln reads row partials" in seen and "ln folded, own pass" in seen, seen
     print("fusion plan: %s" % sorted(map(str, seen)))
+
+
+def test_debug_tensor_decides_by_how_the_engine_was_built(hip_lib):
+    """dd_debug_tensor refuses the gradient of an intermediate tensor when the gradient slab is packed by liveness (its bytes may have been
+    reused) and returns it when every gradient has a range of its own.  Which of the two holds is a property of the engine -- the plan
+    switches are read once, when it is created -- not of the environment at the time of the read: an engine built under DD_NO_GRAD_REUSE=1
+    and read with the variable unset returns the gradient, one built without it and read with it set refuses."""
+    from distdiff_amd.config import tiny_config
+    from distdiff_amd.engine import Engine
+    from distdiff_amd.scheduler import DDIMSchedule
+    from distdiff_amd.weights import synthetic_weights
+    cfg = tiny_config(max_batch=2)
+    w = synthetic_weights(cfg, seed=0, num_classes=5)
+    g = torch.Generator().manual_seed(4)
+    L, D = cfg.latent_size, cfg.guide.feature_dim
+    z = torch.randn(2, 4, L, L, generator=g)
+    emb = torch.randn(4, cfg.text_len, cfg.unet.cross_attention_dim, generator=g)
+    Pc, Pg = F.normalize(torch.randn(5, D, generator=g), dim=-1), F.normalize(torch.randn(5, 3, D, generator=g), dim=-1)
+    old = os.environ.pop("DD_NO_GRAD_REUSE", None)
+    engines = {}
+    try:
+        for built_with in (False, True):
+            if built_with:
+                os.environ["DD_NO_GRAD_REUSE"] = "1"
+            eng = engines[built_with] = Engine(cfg, w, enable_grad=True, max_guidance_period=2)
+            os.environ.pop("DD_NO_GRAD_REUSE", None)
+            sched = DDIMSchedule(cfg.scheduler)
+            eng.set_schedule(sched.set_timesteps(10), sched.alphas_cumprod, sched.final_alpha_cumprod, guidance_period=2)
+            eng.set_prototypes(Pc, Pg)
+            eng.set_prompt(emb.cuda())
+            eng.direct_guidance(z, torch.tensor([1, 3]), 7)
+        # built packed, read with the variable set: refused for the intermediates, served for the pinned program input
+        os.environ["DD_NO_GRAD_REUSE"] = "1"
+        refused = []
+        for idx in range(engines[False].debug_num_tensors(0)):
+            try:
+                engines[False].debug_tensor(0, idx, grad=True)
+            except RuntimeError as e:
+                assert "intermediate tensor" in str(e)
+                refused.append(idx)
+        assert refused and 0 not in refused, refused
+        # built with private ranges, read with the variable unset: every one of those gradients is returned
+        os.environ.pop("DD_NO_GRAD_REUSE", None)
+        got = [engines[True].debug_tensor(0, idx, grad=True) for idx in refused]
+        assert all(torch.isfinite(t).all() for t in got) and any(t.abs().max() > 0 for t in got)
+        assert torch.equal(engines[True].debug_tensor(0, 0, grad=True), engines[False].debug_tensor(0, 0, grad=True))
+    finally:
+        os.environ.pop("DD_NO_GRAD_REUSE", None)
+        if old is not None:
+            os.environ["DD_NO_GRAD_REUSE"] = old
+        for eng in engines.values():
+            eng.close()
