@@ -82,6 +82,47 @@ def test_conv_f32_forward_and_dgrad(hip_lib, case):
     close(unrows(gx, B, Cin, H, W), gx_ref + acc, 2e-5, name + " dgrad")
 
 
+def _ternary(shape, p, g):
+    return ((torch.rand(shape, generator=g) < p) * (torch.randint(0, 2, shape, generator=g) * 2 - 1)).float()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_conv_f32_exact_on_ternary_inputs(hip_lib, case):
+    """The same ten cases on inputs that make the result independent of the order of summation: x, w and the incoming gradient in
+    {-1, 0, 1} (non-zero density min(1, sqrt(400 / K))), bias, residual and the accumulated gradient small integers.  Every product and
+    every partial sum is an integer far below 2^24, so the fp32 MFMA chain, whatever its order, ends on the mathematical sum: forward and
+    accumulating input gradient must equal F.conv2d / autograd on the CPU bit for bit (the sign of a zero aside: both sides add +0)."""
+    from distdiff_amd import ops as O
+    name, B, Cin, Cout, H, W, k, stride, pad, groups = case
+    g = torch.Generator().manual_seed(7)
+    depth = Cin // groups * k * k
+    p = min(1.0, (400.0 / depth) ** 0.5)
+    x = _ternary((B, Cin, H, W), p, g)
+    w = _ternary((Cout, Cin // groups, k, k), p, g)
+    bias = torch.randint(-8, 9, (Cout,), generator=g).float()
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    res = torch.randint(-16, 17, (B, Cout, Ho, Wo), generator=g).float()
+    xr = x.clone().requires_grad_(True)
+    ref = F.relu(F.conv2d(xr, w, bias, stride=stride, padding=pad, groups=groups) + res)
+    assert depth + 8 + 16 < (1 << 24) and float(ref.detach().abs().max()) < (1 << 24)
+    same = lambda a, b: torch.equal((a.float().cpu() + 0.0).contiguous().view(torch.int32), (b.float().cpu() + 0.0).contiguous().view(torch.int32))
+    pk = O.PackedConvF32(w, pad, mode=0, groups=groups, bias=bias)
+    y = unrows(O.conv_f32(rows(x), pk, B, H, W, Ho, Wo, stride=stride, res=rows(res), relu=True), B, Cout, Ho, Wo)
+    bad = (y.cpu() != ref.detach()).nonzero()
+    assert same(y, ref.detach()), "%s fwd: %d elements differ, first (b, c, y, x) %s" % (name, len(bad), bad[:8].tolist())
+    gy = _ternary((B, Cout, Ho, Wo), min(1.0, (400.0 / (Cout // groups * k * k)) ** 0.5), g)
+    (gx_ref,) = torch.autograd.grad(ref, xr, gy)
+    gm = gy * (ref.detach() > 0)
+    pkb = O.PackedConvF32(w, pad, mode=1, groups=groups)
+    acc = torch.randint(-16, 17, (B, Cin, H, W), generator=g).float()
+    gx = unrows(O.conv_f32(rows(gm), pkb, B, Ho, Wo, H, W, stride=1, shift=1 if stride == 2 else 0, parity=1 if stride == 2 else 0, res=rows(acc)),
+                B, Cin, H, W)
+    want = gx_ref + acc
+    assert float(want.abs().max()) < (1 << 24)
+    bad = (gx.cpu() != want).nonzero()
+    assert same(gx, want), "%s dgrad: %d elements differ, first (b, c, y, x) %s" % (name, len(bad), bad[:8].tolist())
+
+
 def _engine(cfg, w, B):
     from distdiff_amd.engine import Engine
     from distdiff_amd.scheduler import DDIMSchedule

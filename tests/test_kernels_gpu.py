@@ -38,7 +38,7 @@ def ops(hip_lib):
 
 
 CONV_CASES = [
-    # name, B, Cin, Cout, H, W, k, stride, pad, up
+    # name, B, Cin, Cout, H, W, k, stride, pad, up[, ksplit (0: the launcher's automatic split, as the engine calls it)]
     ("3x3_c64", 2, 64, 128, 16, 16, 3, 1, 1, 0),
     ("3x3_c320_narrowN", 2, 320, 320, 16, 16, 3, 1, 1, 0),
     ("3x3_smallcin", 2, 4, 64, 16, 16, 3, 1, 1, 0),
@@ -50,21 +50,32 @@ CONV_CASES = [
     ("7x7_stem", 1, 3, 64, 32, 32, 7, 2, 3, 0),
     ("3x3_cout3", 1, 128, 3, 16, 16, 3, 1, 1, 0),
     ("3x3_deepK_splitk", 2, 1280, 128, 8, 8, 3, 1, 1, 0),
-    # shapes routed to the persistent big-tile kernel (M >= 1024): 128x256, 128x320, 256x128 tiles, ragged M, split-K
-    ("big_128x256", 2, 128, 256, 32, 32, 3, 1, 1, 0),
-    ("big_128x320_ragged", 2, 320, 320, 24, 25, 3, 1, 1, 0),
-    ("big_256x128", 1, 64, 128, 40, 40, 3, 1, 1, 0),
-    ("big_up2", 2, 64, 256, 16, 16, 3, 1, 1, 1),
-    ("big_stride2", 2, 64, 256, 64, 64, 3, 2, 1, 0),
-    ("big_1x1_shallowK", 2, 320, 640, 32, 32, 1, 1, 0, 0),
+    # M >= 1024 at a few hundred work items: with the automatic split the launcher gives these to the small kernel with split-K (the names
+    # say what runs; CONV_PLANS pins it) ...
+    ("3x3_c128_n256_m2048_small_split4", 2, 128, 256, 32, 32, 3, 1, 1, 0),
+    ("3x3_c320_n320_ragged_m1200_small_split9", 2, 320, 320, 24, 25, 3, 1, 1, 0),
+    ("3x3_c64_n128_m1600_small_split2", 1, 64, 128, 40, 40, 3, 1, 1, 0),
+    ("3x3_up2_n256_m2048_small_split2", 2, 64, 256, 16, 16, 3, 1, 1, 1),
+    ("3x3_stride2_n256_m2048_small_split2", 2, 64, 256, 64, 64, 3, 2, 1, 0),
+    ("1x1_c320_n640_m2048_small", 2, 320, 640, 32, 32, 1, 1, 0, 0),
     ("big_deepK_splitk", 2, 1280, 320, 24, 24, 3, 1, 1, 0),
-    # <= 100 (N % 160 == 0) / <= 24 (N % 128 == 0) K-steps run as two 4-wave workgroups per CU (128x160 / 128x128, 2 LDS stages);
-    # deeper items keep the 8-wave 128x256 / 256x160 / 256x128 forms: one case per form and per epilogue variant
-    ("big8_128x256_deepK", 2, 512, 256, 24, 24, 3, 1, 1, 0),
-    ("big8_256x128_deepK", 2, 512, 128, 32, 32, 3, 1, 1, 0),
+    # ... and with ksplit = 1 the persistent big-tile kernel takes the same shapes: <= 100 (N % 160 == 0) / <= 24 (N % 128 == 0) K-steps run
+    # as two 4-wave workgroups per CU (128x160 / 128x128, 2 LDS stages); deeper items keep the 8-wave 128x256 / 256x160 / 256x128 forms
+    ("big_128x128_ks1_dgrad_256x128", 2, 128, 256, 32, 32, 3, 1, 1, 0, 1),
+    ("big_128x160_ragged_ks1_dgrad_128x160", 2, 320, 320, 24, 25, 3, 1, 1, 0, 1),
+    ("big_128x128_m1600_ks1_dgrad_256x128", 1, 64, 128, 40, 40, 3, 1, 1, 0, 1),
+    ("big_128x128_up2_ks1_dgrad_256x128", 2, 64, 256, 16, 16, 3, 1, 1, 1, 1),
+    ("big_128x128_stride2_ks1_dgrad_256x128", 2, 64, 256, 64, 64, 3, 2, 1, 0, 1),
+    ("big_128x160_1x1_shallowK_ks1_dgrad_128x160", 2, 320, 640, 32, 32, 1, 1, 0, 0, 1),
+    ("big_128x256_deepK_ks1_dgrad_128x256", 2, 512, 256, 24, 24, 3, 1, 1, 0, 1),
+    ("big_256x128_deepK_ks1_dgrad_128x128", 2, 512, 128, 32, 32, 3, 1, 1, 0, 1),
+    ("big_128x160_pointwise_ks1_dgrad_128x160", 4, 1280, 320, 32, 32, 1, 1, 0, 0, 1),
+    ("big_128x128_ragged_ks1_dgrad_256x128", 3, 128, 384, 20, 21, 3, 1, 1, 0, 1),
+    ("3x3_c512_n256_deepK_small_split15", 2, 512, 256, 24, 24, 3, 1, 1, 0),
+    ("3x3_c512_n128_deepK_small_split15", 2, 512, 128, 32, 32, 3, 1, 1, 0),
     ("big8_256x160_100steps", 4, 768, 160, 32, 32, 3, 1, 1, 0),
-    ("big4_128x160_pointwise", 4, 1280, 320, 32, 32, 1, 1, 0, 0),
-    ("big4_128x128_ragged", 3, 128, 384, 20, 21, 3, 1, 1, 0),
+    ("1x1_c1280_n320_m4096_small_split4", 4, 1280, 320, 32, 32, 1, 1, 0, 0),
+    ("3x3_c128_n384_ragged_small_split4", 3, 128, 384, 20, 21, 3, 1, 1, 0),
     # 3x3 / stride 1 shapes with >= 192 tiles of 256 pixels, W a power of two, Cin % 64 == 0, N % 320 == 0 or % 256 == 0: the halo-resident
     # ping-pong kernel (conv_halo.hip), forward and -- where Cin qualifies as N -- input-gradient; image widths 16 / 32 / 64 / 128
     ("halo_320_32x32", 48, 320, 320, 32, 32, 3, 1, 1, 0),
@@ -97,9 +108,67 @@ CONV_CASES = [
 ]
 
 
+_G, _HALO, _PERSIST = "general", "conv_halo", "conv_halo_persist"
+_F = {f: "big_" + f + ("_two_workgroups" if f in ("128x160", "128x128") else "") for f in ("128x256", "256x160", "256x128", "128x160", "128x128")}
+# (forward plan, input-gradient plan) of every case whose name states a kernel or a form (big*, halo*, n3_, n4_): asserted on the GPU
+# before the launch and on the CPU by tests/test_conv_exact_cases.py, so a change of routing cannot leave a name behind
+CONV_PLANS = {
+    "big_128x128_ks1_dgrad_256x128": ((_G, _F["128x128"], 1), (_G, _F["256x128"], 1)),
+    "big_128x160_ragged_ks1_dgrad_128x160": ((_G, _F["128x160"], 1), (_G, _F["128x160"], 1)),
+    "big_128x128_m1600_ks1_dgrad_256x128": ((_G, _F["128x128"], 1), (_G, _F["256x128"], 1)),
+    "big_128x128_up2_ks1_dgrad_256x128": ((_G, _F["128x128"], 1), (_G, _F["256x128"], 1)),
+    "big_128x128_stride2_ks1_dgrad_256x128": ((_G, _F["128x128"], 1), (_G, _F["256x128"], 1)),
+    "big_128x160_1x1_shallowK_ks1_dgrad_128x160": ((_G, _F["128x160"], 1), (_G, _F["128x160"], 1)),
+    "big_128x256_deepK_ks1_dgrad_128x256": ((_G, _F["128x256"], 1), (_G, _F["128x256"], 1)),
+    "big_256x128_deepK_ks1_dgrad_128x128": ((_G, _F["256x128"], 1), (_G, _F["128x128"], 1)),
+    "big_128x160_pointwise_ks1_dgrad_128x160": ((_G, _F["128x160"], 1), (_G, _F["128x160"], 1)),
+    "big_128x128_ragged_ks1_dgrad_256x128": ((_G, _F["128x128"], 1), (_G, _F["256x128"], 1)),
+    "big_deepK_splitk": ((_G, _F["256x160"], 15), (_G, _F["128x160"], 4)),
+    "big8_256x160_100steps": ((_G, _F["256x160"], 12), (_G, _F["128x128"], 2)),
+    "halo_320_32x32": ((_HALO, None, 1), (_HALO, None, 1)),
+    "halo_256_64x64": ((_PERSIST, None, 1), (_G, _F["256x128"], 2)),
+    "halo_640_16x16": ((_HALO, None, 1), (_G, _F["256x128"], 2)),
+    "halo_256_128x128": ((_PERSIST, None, 1), (_PERSIST, None, 1)),
+    "halo_up2_320": ((_HALO, None, 1), (_PERSIST, None, 1)),
+    "halo_w256_2x128_tiles": ((_PERSIST, None, 1), (_G, _F["256x128"], 1)),
+    "halo_w512_up2": ((_PERSIST, None, 1), (_G, _F["256x128"], 1)),
+    "halo_n128_512x128_tiles": ((_PERSIST, None, 1), (_PERSIST, None, 1)),
+    "halo_persist_n128_cin64_3tiles_oddK": ((_PERSIST, None, 1), (_G, _F["256x128"], 1)),
+    "halo_persist_n256_cin192_2ntiles": ((_PERSIST, None, 1), (_G, "small_256x64", 1)),
+    "halo_persist_ragged_288_tiles": ((_PERSIST, None, 1), (_PERSIST, None, 1)),
+    "halo_persist_up2_cin128": ((_PERSIST, None, 1), (_PERSIST, None, 1)),
+    "halo_8x8_multi_image_split4": ((_HALO, None, 4), (_HALO, None, 4)),
+    "halo_8x8_cin2560_split8": ((_HALO, None, 8), (_HALO, None, 4)),
+    "halo_8x8_cin2560_b16_split_divides_chunks": ((_HALO, None, 8), (_HALO, None, 4)),
+    "n3_vae_conv_out": ((_G, "small_256x64", 1), (_G, _F["128x128"], 1)),
+    "n4_unet_conv_out": ((_G, "small_256x64", 1), (_G, _F["128x160"], 1)),
+}
+
+
+def conv_case_launches(case):
+    """((geometry, keywords) of the forward launch, the same of the input-gradient launch) of a CONV_CASES entry"""
+    name, B, Cin, Cout, H, W, k, stride, pad, up = case[:10]
+    ksplit = case[10] if len(case) > 10 else 0
+    Hl, Wl = H << up, W << up
+    Ho, Wo = (Hl + 2 * pad - k) // stride + 1, (Wl + 2 * pad - k) // stride + 1
+    fwd = ((B, H, W, Ho, Wo), dict(stride=stride, shift=up, ksplit=ksplit))
+    dgrad = ((B, Ho, Wo, Hl, Wl), dict(stride=1, shift=1, parity=1, ksplit=ksplit) if stride == 2 else dict(stride=1, ksplit=ksplit))
+    return fwd, dgrad
+
+
+def expected_conv_plans(name):
+    """CONV_PLANS[name]; in the child process of test_halo_switch_fallbacks_stay_correct the persistent form is switched off"""
+    plans = CONV_PLANS.get(name)
+    if plans and os.environ.get("DD_HALO_PERSIST") == "0":
+        plans = tuple((_HALO, None, p[2]) if p[0] == _PERSIST else p for p in plans)
+    return plans
+
+
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
 def test_conv_forward_and_dgrad(ops, case):
-    name, B, Cin, Cout, H, W, k, stride, pad, up = case
+    name, B, Cin, Cout, H, W, k, stride, pad, up = case[:10]
+    (fgeom, fkw), (dgeom, dkw) = conv_case_launches(case)
+    plans = expected_conv_plans(name)
     g = torch.Generator().manual_seed(hash(name) % 1000)
     x = bf(torch.randn(B, Cin, H, W, generator=g))
     w = bf(torch.randn(Cout, Cin, k, k, generator=g) / math.sqrt(Cin * k * k))
@@ -111,7 +180,10 @@ def test_conv_forward_and_dgrad(ops, case):
     cin_pad = (Cin + 7) // 8 * 8
     xd = ops.to_nhwc_bf16(x, cin_pad).cuda()
     pk = ops.PackedConv(w, pad, mode=0, bias=bias)
-    y = ops.conv_gemm(xd, pk, B, H, W, Ho, Wo, stride=stride, shift=up)
+    assert fgeom == (B, H, W, Ho, Wo)
+    if plans:
+        assert ops.conv_gemm_plan(xd, pk, *fgeom, **fkw) == plans[0], name + " fwd: the launcher plans another kernel than the name states"
+    y = ops.conv_gemm(xd, pk, *fgeom, **fkw)
     torch.cuda.synchronize()
     assert_close(ops.from_nhwc(y, B, Ho, Wo), ref.detach(), what=name + " fwd")
     # input-gradient (dgrad): conv of dY with the transposed/flipped weights; stride 2 -> input-dilated gather
@@ -121,10 +193,10 @@ def test_conv_forward_and_dgrad(ops, case):
     dyd = ops.to_nhwc_bf16(dy, cout_pad).cuda()
     pkd = ops.PackedConv(w, pad, mode=1)
     Hl, Wl = xin.shape[2], xin.shape[3]
-    if stride == 2:
-        dx = ops.conv_gemm(dyd, pkd, B, Ho, Wo, Hl, Wl, stride=1, shift=1, parity=1)
-    else:
-        dx = ops.conv_gemm(dyd, pkd, B, Ho, Wo, Hl, Wl, stride=1)
+    assert dgeom == (B, Ho, Wo, Hl, Wl)
+    if plans:
+        assert ops.conv_gemm_plan(dyd, pkd, *dgeom, **dkw) == plans[1], name + " dgrad: the launcher plans another kernel than the name states"
+    dx = ops.conv_gemm(dyd, pkd, *dgeom, **dkw)      # stride 2: the input-dilated gather (shift = 1, parity = 1)
     torch.cuda.synchronize()
     assert_close(ops.from_nhwc(dx, B, Hl, Wl), gref, what=name + " dgrad")
     if up:  # transpose of the fused nearest-2x: 2x2 sum pooling
