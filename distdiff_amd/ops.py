@@ -293,9 +293,14 @@ def layernorm(x, gamma, beta, eps, dy=None, stats=None, accumulate_into=None, y=
     return dx
 
 
-def _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, causal=False, q_prescaled=False, pv_fp8=False, no_shortk=False):
+def _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, causal=False, q_prescaled=False, pv_fp8=False, no_shortk=False, o=None):
+    """o: write the output there (B * Nq rows, H * D columns: a column view of a wider buffer, as the engine passes it) instead of into a
+    fresh tensor"""
     p = AttnParams()
-    o = torch.zeros((B * Nq, H * D), device=q.device, dtype=q.dtype)
+    if o is None:
+        o = torch.zeros((B * Nq, H * D), device=q.device, dtype=q.dtype)
+    elif tuple(o.shape) != (B * Nq, H * D) or o.dtype != q.dtype or o.stride(1) != 1:
+        raise ValueError("attention: o must be %s rows of %d unit-stride columns of %s" % (B * Nq, H * D, q.dtype))
     lse = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
     p.q, p.k, p.v, p.o, p.lse = _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse)
     p.ldq, p.ldk, p.ldv, p.ldo = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
@@ -331,11 +336,11 @@ def _attn_scratch(q, Nq, Nk, D, ws_images):
     return (_ptr(ws), C.c_size_t(ws.numel()), _ptr(tap), _ptr(part), C.c_size_t(part.numel() * 4)), (ws, tap, part)
 
 
-def attention_gemm(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, ws_images=8):
+def attention_gemm(q, k, v, B, H, Nq, Nk, D, scale, d_o=None, ws_images=8, o=None):
     """wide-head attention through the GEMM kernel (dd_op_attention_gemm_*): same arguments / results as `attention`.  ws_images: scratch
     for that many images (single-head layers then run min(ws_images, 8, B) images per launch)."""
     L = _L(q)
-    p, o, lse = _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale)
+    p, o, lse = _attn_fwd_params(q, k, v, B, H, Nq, Nk, D, scale, o=o)
     sc, _keep = _attn_scratch(q, Nq, Nk, D, max(1, ws_images))
     check(L.dd_op_attention_gemm_fwd(C.byref(p), *sc, _stream()), "attn_gemm_fwd")
     if d_o is None:
