@@ -334,6 +334,7 @@ __global__ void gap_bwd_kernel(const float* gf, T* dx, int ld, int B, int HW, in
   }
 }
 
+// adds the wave sums red[0..n) left to right; gn_block_sum in norm.hip pairs its four, (0 + 1) + (2 + 3): different bits, so not one function
 __device__ float block_sum(float v, float* red) {
   v = wave_sum(v);
   __syncthreads();
