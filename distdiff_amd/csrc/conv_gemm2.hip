@@ -393,7 +393,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void conv_gemm
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           const float2 st = *(const float2*)(smem + LNS_OFF + c_slot2 * 1024 + (wm * (TM * 16) + i * 16 + fr) * 8);
-          rs[i] = st.y * p.alpha; nm[i] = -st.y * st.x;
+          rs[i] = st.y * p.alpha; nm[i] = -rs[i] * st.x;     // alpha scales the folded term too, as in Epi::apply
         }
         auto four = [&](const f32x4& a, const float4& b, const float4& c, int i) {
           const float v0 = __builtin_fmaf(rs[i], a[0], __builtin_fmaf(nm[i], c.x, b.x)), v1 = __builtin_fmaf(rs[i], a[1], __builtin_fmaf(nm[i], c.y, b.y));
@@ -521,7 +521,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void conv_gemm
 #pragma unroll
           for (int i = 0; i < TM; ++i) {
             const float2 st = *(const float2*)(smem + LNS_OFF + c_slot2 * 1024 + (wm * (TM * 16) + i * 16 + fr) * 8);
-            rs[i] = st.y * p.alpha; nm[i] = -st.y * st.x;
+            rs[i] = st.y * p.alpha; nm[i] = -rs[i] * st.x;     // alpha scales the folded term too, as in Epi::apply
           }
         }
 #pragma unroll

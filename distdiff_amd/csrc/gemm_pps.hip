@@ -38,7 +38,7 @@ __device__ __forceinline__ void pp_epilogue_geglu(const ConvGemmParams& p, f32x4
 #pragma unroll
     for (int a4 = 0; a4 < 2; ++a4) {
       const int a = a2 + a4, m = mrow[a4];
-      const float rs = lst[a4].y * p.alpha, nm = -lst[a4].y * lst[a4].x;
+      const float rs = lst[a4].y * p.alpha, nm = -rs * lst[a4].x;      // alpha scales the folded term too: alpha * rstd * (acc - mean * c1) + b'
       float h[8], g[8];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {

@@ -204,7 +204,7 @@ __device__ __forceinline__ void ws_wave(const ConvGemmParams& p, unsigned char* 
       WS_STAMP(it, 2 + 2 * a);
       // ---- epilogue of rows m0 + a * 16 + fr
       const int m = m0 + row;
-      const float rs = lc.y * p.alpha, nm = -lc.y * lc.x;      // CF_LNFOLD: rstd and -rstd * mean of this lane's row (1, 0 otherwise)
+      const float rs = lc.y * p.alpha, nm = -rs * lc.x;      // CF_LNFOLD: alpha * rstd and -alpha * rstd * mean of this lane's row (alpha, 0 otherwise)
       if constexpr (GEGLU) {
         // tile 0: hidden, tile 1: gate pre-activations of output columns fq * 4 .. + 3 of this wave's 16
         float h[4], g[4];

@@ -26,7 +26,7 @@ enum ConvFlags {
   CF_STATS = 256,    // also emit per-(64-row block, output channel) partial statistics (mean, M2) of the stored values: the
                      // GroupNorm that consumes this tensor then needs no statistics pass of its own (conv_gemm_can_emit_stats)
   CF_LNFOLD = 1024,  // the A operand is the RAW input x of a LayerNorm whose gamma is folded into the packed weights (W' = gamma o W) and
-                     // whose beta into the bias (b' = b + W beta): out = rstd[m] * (acc - mean[m] * c1[n]) + b'[n] with
+                     // whose beta into the bias (b' = b + W beta): out = alpha * rstd[m] * (acc - mean[m] * c1[n]) + b'[n] with
                      // c1[n] = sum_k W'[n, k] (of the bf16-rounded W'), (mean, rstd) = ln_stats[m] -- LayerNorm(x) W^T + b without ever
                      // materialising LayerNorm(x).  Pointwise (1x1 / linear) layers only.
   CF_ROWSTATS = 2048 // also emit, per output row and per 80-/64-column wave span, (sum v, sum v^2) of the fp32 values in front of their bf16 rounding

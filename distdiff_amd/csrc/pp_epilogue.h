@@ -55,7 +55,7 @@ __device__ __forceinline__ void pp_epilogue(const ConvGemmParams& p, f32x4 (&acc
       const int a = blk * 4 + hb * LA + a4;
       const int m = mrow[a4];
       bf16_t* yp = (bf16_t*)p.y + (size_t)m * p.y_ld;
-      const float rs = lst[a4].y * p.alpha, nm = -lst[a4].y * lst[a4].x;      // CF_LNFOLD: rstd and -rstd * mean of this lane's row (1, 0 otherwise)
+      const float rs = lst[a4].y * p.alpha, nm = -rs * lst[a4].x;      // CF_LNFOLD: alpha * rstd and -alpha * rstd * mean of this lane's row (alpha, 0 otherwise)
       float r1 = 0.f, r2 = 0.f;                          // CF_ROWSTATS
       auto four = [&](const f32x4& v, int col, unsigned q0, unsigned q1, float* t1, float* t2) {
         float4 b = *(const float4*)(bw + col);

@@ -5,6 +5,9 @@ table on the CPU); tests/test_conv_exact_gpu.py runs it.
 A case is (Problem, plan, f16): the problem in the terms of tests/exact_ref.py, the (kind, form, split) the launcher must give it, and
 whether the fp16 library runs it too (one case per kind and form).  The shapes are the smallest the planner routes as stated; tuples in
 the comments are (B, Cin, Cout, H, W).  Halo kinds need M >= 49152 rows.
+
+STAT_CASES is the second table: the statistics epilogues, the LayerNorm fold and the GEGLU product, which have closed forms on the
+ternary family only (exact_ref.expected_buffers); STAT_REFUSALS is what the launcher must refuse of them.
 """
 import os
 import sys
@@ -15,6 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_conv_big_bits as big  # noqa: E402
 import make_pingpong_bits as pp  # noqa: E402
+import exact_ref as X  # noqa: E402
 from exact_ref import Problem, pad8, stored_width, store_dtype  # noqa: E402
 
 G, HALO, PERSIST, WS, PPS = "general", "conv_halo", "conv_halo_persist", "gemm_ws", "gemm_pps"
@@ -120,9 +124,138 @@ NAMES = [c[0].name for c in CASES]
 HALO_CASES = [c for c in CASES if c[1][0] in (HALO, PERSIST)]
 
 
+# ---- the statistics epilogues (CF_STATS "s", CF_ROWSTATS "w"), the LayerNorm fold ("l") and the GEGLU product ("G", "g"): ternary only ----
+# A case is (Problem, plan, f16, rowspan, slots): rowspan is the span layout of a "w" case (span_list), slots names the CF_STATS slot map
+# of an "s" case ("m64": m >> 6; "halo": exact_ref.slots_halo).  One case per (kernel or form) x (flag set) the launcher honours.  No
+# kernel honours "l" together with "w" (rowstats_shape_ok refuses CF_LNFOLD) or "s" together with "w"; both are asserted as refusals in
+# tests/test_conv_exact_cases.py.
+
+def sconv(name, B, Cin, Cout, H, W, plan, fl, f16=False, slots="m64", **kw):
+    kw.setdefault("ksplit", 1 if plan[0] == G else 0)
+    return Problem(name, B, Cin, Cout, H, W, fl=fl, **kw), plan, f16, 0, slots
+
+
+def sgemm(name, M, K, N, plan, fl, f16=False, rowspan=0, ksplit=1):
+    return Problem(name, 1, K, N, M, 1, k=1, fl=fl, ksplit=ksplit), plan, f16, rowspan, "m64"
+
+
+STAT_CASES = [
+    # ---- CF_STATS on conv_gemm_big_kernel: FE epilogue of every form ----
+    sconv("s_big_128x256", 2, 512, 256, 24, 24, (G, F1, 1), "bs", f16=True),
+    sconv("s_big_128x256_res_relu", 2, 512, 256, 24, 24, (G, F1, 1), "brus"),
+    sconv("s_big_256x160", 2, 1280, 320, 24, 24, (G, F2, 1), "bs", f16=True),
+    sconv("s_big_256x128", 2, 512, 128, 32, 32, (G, F3, 1), "bs", f16=True),
+    sconv("s_big_128x160_two_workgroups_res", 2, 320, 320, 24, 24, (G, F4, 1), "brs", f16=True),
+    sconv("s_big_128x160_two_workgroups_pointwise_res", 4, 1280, 320, 32, 32, (G, F4, 1), "brs", k=1),
+    sconv("s_big_128x128_two_workgroups_res", 3, 128, 384, 32, 32, (G, F5, 1), "brs", f16=True),
+    # ---- CF_STATS on the halo kernels: slot m >> 6, and the block map of tiles narrower than 64 pixels ----
+    sconv("s_halo_320_32x32_res", 48, 320, 320, 32, 32, (HALO, None, 1), "brs", f16=True),
+    sconv("s_halo_320_32x32_res_relu", 48, 320, 320, 32, 32, (HALO, None, 1), "brus"),
+    sconv("s_halo_640_16x16", 192, 128, 640, 16, 16, (HALO, None, 1), "bs"),
+    sconv("s_halo_up2_320", 24, 128, 320, 32, 32, (HALO, None, 1), "bs", up=1),
+    sconv("s_halo_w48_block_map", 24, 64, 320, 48, 48, (HALO, None, 1), "bs", f16=True, slots="halo"),
+    sconv("s_halo_w80_block_map", 8, 128, 320, 80, 80, (HALO, None, 1), "bs", slots="halo"),
+    sconv("s_halo_w96_block_map_res", 6, 320, 320, 96, 96, (HALO, None, 1), "brs", slots="halo"),
+    sconv("s_persist_256_64x64_res", 12, 64, 256, 64, 64, (PERSIST, None, 1), "brs", f16=True, slots="halo"),
+    sconv("s_persist_w256_res", 1, 64, 256, 256, 256, (PERSIST, None, 1), "brs", slots="halo"),
+    sconv("s_persist_n128_256x512_res", 1, 128, 128, 256, 512, (PERSIST, None, 1), "brs", slots="halo"),
+    # ---- gemm_pps: CF_STATS, CF_ROWSTATS (80-column spans) ----
+    sgemm("s_pps_n320_res", 49152, 320, 320, (PPS, None, 1), "brs", f16=True),
+    sgemm("s_pps_n320_res_relu", 49152, 320, 320, (PPS, None, 1), "brus"),
+    sgemm("w_pps_n320_res", 49152, 320, 320, (PPS, None, 1), "brw", f16=True, rowspan=80),
+    sgemm("w_pps_n640_k1280_res", 49152, 1280, 640, (PPS, None, 1), "brw", rowspan=80),
+    # ---- gemm_ws: CF_ROWSTATS in 48 + 32 column spans ----
+    sgemm("w_ws_n320", 33024, 320, 320, (WS, None, 1), "bw", f16=True, rowspan="ws"),
+    sgemm("w_ws_n640_relu", 36928, 320, 640, (WS, None, 1), "buw", rowspan="ws"),
+    sgemm("w_ws_n640_views", 32768, 320, 640, (WS, None, 1), "bwv", rowspan="ws"),
+    # ---- CF_ROWSTATS on the two-workgroup forms of conv_gemm_big_kernel ----
+    sgemm("w_big_128x160_two_workgroups_res", 2048, 320, 320, (G, F4, 1), "brw", f16=True, rowspan=80),
+    sgemm("w_big_128x160_two_workgroups_res_ragged_m", 3000, 640, 1280, (G, F4, 1), "brw", rowspan=80),
+    sgemm("w_big_128x128_two_workgroups_res", 4096, 320, 384, (G, F5, 1), "brw", f16=True, rowspan=64),
+    # ---- CF_LNFOLD: the generic epilogue of the small kernel, the folded epilogue of the two-workgroup forms, gemm_ws, gemm_pps ----
+    sgemm("l_small_256x64", 300, 320, 320, (G, S256, 1), "bl", f16=True),
+    sgemm("l_small_128x128", 64, 320, 320, (G, S128, 1), "bl", f16=True),
+    sgemm("l_small_256x64_alpha", 300, 320, 320, (G, S256, 1), "bla"),
+    sgemm("l_big_128x160_two_workgroups", 2048, 640, 640, (G, F4, 1), "bl", f16=True),
+    sgemm("l_big_128x160_two_workgroups_alpha", 2048, 640, 640, (G, F4, 1), "bla"),
+    sgemm("l_big_128x160_two_workgroups_n3840", 1024, 1280, 3840, (G, F4, 1), "bl"),
+    sgemm("l_ws_n960", 33088, 320, 960, (WS, None, 1), "bl", f16=True),
+    sgemm("l_ws_n960_alpha", 33088, 320, 960, (WS, None, 1), "bla"),
+    sgemm("l_pps_n640", 49152, 640, 640, (PPS, None, 1), "bl", f16=True),
+    sgemm("l_pps_n640_alpha", 49152, 640, 640, (PPS, None, 1), "bla"),
+    # ---- GEGLU: y = hidden * gelu_poly(gate), with the fold and with the raw stash ----
+    sgemm("G_big_128x128_two_workgroups_fold", 1024, 320, 2560, (G, F5, 1), "bGl", f16=True),
+    sgemm("G_big_128x128_two_workgroups_fold_alpha", 1024, 320, 2560, (G, F5, 1), "bGla"),
+    sgemm("g_big_128x128_two_workgroups_fold_raw", 1024, 320, 512, (G, F5, 1), "bgl"),
+    sgemm("G_big_128x128_two_workgroups_ragged_m", 1500, 320, 2560, (G, F5, 1), "bG", f16=True),
+    sgemm("G_small_128x128", 200, 128, 512, (G, S128, 1), "bG", f16=True),
+    sgemm("g_ws_n2560_fold_raw", 33088, 320, 2560, (WS, None, 1), "bgl", f16=True),
+    sgemm("G_ws_n512", 32832, 320, 512, (WS, None, 1), "bG", f16=True),
+    sgemm("G_pps_n1024_fold", 12288, 320, 1024, (PPS, None, 1), "bGl", f16=True),
+    sgemm("G_pps_n2560_k640_fold", 24576, 640, 2560, (PPS, None, 1), "bGl"),
+    sgemm("G_pps_n1024_fold_alpha", 12288, 320, 1024, (PPS, None, 1), "bGla"),
+    sgemm("g_pps_raw_stash_and_y", 40960, 256, 512, (PPS, None, 1), "bg", f16=True),
+    # ---- the fold and GEGLU on every other recorded (form, split): the generic epilogue (Epi::apply) of the eight-wave forms and of the
+    # small kernel, and the split-K reduce kernel (the smallest GEMMs the planner routes so; ksplit = 4 is the caller's) ----
+    sgemm("G_small_128x128_fold", 64, 128, 64, (G, S128, 1), "bGl", ksplit=0),
+    sgemm("G_small_128x128_splitk2", 64, 128, 64, (G, S128, 2), "bG", ksplit=4),
+    sgemm("l_small_128x128_splitk2", 64, 128, 64, (G, S128, 2), "bl", ksplit=4),
+    sgemm("G_small_128x128_splitk2_fold", 64, 128, 64, (G, S128, 2), "bGl", ksplit=4),
+    sgemm("G_small_256x64", 256, 128, 64, (G, S256, 1), "bG", f16=True, ksplit=0),
+    sgemm("G_small_256x64_fold", 256, 128, 64, (G, S256, 1), "bGl", ksplit=0),
+    sgemm("G_small_256x64_splitk2", 256, 128, 64, (G, S256, 2), "bG", ksplit=4),
+    sgemm("l_small_256x64_splitk2", 256, 128, 64, (G, S256, 2), "bl", ksplit=4),
+    sgemm("G_small_256x64_splitk2_fold", 256, 128, 64, (G, S256, 2), "bGl", ksplit=4),
+    sgemm("G_big_128x256", 1024, 2560, 256, (G, F1, 1), "bG", f16=True),
+    sgemm("l_big_128x256", 1024, 2560, 256, (G, F1, 1), "bl", f16=True),
+    sgemm("G_big_128x256_fold", 1024, 2560, 256, (G, F1, 1), "bGl"),
+    sgemm("G_big_128x256_splitk4", 1024, 2560, 256, (G, F1, 4), "bG", ksplit=4),
+    sgemm("l_big_128x256_splitk4", 1024, 2560, 256, (G, F1, 4), "bl", ksplit=4),
+    sgemm("G_big_128x256_splitk4_fold", 1024, 2560, 256, (G, F1, 4), "bGl", ksplit=4),
+    sgemm("G_big_256x128", 1024, 128, 64, (G, F3, 1), "bG", f16=True),
+    sgemm("l_big_256x128", 1024, 128, 64, (G, F3, 1), "bl", f16=True),
+    sgemm("G_big_256x128_fold", 1024, 128, 64, (G, F3, 1), "bGl"),
+    sgemm("G_big_256x128_splitk2", 1024, 128, 64, (G, F3, 2), "bG", ksplit=4),
+    sgemm("l_big_256x128_splitk2", 1024, 128, 64, (G, F3, 2), "bl", ksplit=4),
+    sgemm("G_big_256x128_splitk2_fold", 1024, 128, 64, (G, F3, 2), "bGl", ksplit=4),
+    sgemm("l_big_128x160_two_workgroups_splitk2", 1024, 128, 320, (G, F4, 2), "bl", ksplit=4),
+    sgemm("l_big_128x128_two_workgroups", 1024, 128, 128, (G, F5, 1), "bl", f16=True),
+    sgemm("G_big_128x128_two_workgroups_splitk2", 1024, 128, 128, (G, F5, 2), "bG", ksplit=4),
+    sgemm("l_big_128x128_two_workgroups_splitk2", 1024, 128, 128, (G, F5, 2), "bl", ksplit=4),
+    sgemm("G_big_128x128_two_workgroups_splitk2_fold", 1024, 128, 128, (G, F5, 2), "bGl", ksplit=4),
+]
+STAT_NAMES = [c[0].name for c in STAT_CASES]
+
+
+def stat_expected(prob, acc, inp, dtype, rowspan, slots, mutant=None, check=True):
+    """exact_ref.expected_buffers for a case of STAT_CASES (or one cut to fewer rows), with the exactness conditions asserted first;
+    returns (buffers, bounds found)"""
+    spans = span_list(prob, rowspan) if "w" in prob.fl else None
+    slot_of = (X.slots_halo if slots == "halo" else X.slots_m64)(prob) if "s" in prob.fl else None
+    bufs = X.expected_buffers(prob, acc, inp, dtype, spans, slot_of, mutant)
+    found = None
+    if check:
+        assert mutant is None
+        X.check_conditions(prob, inp, "ternary", dtype, ref=None if "l" in prob.fl or "g" in prob.fl or "G" in prob.fl else bufs["y"])
+        found = X.check_stat_conditions(prob, inp, bufs, dtype, spans, slot_of)
+    return bufs, found
+
+# what the launcher refuses: (Problem, rowspan) -- asserted as refusals on the CPU, never run
+STAT_REFUSALS = [
+    (Problem("s_ragged_m", 2, 320, 320, 24, 25, fl="bs", ksplit=1), 0),                      # CF_STATS needs whole 64-row blocks
+    (Problem("s_small_kernel", 2, 64, 128, 16, 16, fl="bs"), 0),                             # the small kernel has no CF_STATS epilogue
+    (Problem("s_halo_8x8", 32, 2560, 1280, 8, 8, fl="bs"), 0),                               # nor has the chunk-split form of the 8 x 8 level
+    (Problem("s_and_w_pps", 1, 1280, 640, 49152, 1, k=1, fl="bsw", ksplit=1), 80),           # one statistics epilogue per launch
+    (Problem("w_m512_too_few_work_items", 1, 320, 320, 512, 1, k=1, fl="brw", ksplit=1), 80),
+    (Problem("l_and_w_ws", 1, 320, 320, 33024, 1, k=1, fl="blw", ksplit=1), "ws"),           # no kernel honours the fold with row partials
+    (Problem("l_and_w_big", 1, 320, 320, 2048, 1, k=1, fl="blw", ksplit=1), 80),
+    (Problem("l_and_w_pps", 1, 320, 320, 49152, 1, k=1, fl="blw", ksplit=1), 80),
+]
+
+
 def record_problems():
     """{"big:case" | "pp:case": (Problem, salt, rowstat span | 0, plan | kind index)} for every case of the two bit records, in the flag
-    letters of exact_ref (G: GEGLU without the stash, l: CF_LNFOLD -- neither has a closed form for y)"""
+    letters of exact_ref (G: GEGLU without the stash, l: CF_LNFOLD -- on the records' lattice inputs neither has a closed form for y)"""
     out = {}
     for name, kind, B, H, shift, Cout, Cin, mode, fl in pp.CONV:
         f = "".join(c for c in fl if c in "brsu") + ("fn" if "f" in fl else "") + ("n" if "n" in fl else "")
@@ -144,17 +277,29 @@ def record_problems():
 
 
 def closed_form_outputs(prob):
-    """the outputs of a case that exact_ref derives: "raw" for the stash, "y" unless GELU or the LayerNorm fold is in it"""
+    """the outputs of a case that exact_ref derives on LATTICE inputs (the bit records): "raw" for the stash, "y" unless GELU or the
+    LayerNorm fold is in it (STAT_CASES derives every output, on ternary inputs)"""
     if "g" in prob.fl:
         return ["raw"]
     return [] if ("G" in prob.fl or "l" in prob.fl) else ["y"]
 
 
-def launch_args(ops, prob, dtype=torch.bfloat16, inp=None, dev="cpu", rowspan=0):
+def span_list(prob, rowspan):
+    """the column spans of a CF_ROWSTATS case: a list of widths as it is, one width for the whole row, "ws" for gemm_ws's 48 + 32"""
+    if rowspan == "ws":
+        return [48, 32] * (prob.N // 80)
+    return list(rowspan) if isinstance(rowspan, (list, tuple)) else [rowspan] * (prob.N // rowspan)
+
+
+def launch_args(ops, prob, dtype=torch.bfloat16, inp=None, dev="cpu", rowspan=0, bufs=None):
     """(pk, x, kw, out): the packed weights, the input rows and the keywords of ops.conv_gemm / ops.conv_gemm_plan for one case, and
     `out`, the WHOLE buffer that is compared (the output with its NaN-prefilled spare columns; the raw stash for "g").  inp = None (the
-    planner: it only tests pointers for null): buffers of the right shape that nobody reads."""
+    planner: it only tests pointers for null): buffers of the right shape that nobody reads.  bufs: a dict that receives EVERY whole
+    buffer of the launch under the names of exact_ref.expected_buffers ("y", "raw", "stats", "rowpart"): the statistics go into views of
+    NaN-prefilled wider buffers (partials: channels [64, 64 + N) of [M / 64, 64 + N, 2]; row partials: the first spans of
+    [M, spans + 3, 2])."""
     fl = prob.fl
+    bufs = {} if bufs is None else bufs
     full = (lambda shape, dt: torch.empty(shape, dtype=dt)) if inp is None else (lambda shape, dt: torch.full(shape, float("nan"), dtype=dt, device=dev))
     put = lambda t, dt: torch.empty(t, dtype=dt) if inp is None else t.to(dt).to(dev)
     w = torch.zeros((prob.Cout, prob.Cin, prob.k, prob.k)) if inp is None else inp["w"]
@@ -182,12 +327,21 @@ def launch_args(ops, prob, dtype=torch.bfloat16, inp=None, dev="cpu", rowspan=0)
         kw["res"] = put((M, ncols) if inp is None else inp["res"], torch.float32 if "R" in fl else dtype)
     if "m" in fl:
         kw["mask"] = put((M, ncols) if inp is None else inp["mask"], dtype)
+    bufs["y"] = ybuf
     if "g" in fl:
-        kw["raw"] = out = full((M, prob.N), dtype)
+        kw["raw"] = out = bufs["raw"] = full((M, prob.N), dtype)
     if "s" in fl:
-        kw["stats"] = full((M // 64, prob.N, 2), torch.float32)
+        bufs["stats"] = full((M // 64, X.STATS_PAD + prob.N, 2), torch.float32)
+        kw["stats"] = bufs["stats"][:, X.STATS_PAD:]
     if "w" in fl:
-        kw["rowpart"] = full((M, prob.N // rowspan, 2), torch.float32)
+        nspans = len(span_list(prob, rowspan))
+        bufs["rowpart"] = full((M, nspans + X.SPAN_PAD, 2), torch.float32)
+        kw["rowpart"] = bufs["rowpart"][:, :nspans]
+    if "l" in fl:
+        # the synthetic (mean, rstd) rows and c1 in the packed column order (a second PackedConv: it reuses the bias permutation)
+        kw["ln_stats"] = put((M, 2) if inp is None else inp["ln_stats"], torch.float32)
+        c1 = torch.zeros(prob.N) if inp is None else X.ln_c1(inp)
+        kw["ln_c1"] = ops.PackedConv(w, prob.pad, geglu="g" in fl or "G" in fl, bias=c1, device=dev, dtype=dtype).bias
     return pk, x, kw, out
 
 

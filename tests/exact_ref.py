@@ -14,10 +14,20 @@ Two input families:
 A Problem names the FORWARD convolution (a pointwise GEMM is B = 1, H = M, W = 1, k = 1); dgrad = True is its input gradient (packing
 mode 1: Cout -> Cin channels at the forward input's logical size, F.conv_transpose2d).  check_conditions() asserts what the argument
 above needs before anything is compared.
+
+On the ternary family the statistics epilogues, the LayerNorm fold and GEGLU have closed forms too (expected_buffers; conditions in
+check_stat_conditions).  CF_STATS: plain sums a, q of the integers of a 64-row block, mean = a / 64, M2 = max(q - a * mean, 0), exact
+while a^2 and q stay below 2^24.  CF_ROWSTATS: (sum, sum of squares) over a wave's column span.  CF_LNFOLD: the kernels only read
+(mean, rstd), so the test supplies small integer means and power-of-two rstd, and alpha * rstd * (acc - mean * c1) + b' is one exact
+number in either spelling the kernels use.  GEGLU: gelu_poly_f is a clamp, multiplications and fmas; each is formed exactly here and
+rounded once (gelu_phi), on a table of the multiples of 1 / 8 inside the clamp.  The lattice family has none of these: its squares are
+not exact.
 """
 import collections
+import fractions
 import hashlib
 import os
+import re
 import sys
 
 import torch
@@ -27,9 +37,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "gol
 from make_pingpong_bits import lattice  # noqa: E402
 
 # flags: b bias, r 16-bit residual, R fp32 residual, u ReLU, m mask, f fp32 output, n output into NaN-prefilled 8-wide rows,
-#        g GEGLU with the raw stash, a alpha = 0.5, v strided x / y views (64 / 32 columns wider), s CF_STATS and w CF_ROWSTATS buffers
-#        (their contents have no closed form; y has); G GEGLU without the stash and l CF_LNFOLD appear in the bit records only (no closed
-#        form for y)
+#        g GEGLU with the raw stash, G GEGLU without it, a alpha = 0.5, v strided x / y views (64 / 32 columns wider), s CF_STATS and
+#        w CF_ROWSTATS buffers, l CF_LNFOLD.
+# s, w, l, G and the y of g have closed forms on the TERNARY family only (expected_stats, expected_rowpart, fold(), geglu_product()): the
+# sums of squares of the lattice family (units of 1 / 2^20) are not exact in fp32, and neither are its folded or gated values, so on lattice
+# inputs -- the bit records -- those outputs are not derived here.
 _Problem = collections.namedtuple("Problem", "name B Cin Cout H W k stride pad up dgrad fl ksplit")
 
 
@@ -112,7 +124,8 @@ def lattice_denominators(prob):
 
 def make_inputs(prob, family, salt=0):
     """{"w": OIHW fp32, "bias": [N] | None, "x": rows [M_in, pad8(channels)], "res": rows [M, ncols] | None, "mask": rows | None,
-    "dx", "dw", "db": the denominators of x, of w and of bias / res}.  lattice with salt = 16 * (case index) is the input of the bit records."""
+    "dx", "dw", "db": the denominators of x, of w and of bias / res, "ln_stats": [M, 2] (mean, rstd) with "l" (ternary only) | None}.
+    lattice with salt = 16 * (case index) is the input of the bit records."""
     ih, iw = prob.in_hw
     m_in, cin = prob.B * ih * iw, pad8(prob.in_ch)
     wshape = (prob.Cout, prob.Cin, prob.k, prob.k)
@@ -136,7 +149,24 @@ def make_inputs(prob, family, salt=0):
         mask = _integers((prob.M, prob.ncols), 2, g) if "m" in prob.fl else None
     if cin != prob.in_ch:
         x[:, prob.in_ch:] = 0
-    return dict(w=w, bias=bias, x=x, res=res, mask=mask, dx=dx, dw=dw, db=16 if family == "lattice" else 1)
+    ln_stats = None
+    if "l" in prob.fl:
+        # the kernels only READ ln_stats[m] = (mean, rstd): small integer means and power-of-two rstd keep rstd * (acc - mean * c1) + b' one
+        # exact real number in both spellings of the fold (a generator of its own: the other operands do not depend on the flag)
+        assert family == "ternary" and prob.k == 1 and not prob.dgrad
+        g2 = torch.Generator().manual_seed(5000 + salt)
+        mean = torch.randint(LN_MEAN[0], LN_MEAN[1] + 1, (prob.M,), generator=g2).float()
+        rstd = torch.tensor(LN_RSTD)[torch.randint(0, len(LN_RSTD), (prob.M,), generator=g2)]
+        ln_stats = torch.stack([mean, rstd], dim=1)
+    return dict(w=w, bias=bias, x=x, res=res, mask=mask, dx=dx, dw=dw, db=16 if family == "lattice" else 1, ln_stats=ln_stats)
+
+
+LN_MEAN, LN_RSTD = (-3, 3), (0.25, 0.5, 1.0, 2.0)
+
+
+def ln_c1(inp):
+    """CF_LNFOLD: the column sums of the (folded) weights in natural column order; the packer permutes them for GEGLU"""
+    return inp["w"].sum(dim=(1, 2, 3))
 
 
 GEGLU_PERM_CACHE = {}
@@ -168,12 +198,26 @@ def accumulate(prob, x_rows, w, mutant=None):
     return y.permute(0, 2, 3, 1).reshape(prob.M, prob.N)
 
 
-def epilogue(prob, acc, inp):
-    """fp32 rows before the one rounding: mask(relu(alpha * acc + bias + res)); with "g" the pre-activations in packed column order"""
-    v = acc * prob.alpha if prob.alpha != 1.0 else acc
+def epilogue(prob, acc, inp, mutant=None):
+    """fp32 rows before the one rounding: mask(relu(alpha * fold(acc) + bias + res)), fold(acc) = rstd[m] * (acc - mean[m] * c1[n]) with
+    "l"; with "g" / "G" the pre-activations in packed column order (geglu_product() makes y of them).  mutant: see STAT_MUTANTS"""
+    v = acc
+    if "l" in prob.fl:
+        st, c1 = inp["ln_stats"], ln_c1(inp)
+        if mutant == "ln_stats_of_the_neighbouring_row":
+            st = st.clone()
+            tail = torch.arange(prob.M - 64, prob.M)
+            st[tail] = inp["ln_stats"][tail ^ 1]
+        if mutant == "c1_in_natural_order":          # the kernel indexes c1 by PACKED column: natural values at packed positions
+            assert "g" in prob.fl or "G" in prob.fl
+            inv = torch.empty(prob.N, dtype=torch.long)
+            inv[geglu_perm(prob.N)] = torch.arange(prob.N)
+            c1 = c1[inv]                             # natural column perm[q] gets c1[q]
+        v = st[:, 1:2] * (v - st[:, 0:1] * c1[None, :])
+    v = v * prob.alpha if prob.alpha != 1.0 else v
     if inp["bias"] is not None:
         v = v + inp["bias"][None, :]
-    if "g" in prob.fl:
+    if "g" in prob.fl or "G" in prob.fl:
         return v[:, geglu_perm(prob.N)]
     if inp["res"] is not None:
         v = v + inp["res"]
@@ -206,6 +250,230 @@ def finish(prob, acc, inp, dtype=torch.bfloat16):
 
 def expected(prob, inp, dtype=torch.bfloat16, mutant=None):
     return finish(prob, accumulate(prob, inp["x"], inp["w"], mutant), inp, dtype)
+
+
+# ---- the statistics epilogues, the LayerNorm fold and GEGLU on the ternary family -----------------------------------------------------
+
+def _round32(fr):
+    """a Fraction rounded to the nearest fp32 (ties to even), as a Fraction; normal range only"""
+    if fr == 0:
+        return fr
+    e = 0
+    a = abs(fr)
+    while a >= (1 << 24):
+        a /= 2
+        e += 1
+    while a < (1 << 23):
+        a *= 2
+        e -= 1
+    assert e >= -149, "subnormal"
+    return (round(a) * fractions.Fraction(2) ** e) * (1 if fr > 0 else -1)          # round(Fraction) rounds half to even
+
+
+def gelu_literals():
+    """(clamp, the ten coefficients) of gelu_poly_f, read from distdiff_amd/csrc/common.h as tests/test_oracle.py::test_gelu_polynomial does"""
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "distdiff_amd", "csrc", "common.h")).read()
+    clamp = float(re.search(r"#define\s+DD_GELU_CLAMP\s+([0-9.]+)f", src).group(1))
+    body = re.search(r"#define\s+DD_GELU_POLY\s*\{(.*?)\}", src, re.S).group(1).replace("\\", " ")
+    c = [float(torch.tensor(float(v.strip().rstrip("f")), dtype=torch.float32)) for v in body.split(",")]
+    assert len(c) == 10
+    return clamp, c
+
+
+_PHI = {}
+
+
+def gelu_phi(t):
+    """Phi~(t) of gelu_poly_f for one clamped gate value t (a float that is exact in fp32): u = t * t, nine fmas, fma(t, p, 0.5), every
+    operation formed exactly (fractions.Fraction; math.fma where Python has it gives the same) and rounded once to fp32"""
+    if t not in _PHI:
+        if "lit" not in _PHI:
+            _PHI["lit"] = gelu_literals()
+        clamp, c = _PHI["lit"]
+        assert abs(t) <= clamp
+        Fr = fractions.Fraction
+        ft = Fr(t)
+        u = _round32(ft * ft)
+        p = Fr(c[9])
+        for k in range(8, -1, -1):
+            p = _round32(p * u + Fr(c[k]))
+        _PHI[t] = float(_round32(ft * p + Fr(1, 2)))
+    return _PHI[t]
+
+
+GATE_LATTICE = 8            # the gate table: the multiples of 1 / 8 inside the clamp (integers; quarters under "l", eighths with alpha = 0.5)
+
+
+def gate_table():
+    """(clamp, Phi~ of every multiple of 1 / 8 in [-clamp, clamp] as fp32)"""
+    if "table" not in _PHI:
+        clamp = gelu_literals()[0]
+        n = int(clamp * GATE_LATTICE)
+        assert n == clamp * GATE_LATTICE
+        _PHI["table"] = clamp, torch.tensor([gelu_phi(i / GATE_LATTICE) for i in range(-n, n + 1)], dtype=torch.float32)
+    return _PHI["table"]
+
+
+def gelu_exact(g):
+    """gelu_poly_f on fp32 gates of the table's lattice: g * Phi~(clamp(g)), one fp32 rounding per operation (the product of two fp32
+    numbers is exact in float64)"""
+    clamp, table = gate_table()
+    t = g.clamp(-clamp, clamp)
+    idx = (t + clamp) * GATE_LATTICE
+    assert torch.equal(idx, torch.round(idx)), "gate values outside the table (not multiples of 1 / %d)" % GATE_LATTICE
+    return (g.double() * table[idx.long()].double()).float()
+
+
+def geglu_product(prob, v, mutant=None):
+    """y rows [M, N / 2] in fp32 of the packed pre-activations v (16 hidden | 16 gate columns per group of 32): round32(h * gelu_poly(g)).
+    A zero keeps the sign of the product (a negative hidden value times gelu(0) = +0 is -0, and the kernels store that)"""
+    M = v.shape[0]
+    grp = v.reshape(M, prob.N // 32, 2, 16)
+    h, g = grp[:, :, 0], grp[:, :, 1]
+    if mutant == "last_gate_group_with_the_previous_hidden":
+        h = h.clone()
+        h[:, -1] = h[:, -2]
+    return (h.double() * gelu_exact(g).double()).float().reshape(M, prob.N // 2)
+
+
+def halo_tile_width(prob):
+    """the halo kernels' tile width: the largest power-of-two factor of the output width (capped at 64 or 128 by the tile form; below 64
+    the cap does not matter)"""
+    wo = prob.out_hw[1]
+    return wo & -wo
+
+
+def slots_m64(prob):
+    """CF_STATS slot of every output row: m >> 6 (every kernel but the narrow-tile halo forms)"""
+    return torch.arange(prob.M) >> 6
+
+
+def slots_halo(prob):
+    """CF_STATS slot of every output row on the halo kernels: with tiles narrower than 64 pixels a block is 64 / tw image rows by tw
+    pixels, slot (image's first row >> 6) + (oy // (64 / tw)) * tiles_x + ox // tw; from 64 pixels on it is m >> 6"""
+    tw = halo_tile_width(prob)
+    if tw >= 64:
+        return slots_m64(prob)
+    oh, ow = prob.out_hw
+    m = torch.arange(prob.M)
+    img, oy, ox = m // (oh * ow), (m // ow) % oh, m % ow
+    return (img * oh * ow >> 6) + (oy // (64 // tw)) * (ow // tw) + ox // tw
+
+
+def _block_sums(v, slot_of, mutant=None):
+    """(a, q): [slots, N] float64 sums and sums of squares of the 64 rows of every slot"""
+    M, N = v.shape
+    nslots = M // 64
+    assert M % 64 == 0 and torch.equal(torch.bincount(slot_of, minlength=nslots), torch.full((nslots,), 64)), "the slot map is not one-to-one"
+    order = torch.argsort(slot_of, stable=True)
+    blocks = v[order].double().reshape(nslots, 64, N)
+    if mutant == "last_row_of_a_block_twice":
+        blocks = blocks.clone()
+        blocks[:, 62] = blocks[:, 63]
+    return blocks.sum(1), (blocks * blocks).sum(1), order
+
+
+def expected_stats(prob, v, slot_of, mutant=None):
+    """CF_STATS: [M / 64, N, 2] fp32 (mean, M2) of the 64 rows of every slot, formed in fp32 as the emitters do: a = sum v, q = sum v^2,
+    mean = a * (1 / 64), M2 = max(q - a * mean, 0).  v: epilogue()'s rows; slot_of: slots_m64 / slots_halo"""
+    a64, q64, order = _block_sums(v, slot_of, mutant)
+    a, q = a64.float(), q64.float()
+    mean = a * (1.0 / 64.0)
+    m2 = (q - a * mean).clamp_min(0)
+    out = torch.stack([mean, m2], dim=2) + 0.0
+    if mutant == "narrow_halo_tile_in_slot_m64":       # each block's partials land in slot (its first row >> 6): collisions, holes stay NaN
+        first = order.reshape(-1, 64).min(1).values >> 6
+        moved = torch.full_like(out, float("nan"))
+        moved[first] = out
+        return moved
+    return out
+
+
+def expected_rowpart(prob, v, spans, mutant=None):
+    """CF_ROWSTATS: [M, len(spans), 2] fp32 (sum v, sum v^2) of every row over consecutive column spans of the given widths"""
+    assert sum(spans) == v.shape[1] and "g" not in prob.fl and "G" not in prob.fl
+    parts = torch.split(v.double(), list(spans), dim=1)
+    out = torch.stack([torch.stack([p.sum(1), (p * p).sum(1)], dim=1) for p in parts], dim=1).float()
+    if mutant == "span_sums_in_the_neighbouring_span":
+        out = out[:, torch.arange(len(spans)) ^ 1]
+    return out
+
+
+STATS_PAD, SPAN_PAD = 64, 3      # channels in front of the op's range in the partials buffer; spare span slots behind the op's spans
+
+
+def expected_buffers(prob, acc, inp, dtype=torch.bfloat16, spans=None, slot_of=None, mutant=None):
+    """{"y", "raw", "stats", "rowpart"}: every WHOLE buffer the launch of tests/conv_exact_cases.py::launch_args leaves, NaN wherever the
+    kernel must not write, and "v", the fp32 rows the statistics are taken of.  stats: [M / 64, 64 + N, 2] with the partials in channels
+    [64, 64 + N); rowpart: [M, len(spans) + 3, 2]"""
+    fl = prob.fl
+    nan = lambda shape, dt: torch.full(shape, float("nan"), dtype=dt)
+    v = epilogue(prob, acc, inp, mutant)
+    out = dict(v=v)
+    dt = store_dtype(prob, dtype)
+    if "g" in fl or "G" in fl:
+        yrows = geglu_product(prob, v, mutant)
+        if "g" in fl:
+            out["raw"] = v.to(dtype)
+        out["y"] = yrows.to(dt)
+    else:
+        out["y"] = nan((prob.M, stored_width(prob)), dt)
+        out["y"][:, :v.shape[1]] = v.to(dt)
+    if "s" in fl:
+        sv = epilogue(prob._replace(fl=fl.replace("u", "")), acc, inp) if mutant == "stats_in_front_of_the_relu" else v
+        out["stats"] = nan((prob.M // 64, STATS_PAD + prob.N, 2), torch.float32)
+        out["stats"][:, STATS_PAD:STATS_PAD + prob.N] = expected_stats(prob, sv, slot_of, mutant)
+    if "w" in fl:
+        out["rowpart"] = nan((prob.M, len(spans) + SPAN_PAD, 2), torch.float32)
+        out["rowpart"][:, :len(spans)] = expected_rowpart(prob, v, spans, mutant)
+    return out
+
+
+# mutants of the statistics / fold / GEGLU epilogues (expected_buffers(mutant=...)): name, the flags a case needs, a further condition
+STAT_MUTANTS = (
+    ("last_row_of_a_block_twice", "s", lambda p: True),
+    ("stats_in_front_of_the_relu", "su", lambda p: True),
+    ("narrow_halo_tile_in_slot_m64", "s", lambda p: p.k == 3 and halo_tile_width(p) < 64 and p.out_hw[1] // halo_tile_width(p) > 1),
+    ("ln_stats_of_the_neighbouring_row", "l", lambda p: True),
+    ("c1_in_natural_order", "l", lambda p: "g" in p.fl or "G" in p.fl),
+    ("last_gate_group_with_the_previous_hidden", "", lambda p: "g" in p.fl or "G" in p.fl),
+    ("span_sums_in_the_neighbouring_span", "w", lambda p: True),
+)
+
+
+def check_stat_conditions(prob, inp, bufs, dtype=torch.bfloat16, spans=None, slot_of=None):
+    """What the closed forms of the statistics outputs need, asserted per case (ternary): returns the bounds found"""
+    fl, v = prob.fl, bufs["v"]
+    found = {}
+    lattice = 1 if "l" not in fl else (8 if "a" in fl else 4)
+    if "a" in fl and "l" not in fl:
+        lattice = 2
+    assert torch.equal(v * lattice, torch.round(v * lattice)), "%s: v is not on the lattice 1 / %d" % (prob.name, lattice)
+    found["max|v|"] = float(v.abs().max())
+    assert found["max|v|"] * lattice < (1 << 24)
+    if "l" in fl:
+        st, c1 = inp["ln_stats"], ln_c1(inp)
+        assert torch.equal(st[:, 0], torch.round(st[:, 0])) and LN_MEAN[0] <= st[:, 0].min() and st[:, 0].max() <= LN_MEAN[1]
+        assert all(float(r) in LN_RSTD for r in st[:, 1].unique())
+        # acc - mean * c1 is an integer below 2^24; rstd a power of two: exact in both spellings of the fold
+        bound = prob.depth + LN_MEAN[1] * float(c1.abs().max())
+        assert bound * max(LN_RSTD) * 8 < (1 << 24)
+        found["fold bound"] = bound
+    if "g" in fl or "G" in fl:
+        g = v.reshape(prob.M, prob.N // 32, 2, 16)[:, :, 1]
+        assert torch.equal(g * GATE_LATTICE, torch.round(g * GATE_LATTICE)), "%s: gates outside the table" % prob.name
+        found["max|gate|"] = float(g.abs().max())
+    if "s" in fl:
+        assert lattice == 1 and torch.equal(v.to(dtype).float(), v), "%s: v is not exact in the stored format" % prob.name
+        a, q, _o = _block_sums(v, slot_of)
+        found["max|a|"], found["max q"] = float(a.abs().max()), float(q.max())
+        assert found["max|a|"] ** 2 < (1 << 24) and found["max q"] < (1 << 24), (prob.name, found)
+    if "w" in fl:
+        assert lattice <= 2
+        rp = expected_rowpart(prob, v, spans).double()
+        found["max|span sum|"], found["max span sum of squares"] = float(rp[:, :, 0].abs().max()), float(rp[:, :, 1].max())
+        assert found["max|span sum|"] * lattice < (1 << 24) and found["max span sum of squares"] * lattice * lattice < (1 << 24), (prob.name, found)
+    return found
 
 
 def mutant_rows(prob, inp, mutant):
@@ -246,12 +514,22 @@ def digest(t):
 
 def mismatch_report(prob, got, want, tile_rows=256):
     """None if got and want hold the same bits (NaN prefill included), else a text: the count of wrong elements, the first eight as
-    (image, oy, ox, n) with got / want, whether all lie on an image border, their row index modulo the tile height"""
+    (image, oy, ox, n) with got / want, whether all lie on an image border, their row index modulo the tile height; for a statistics
+    buffer (three dimensions) the first eight as (block, channel) or (row, span) and which of the pair"""
     got, want = got.cpu(), want.cpu()
     assert got.shape == want.shape and got.dtype == want.dtype, (prob.name, got.shape, want.shape, got.dtype, want.dtype)
     if torch.equal(bits(got), bits(want)):
         return None
     bad = (bits(got) != bits(want)).nonzero()
+    if got.dim() == 3:       # a statistics buffer [blocks | rows, channels | spans, 2]
+        what = ("row", "span") if got.shape[0] == prob.M else ("block", "channel")
+        lines = ["%s: %d of %d statistics differ (%d %ss, %d %ss touched)"
+                 % (prob.name, len(bad), got.numel(), bad[:, 0].unique().numel(), what[0], bad[:, 1].unique().numel(), what[1])]
+        for r, c, e in bad[:8].tolist():
+            lines.append("  (%s %d, %s %d, %s): got %r want %r" % (what[0], r, what[1], c, ("first", "second")[e], float(got[r, c, e]), float(want[r, c, e])))
+        lines.append("  %ss: %s%s" % (what[0], bad[:, 0].unique().tolist()[:16], " ..." if bad[:, 0].unique().numel() > 16 else ""))
+        lines.append("  %ss: %s%s" % (what[1], bad[:, 1].unique().tolist()[:16], " ..." if bad[:, 1].unique().numel() > 16 else ""))
+        return "\n".join(lines)
     oh, ow = prob.out_hw
     rows, cols = bad[:, 0], bad[:, 1]
     oy, ox = (rows // ow) % oh, rows % ow

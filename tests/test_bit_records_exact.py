@@ -19,7 +19,11 @@ import make_pingpong_bits as pp  # noqa: E402
 
 ORDER = "depends on the order of summation or holds quantities fp32 does not represent exactly"
 ACT = "depends on rstd / GELU"
-# outputs of the two records without a closed form: {"record:case/output": reason}
+# outputs of the two records without a closed form ON THE RECORDS' INPUTS: {"record:case/output": reason}.  The reason is the lattice, not
+# the outputs: sums of squares of multiples of 1 / 1024 are not exact in fp32, and the (mean, rstd) rows of the recorded folds are those
+# of the lattice rows, so their products are rounded.  On ternary inputs with synthetic (mean, rstd) the same outputs (partials, row
+# partials, the folded and the GEGLU y) are compared bit for bit by tests/test_conv_exact_gpu.py::test_conv_gemm_stat_outputs_exact;
+# the split-K partial buffers stay what they are, scratch whose layout is the kernel's own.
 NO_CLOSED_FORM = {
     "big:f4_stats/stats": ORDER, "big:f1_ragged_n_tile_stats/stats": ORDER, "big:f5_3x3_stride2_fast_padding_taps_stats/stats": ORDER,
     "big:f4_rowstats/rowpart": ORDER, "big:f5_rowstats/rowpart": ORDER,

@@ -2,8 +2,14 @@
 what the exact comparison sees that the tolerance test does not.
 
 dd_op_conv_gemm_plan tests pointers for null and reads no device, so routing drift of the cases of tests/test_conv_exact_gpu.py fails
-here, without a GPU, for both libraries.  Coverage: every distinct non-refused (kind, form, narrow, split > 1) among the recorded outcomes
-of tests/golden/conv_plan_table.npz for problems without CF_STATS / CF_LNFOLD / CF_ROWSTATS is the plan of at least one exact case.
+here, without a GPU, for both libraries.  Coverage: every distinct non-refused (kind, form, narrow, split > 1, CF_STATS, CF_ROWSTATS,
+CF_LNFOLD, GEGLU) among the recorded outcomes of tests/golden/conv_plan_table.npz is the plan of at least one exact case of CASES or
+STAT_CASES; the list of combinations without a closed form is asserted whole and is empty.  What the launcher must refuse of the
+statistics flags is asserted as refused.
+
+Seven more mutants (exact_ref.STAT_MUTANTS) stand for faults of the statistics, fold and GEGLU epilogues; each must show in the exact
+comparison of the whole buffers on every case it applies to, and what the tolerance tests of tests/test_kernels_gpu.py make of the same
+mutant on their own kind of inputs is printed beside it.
 
 Sensitivity: three mutants of the reference (tests/exact_ref.py: one 8-channel vector of one tap dropped at the last image column, two
 taps swapped, the first 64-channel chunk used twice) must show as mismatches of the exact comparison on every ternary case they apply to;
@@ -16,6 +22,7 @@ import math
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 import conv_exact_cases as T
 import conv_plan_cases as plan_cases
@@ -42,21 +49,36 @@ def raw_plan(ops, prob, dtype=torch.bfloat16, rowspan=0):
 
 def test_case_names_are_unique():
     assert len(set(T.NAMES)) == len(T.NAMES)
+    assert len(set(T.STAT_NAMES)) == len(T.STAT_NAMES) and not set(T.STAT_NAMES) & set(T.NAMES)
 
 
 def test_every_case_plans_as_stated(ops):
     bad = []
-    for prob, plan, f16 in T.CASES:
+    for prob, plan, f16, rowspan in [c + (0,) for c in T.CASES] + [c[:4] for c in T.STAT_CASES]:
         for dtype in (torch.bfloat16, torch.float16) if f16 else (torch.bfloat16,):
-            got = T.plan_of(ops, prob, dtype)
+            try:
+                got = T.plan_of(ops, prob, dtype, rowspan=rowspan)
+            except RuntimeError as e:
+                got = "refused (%s)" % e
             if got != plan:
                 bad.append("%s (%s): planned %s, the case is about %s" % (prob.name, dtype, got, plan))
     assert not bad, "\n".join(bad)
 
 
+def test_statistics_refusals_are_refused(ops):
+    """what the launcher must refuse is asserted here and never launched"""
+    for prob, rowspan in T.STAT_REFUSALS:
+        for dtype in (torch.bfloat16, torch.float16):
+            with pytest.raises(RuntimeError, match="refuses"):
+                T.plan_of(ops, prob, dtype, rowspan=rowspan)
+
+
 def test_every_kind_and_form_runs_on_the_fp16_library():
     want = {(k, f) for _p, (k, f, _s), _h in T.CASES if "goes_general" not in _p.name}
     assert {(k, f) for _p, (k, f, _s), h in T.CASES if h} == want
+    kind_of = lambda p: "".join(sorted(c for c in p.fl.replace("G", "g") if c in "swlg"))
+    want = {(k, f, kind_of(p)) for p, (k, f, _s), *_r in T.STAT_CASES}
+    assert {(k, f, kind_of(p)) for p, (k, f, _s), h, *_r in T.STAT_CASES if h} >= {w for w in want if len(w[2]) == 1}     # one per form and statistics kind
 
 
 def test_record_cases_plan_as_their_records_state(ops):
@@ -76,15 +98,25 @@ def test_table_covers_every_recorded_plan(ops):
     want = t["outcomes"][t["index"]]
     assert len(rows) == len(want)
     flags = rows[:, plan_cases.COL["flags"]]
-    keep = (want[:, 0] >= 0) & ((flags & (plan_cases.STATS | plan_cases.LNFOLD | plan_cases.ROWSTATS)) == 0)
-    w = want[keep].astype(np.int64)
-    need = set(map(tuple, np.unique(np.stack([w[:, 0], w[:, 1], w[:, 3], (w[:, 2] > 1).astype(np.int64)], axis=1), axis=0).tolist()))
-    assert len(need) >= 19, sorted(need)
+    # an empty problem (M <= 0 or N <= 0) is accepted and launches nothing: no kernel, no output, nothing to compare
+    keep = (want[:, 0] >= 0) & (rows[:, plan_cases.COL["M"]] > 0) & (rows[:, plan_cases.COL["N"]] > 0)
+    w, f = want[keep].astype(np.int64), flags[keep]
+    bit = lambda b: ((f & b) != 0).astype(np.int64)
+    key = np.stack([w[:, 0], w[:, 1], w[:, 3], (w[:, 2] > 1).astype(np.int64), bit(plan_cases.STATS), bit(plan_cases.ROWSTATS), bit(plan_cases.LNFOLD),
+                    bit(plan_cases.GEGLU)], axis=1)
+    need = set(map(tuple, np.unique(key, axis=0).tolist()))
+    assert len(need) >= 60, sorted(need)
     have = set()
-    for prob, _plan, _f16 in T.CASES:
-        kind, form, split, narrow = raw_plan(ops, prob)
-        have.add((kind, form, narrow, int(split > 1)))
-    assert not need - have, "recorded (kind, form, narrow, split > 1) that no exact case runs: %s" % sorted(need - have)
+    for prob, rowspan in [(c[0], 0) for c in T.CASES] + [(c[0], c[3]) for c in T.STAT_CASES]:
+        kind, form, split, narrow = raw_plan(ops, prob, rowspan=rowspan)
+        fl = prob.fl
+        have.add((kind, form, narrow, int(split > 1), int("s" in fl), int("w" in fl), int("l" in fl), int("g" in fl or "G" in fl)))
+    assert NO_CLOSED_FORM == [], "every statistics, fold and GEGLU output has a closed form on ternary inputs"
+    missing = need - have - set(NO_CLOSED_FORM)
+    assert not missing, "recorded (kind, form, narrow, split > 1, stats, rowstats, lnfold, geglu) that no exact case runs: %s" % sorted(missing)
+
+
+NO_CLOSED_FORM = []      # recorded combinations that cannot be compared exactly: none
 
 
 def _one_image(prob):
@@ -161,6 +193,149 @@ def test_dropped_vector_passes_the_tolerance_test_at_k23040():
     assert all(e > noise for e in errs)
     assert any(e <= lim for e in errs), "no dropped vector passes the tolerance test any more: %r against %.4f" % (errs, lim)
     assert wrong > 1000
+
+
+# ---- the statistics / fold / GEGLU outputs: mutants of the reference, and what the tolerance tests make of them ----------------------
+
+def _gaussian_inputs(prob):
+    """operands of the kind tests/test_kernels_gpu.py draws for a GEMM case (test_layernorm_folded_into_linear under "l", else
+    test_linear_emits_layernorm_row_partials / test_conv_emits_groupnorm_partials), and the rows' own (mean, rstd)"""
+    g = torch.Generator().manual_seed(77)
+    bf = lambda t: t.to(torch.bfloat16).float()
+    M, K, N = prob.M, prob.Cin, prob.N
+    x = bf(torch.randn(M, K, generator=g) * 1.7 + torch.randn(M, 1, generator=g) * 0.8) if "l" in prob.fl else bf(torch.randn(M, K, generator=g))
+    w = torch.randn(N, K, generator=g) / math.sqrt(K)
+    if "l" in prob.fl:
+        w = w * (1.0 + 0.3 * torch.randn(K, generator=g))[None, :]
+    res = bf(torch.randn(M, N, generator=g)) if "r" in prob.fl else None
+    st = torch.stack([x.mean(1), (x.var(1, unbiased=False) + 1e-5).rsqrt()], dim=1)
+    return dict(x=x, w=bf(w)[:, :, None, None], bias=torch.randn(N, generator=g), res=res, mask=None, ln_stats=st)
+
+
+def _tolerance_view(name):
+    """(largest error, limit, note): what the assertion of tests/test_kernels_gpu.py that guards the mutant's output computes for it on
+    that test's kind of Gaussian inputs (limit = atol + rtol * max|ref|, its assert_close); None, None and a fact where the test has no
+    assertion that could see the mutant"""
+    close = lambda got, ref, rtol, atol: (float((got - ref).abs().max()), atol + rtol * float(ref.abs().max()))
+    if name in ("last_row_of_a_block_twice", "stats_in_front_of_the_relu"):
+        prob = X.Problem("gauss", 1, 320, 320, 4096, 1, k=1, fl="brus" if "relu" in name else "brs")
+        inp = _gaussian_inputs(prob)
+        acc = X.accumulate(prob, inp["x"], inp["w"])
+        slot_of = X.slots_m64(prob)
+        ref = X.expected_stats(prob, X.epilogue(prob, acc, inp), slot_of)
+        sv = X.epilogue(prob._replace(fl="brs"), acc, inp) if "relu" in name else X.epilogue(prob, acc, inp)
+        mut = X.expected_stats(prob, sv, slot_of, name if "relu" not in name else None)
+        e1, l1 = close(mut[:, :, 0], ref[:, :, 0], 2e-3, 2e-3)
+        e2, l2 = close(mut[:, :, 1], ref[:, :, 1], 2e-2, 2e-2)
+        note = "partial mean %.4f against %.4f, partial M2 %.3f against %.3f" % (e1, l1, e2, l2)
+        if "relu" in name:
+            note += " (and test_conv_emits_groupnorm_partials has no case with a ReLU)"
+        return max(e1 / l1, e2 / l2), 1.0, note
+    if name == "narrow_halo_tile_in_slot_m64":
+        import test_kernels_gpu as K
+        narrow = [c[0] for c in K.STATS_CASES if K.STATS_PLANS[c[0]][0].startswith("conv_halo") and X.halo_tile_width(X.Problem(c[0], *c[1:6])) < 64
+                  and c[5] // X.halo_tile_width(X.Problem(c[0], *c[1:6])) > 1]
+        return None, None, ("%d of the cases of test_conv_emits_groupnorm_partials that run a halo kernel have several tiles narrower than 64 pixels per "
+                            "image row: the block map never runs there" % len(narrow))
+    if name == "span_sums_in_the_neighbouring_span":
+        return 0.0, None, "test_linear_emits_layernorm_row_partials and test_weight_stationary_gemm sum the partials over the spans: a permutation of spans changes nothing they look at"
+    geglu = name != "ln_stats_of_the_neighbouring_row"
+    fl = "bG" if name == "last_gate_group_with_the_previous_hidden" else ("bGl" if geglu else "bl")
+    prob = X.Problem("gauss", 1, 320, 2560 if geglu else 960, 1500 if fl == "bG" else 4096, 1, k=1, fl=fl)
+    inp = _gaussian_inputs(prob)
+    acc = X.accumulate(prob, inp["x"], inp["w"])
+
+    def y(mutant):
+        v = X.epilogue(prob, acc, inp, mutant)
+        if not geglu:
+            return v
+        grp = v.reshape(prob.M, prob.N // 32, 2, 16)
+        h, gate = grp[:, :, 0].clone(), grp[:, :, 1]
+        if mutant == "last_gate_group_with_the_previous_hidden":
+            h[:, -1] = h[:, -2]
+        return (h * F.gelu(gate)).reshape(prob.M, prob.N // 2)
+    err, lim = close(y(name), y(None), 1.5e-2, 2e-2 if "l" in fl else 1e-3)
+    return err, lim, "largest error %.4f against the limit %.4f" % (err, lim)
+
+
+def test_mutants_of_the_statistics_outputs_show_on_every_case():
+    """Seven mutants of the reference's statistics, fold and GEGLU epilogues (exact_ref.STAT_MUTANTS), each on every case of STAT_CASES it
+    applies to, cut to one image or 4096 rows: the exact comparison of the whole buffers must see every one.  What the tolerance tests
+    of tests/test_kernels_gpu.py compute for the same mutant on their kind of inputs is printed beside it, not asserted."""
+    quiet, applied = [], {name: 0 for name, _fl, _a in X.STAT_MUTANTS}
+    for i, (prob, _plan, _f16, rowspan, slots) in enumerate(T.STAT_CASES):
+        prob = _one_image(prob)
+        muts = [name for name, need, applies in X.STAT_MUTANTS if all(c in prob.fl for c in need) and applies(prob)
+                and (slots == "halo" or name != "narrow_halo_tile_in_slot_m64")]          # the block map is the halo kernels'
+        if not muts:
+            continue
+        inp = X.make_inputs(prob, "ternary", i)
+        acc = X.accumulate(prob, inp["x"], inp["w"])
+        want, _found = T.stat_expected(prob, acc, inp, torch.bfloat16, rowspan, slots)
+        for name in muts:
+            applied[name] += 1
+            got, _f = T.stat_expected(prob, acc, inp, torch.bfloat16, rowspan, slots, mutant=name, check=False)
+            if all(X.mismatch_report(prob, got[k], want[k]) is None for k in want if k != "v"):
+                quiet.append((prob.name, name))
+    print("statistics mutants applied (cases): %s" % applied)
+    for name, _fl, _a in X.STAT_MUTANTS:
+        err, lim, note = _tolerance_view(name)
+        verdict = "no assertion looks" if lim is None else ("inside its limit" if err <= lim else "outside its limit")
+        print("  %s: exact comparison sees it on %d of %d cases; tolerance test: %s -- %s" % (name, applied[name] - sum(n == name for _p, n in quiet), applied[name], verdict, note))
+    assert not quiet, "mutants the exact comparison did not see: %s" % quiet
+    assert min(applied.values()) >= 2, applied
+
+
+def test_gelu_emulation_equals_the_oracle_evaluation_on_the_gate_table():
+    """exact_ref's gelu (every fma formed exactly, rounded once) against the evaluation of tests/test_oracle.py::test_gelu_polynomial
+    (float64 product and sum, then one rounding to fp32: a double rounding) on the multiples of 1 / 8 inside the clamp: where the two
+    differ it is printed, and the exact one is what the GPU comparison uses"""
+    clamp, c = X.gelu_literals()
+    _clamp, table = X.gate_table()
+    t = np.arange(-int(clamp * X.GATE_LATTICE), int(clamp * X.GATE_LATTICE) + 1, dtype=np.float32) / np.float32(X.GATE_LATTICE)
+    c = np.array(c, dtype=np.float32)
+    u = (t * t).astype(np.float32)
+    p = np.full_like(u, c[9])
+    for k in range(8, -1, -1):
+        p = (p.astype(np.float64) * u + c[k]).astype(np.float32)
+    phi = (t.astype(np.float64) * p + 0.5).astype(np.float32)
+    differ = np.nonzero(phi.view(np.int32) != table.numpy().view(np.int32))[0]
+    for i in differ:
+        print("gate %g: float64 evaluation %r, exact fmas %r" % (t[i], float(phi[i]), float(table[i])))
+    print("gelu on the gate table: %d of %d values differ between the float64 evaluation and the exact one" % (len(differ), len(t)))
+    assert len(t) == 73 and np.abs(phi.astype(np.float64) - table.numpy().astype(np.float64)).max() <= 2.0 ** -23      # a last place at most
+    assert float(table[0]) >= 0.0 and abs(float(table[-1]) - 1.0) <= 2e-6 and float(table[len(t) // 2]) == 0.5
+
+
+# ---- tests/test_kernels_gpu.py: the plan dicts of the statistics / fold / weight-stationary tests, answered here without a device --------
+
+def test_tolerance_test_plan_dicts_hold(ops):
+    import test_kernels_gpu as K
+    z, e = torch.zeros, torch.empty
+    assert set(K.WS_PLANS) == {c[0] for c in K.WS_CASES} and set(K.STATS_PLANS) == {c[0] for c in K.STATS_CASES}
+    for name, M, N, res, lnfold, rowstats, geglu in K.WS_CASES:
+        views = "views" in name
+        ncols = N // 2 if geglu else N
+        pk = ops.PackedConv(z(N, 320), 0, geglu=geglu, bias=z(N), device="cpu")
+        kw = dict(y=e(M, ncols + (32 if views else 0), dtype=torch.bfloat16)[:, :ncols], ksplit=1, x_ld=320 + (64 if views else 0), res=True if res else None,
+                  ln_stats=True if lnfold else None, rowpart=e(M, N // 40, 2) if rowstats else None, raw=e(M, N, dtype=torch.bfloat16) if geglu and lnfold else None)
+        got = ops.conv_gemm_plan(None, pk, 1, M, 1, M, 1, **kw)
+        assert got == K.WS_PLANS[name], (name, got)
+        for word, kind in (("pingpong", "gemm_pps"), ("two_workgroup", "general")):      # a name that states a kernel states the one that runs
+            assert word not in name or got[0] == kind, (name, got)
+    for (M, Cc, N, geglu), plan in K.LNFOLD_PLANS.items():
+        pk = ops.PackedConv(z(N, Cc), 0, geglu=geglu, bias=z(N), device="cpu")
+        assert ops.conv_gemm_plan(None, pk, 1, M, 1, M, 1, ksplit=1, ln_stats=True) == plan, (M, Cc, N, geglu)
+    for (M, Kk, N), plan in K.ROWPART_PLANS.items():
+        pk = ops.PackedConv(z(N, Kk), 0, bias=z(N), device="cpu")
+        assert ops.conv_gemm_plan(None, pk, 1, M, 1, M, 1, res=True, ksplit=1, rowpart=e(M, N // 40, 2)) == plan, (M, Kk, N)
+    for case in K.STATS_CASES:
+        name, B, Cin, Cout, H, W, k, with_res = case[:8]
+        pk = ops.PackedConv(z(Cout, Cin, k, k), k // 2, bias=z(Cout), device="cpu")
+        y, st = e(B * H * W, Cout + 64, dtype=torch.bfloat16)[:, 64:], e(B * H * W // 64, Cout + 64, 2)[:, 64:]
+        got = ops.conv_gemm_plan(None, pk, B, H, W, H, W, res=True if with_res else None, y=y, stats=st)
+        assert got == K.STATS_PLANS[name], (name, got)
+        assert not name.startswith("halo") or got[0].startswith("conv_halo"), (name, got)
 
 
 # ---- tests/test_kernels_gpu.py::CONV_CASES: the names say what runs -----------------------------------------------------------------

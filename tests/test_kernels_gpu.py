@@ -408,9 +408,13 @@ def test_layernorm(ops, Cc):
     assert_close(dx, gx, rtol=2e-2, atol=2e-3, what="ln bwd")
 
 
-@pytest.mark.parametrize("M,Cc,N,geglu", [(4096, 320, 960, False), (2048, 640, 640, False), (4096, 320, 2560, True), (300, 320, 320, False),
-                                            (1024, 1280, 3840, False), (49152, 320, 960, False), (49152, 640, 640, False),
-                                            (12288, 320, 1024, True), (24576, 640, 2560, True)])
+_F160, _F128 = ("general", _F["128x160"], 1), ("general", _F["128x128"], 1)
+LNFOLD_PLANS = {(4096, 320, 960, False): _F160, (2048, 640, 640, False): _F160, (4096, 320, 2560, True): _F128,
+                (300, 320, 320, False): ("general", "small_256x64", 1), (1024, 1280, 3840, False): _F160, (49152, 320, 960, False): ("gemm_ws", None, 1),
+                (49152, 640, 640, False): ("gemm_pps", None, 1), (12288, 320, 1024, True): ("gemm_pps", None, 1), (24576, 640, 2560, True): ("gemm_pps", None, 1)}
+
+
+@pytest.mark.parametrize("M,Cc,N,geglu", list(LNFOLD_PLANS))
 def test_layernorm_folded_into_linear(ops, M, Cc, N, geglu):
     """CF_LNFOLD: LayerNorm(x) W^T + b computed as rstd * (x (gamma o W)^T - mean * c1) + (b + W beta) from the RAW x and the row
     statistics -- the transformer blocks' LayerNorm -> QKV / to_q / GEGLU projections (diffusers BasicTransformerBlock).
@@ -436,14 +440,22 @@ def test_layernorm_folded_into_linear(ops, M, Cc, N, geglu):
     mu, var = x.mean(1), x.var(1, unbiased=False)
     assert_close(stats[:, 0], mu, rtol=1e-4, atol=1e-5, what="ln mean")
     assert_close(stats[:, 1], (var + 1e-5).rsqrt(), rtol=1e-4, atol=1e-5, what="ln rstd")
+    assert ops.conv_gemm_plan(xd, pk, 1, M, 1, M, 1, ksplit=1, ln_stats=stats, ln_c1=pc.bias) == LNFOLD_PLANS[(M, Cc, N, geglu)]
     y = ops.conv_gemm(xd, pk, 1, M, 1, M, 1, ksplit=1, ln_stats=stats, ln_c1=pc.bias)
     torch.cuda.synchronize()
     assert_close(y, ref, rtol=1.5e-2, atol=2e-2, what="ln-folded linear")
 
 
-WS_CASES = [("n320_bias", 36928, 320, False, False, False, False), ("n320_rowstats", 36928, 320, False, False, True, False), ("n320_res_rowstats_takes_the_pingpong_gemm", 36864, 320, True, False, True, False),
+WS_CASES = [("n320_bias", 36928, 320, False, False, False, False), ("n320_rowstats", 36928, 320, False, False, True, False), ("n320_res_rowstats_takes_the_pingpong_gemm", 49152, 320, True, False, True, False),
             ("n960_lnfold", 33088, 960, False, True, False, False), ("n640_rowstats_views", 32768, 640, False, False, True, False),
             ("geglu2560_lnfold_raw", 33088, 2560, False, True, False, True), ("geglu512_plain", 32832, 512, False, False, False, True)]
+
+
+# what runs each case (ops.conv_gemm_plan; asserted in the test, and on the CPU by tests/test_conv_exact_cases.py): the weight-stationary
+# GEMM has no residual epilogue, so the residual case goes on to the ping-pong GEMM
+_WS, _PPS = ("gemm_ws", None, 1), ("gemm_pps", None, 1)
+WS_PLANS = {"n320_bias": _WS, "n320_rowstats": _WS, "n320_res_rowstats_takes_the_pingpong_gemm": _PPS, "n960_lnfold": _WS,
+            "n640_rowstats_views": _WS, "geglu2560_lnfold_raw": _WS, "geglu512_plain": _WS}
 
 
 @pytest.mark.parametrize("case", WS_CASES, ids=[c[0] for c in WS_CASES])
@@ -490,7 +502,9 @@ def test_weight_stationary_gemm(ops, case):
     if res:
         ref = ref + r
     part = torch.zeros((M, N // 40, 2), device="cuda", dtype=torch.float32) if rowstats else None
-    ops.conv_gemm(xd, pk, 1, M, 1, M, 1, y=yd, res=rd, ksplit=1, ln_stats=stats, ln_c1=c1, rowpart=part, raw=raw, x_ld=xs.stride(0))
+    kw = dict(y=yd, res=rd, ksplit=1, ln_stats=stats, ln_c1=c1, rowpart=part, raw=raw, x_ld=xs.stride(0))
+    assert ops.conv_gemm_plan(xd, pk, 1, M, 1, M, 1, **kw) == WS_PLANS[case[0]]
+    ops.conv_gemm(xd, pk, 1, M, 1, M, 1, **kw)
     torch.cuda.synchronize()
     assert_close(yd, ref, rtol=1.5e-2, atol=2e-2 if lnfold else 1e-3, what="ws gemm " + case[0])
     if views:
@@ -504,7 +518,11 @@ def test_weight_stationary_gemm(ops, case):
         assert_close(part[:, :, 1].sum(1), (ref * ref).sum(1), rtol=2e-3, atol=3e-2, what="ws row sums of squares")
 
 
-@pytest.mark.parametrize("M,K,N", [(16384, 320, 320), (8192, 1280, 640), (3000, 640, 1280), (49152, 320, 320), (49152, 1280, 640)])
+ROWPART_PLANS = {(16384, 320, 320): _F160, (8192, 1280, 640): _F160, (3000, 640, 1280): _F160, (49152, 320, 320): ("gemm_pps", None, 1),
+                 (49152, 1280, 640): ("gemm_pps", None, 1)}
+
+
+@pytest.mark.parametrize("M,K,N", list(ROWPART_PLANS))
 def test_linear_emits_layernorm_row_partials(ops, M, K, N):
     """CF_ROWSTATS: the to_out / ff.net.2 / proj_in GEMMs emit (sum, sum^2) of every output row per 80-column wave span; the LayerNorm
     that follows finalises (mean, rstd) from them instead of reading the tensor."""
@@ -516,7 +534,9 @@ def test_linear_emits_layernorm_row_partials(ops, M, K, N):
     pk = ops.PackedConv(w, 0, bias=bias)
     spans = N // 40       # the narrowest span any kernel form writes (gemm_ws.hip: 48 + 32 columns); the spans a form does not write stay zero
     part = torch.zeros((M, spans, 2), device="cuda", dtype=torch.float32)
-    y = ops.conv_gemm(x.to(torch.bfloat16).cuda(), pk, 1, M, 1, M, 1, res=res.to(torch.bfloat16).cuda(), ksplit=1, rowpart=part)
+    xd, rd = x.to(torch.bfloat16).cuda(), res.to(torch.bfloat16).cuda()
+    assert ops.conv_gemm_plan(xd, pk, 1, M, 1, M, 1, res=rd, ksplit=1, rowpart=part) == ROWPART_PLANS[(M, K, N)]
+    y = ops.conv_gemm(xd, pk, 1, M, 1, M, 1, res=rd, ksplit=1, rowpart=part)
     torch.cuda.synchronize()
     ref = x @ w.t() + bias + res
     assert_close(y, ref, what="rowstats: output")
@@ -1014,6 +1034,12 @@ STATS_CASES = [
 ]
 
 
+_HALO1, _PERSIST1 = (_HALO, None, 1), (_PERSIST, None, 1)
+STATS_PLANS = {"fe_128x160_3x3": _F160, "fe_1x1_res": _F160, "generic_256x160_deepK": ("general", _F["256x160"], 1), "two_wg_128x128": _F128,
+               "halo_320_res": _HALO1, "halo_256": _PERSIST1, "halo_w256_res": _PERSIST1, "halo_n128_res": _PERSIST1, "halo_320_res_shift50": _HALO1,
+               "fe_1x1_res_shift50": _F160, "two_wg_128x128_shift50": _F128}
+
+
 @pytest.mark.parametrize("case", STATS_CASES, ids=[c[0] for c in STATS_CASES])
 def test_conv_emits_groupnorm_partials(ops, case):
     """CF_STATS: the implicit-GEMM epilogue also emits per-(64-row block, channel) partial (mean, M2) of the values it stores, and
@@ -1036,6 +1062,7 @@ def test_conv_emits_groupnorm_partials(ops, case):
     ybuf = torch.zeros(M, Ct, device="cuda", dtype=torch.bfloat16)
     part = torch.zeros(M // 64, Ct, 2, device="cuda", dtype=torch.float32)
     resd = ops.to_nhwc_bf16(res, Cout).cuda() if with_res else None
+    assert ops.conv_gemm_plan(xd, pk, B, H, W, H, W, res=resd, y=ybuf[:, 64:], stats=part[:, 64:]) == STATS_PLANS[name]
     y = ops.conv_gemm(xd, pk, B, H, W, H, W, res=resd, y=ybuf[:, 64:], stats=part[:, 64:])
     torch.cuda.synchronize()
     assert_close(ops.from_nhwc(ybuf[:, 64:], B, H, W), ref, what=name + " conv")
