@@ -134,6 +134,7 @@ OPS_SYMBOLS = [
     "dd_op_step_coefs", "dd_op_sampler_step_scratch_floats", "dd_op_sampler_step", "dd_op_sampler_step_bwd",
     "dd_op_step_coef_2m", "dd_op_sampler_step_2m", "dd_op_step_coefs_eta", "dd_op_sampler_step_n",
     "dd_op_step_coefs_sde", "dd_op_step_coef_2m_sde", "dd_op_sampler_step_2m_n",
+    "dd_op_sampler_step1", "dd_op_sampler_step1_bwd",
     "dd_debug_tensor", "dd_debug_num_tensors", "dd_debug_fusion_plan", "dd_debug_set_image", "dd_debug_set_images",
     "dd_debug_plan_only", "dd_debug_plan_dump",
 ]
@@ -145,7 +146,18 @@ ENGINE_SYMBOLS = [
     "dd_set_schedule_s", "dd_denoise_step_h", "dd_direct_guidance_h",
     "dd_set_schedule_e", "dd_denoise_step_n", "dd_direct_guidance_n",
     "dd_set_schedule_sde", "dd_denoise_step_hn", "dd_direct_guidance_hn",
+    "dd_set_cfg_free", "dd_cfg_free",
 ]
+# the CFG-free mode arrived without a version bump (entry points added, ABI_VERSION unchanged): a library built before it loads and
+# runs everything else; only asking for the mode needs them (require_cfg_free)
+CFG_FREE_SYMBOLS = ["dd_op_sampler_step1", "dd_op_sampler_step1_bwd", "dd_set_cfg_free", "dd_cfg_free"]
+
+
+def require_cfg_free(l):
+    missing = [n for n in CFG_FREE_SYMBOLS if not hasattr(l, n)]
+    if missing:
+        raise DistDiffLibraryError("this library was built without the CFG-free mode (missing %s): rebuild with "
+                                   "`python -m distdiff_amd.build`" % ", ".join(missing))
 
 
 def _declare(l):
@@ -186,6 +198,10 @@ def _declare(l):
     l.dd_op_step_coefs_sde.argtypes = [i, C.c_double, C.c_double, C.c_double, vp]
     l.dd_op_step_coef_2m_sde.argtypes = [i, i, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     l.dd_op_sampler_step_2m_n.argtypes = [vp, i, vp, vp, f, vp, f, C.c_uint64, i, vp, vp, vp, i, i, i, vp, vp, i, f, vp, vp, vp]
+    if hasattr(l, "dd_op_sampler_step1"):
+        l.dd_op_sampler_step1.argtypes = [vp, i, vp, vp, f, vp, f, C.c_uint64, i, vp, vp, vp, i, i, i, vp, vp, i, vp]
+    if hasattr(l, "dd_op_sampler_step1_bwd"):
+        l.dd_op_sampler_step1_bwd.argtypes = [vp, vp, vp, i, vp, i, i, i, vp, vp, i, vp]
     l.dd_op_sumpool2x2.argtypes = [vp, i, vp, i, i, i, i, i, i, vp]
     l.dd_op_geglu_bwd.argtypes = [vp, i, vp, i, vp, i, i, i, vp]
     l.dd_op_maxpool3x3s2.argtypes = [vp, vp, i, i, i, i, vp]

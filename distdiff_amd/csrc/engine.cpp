@@ -40,7 +40,7 @@ inline void cot_mul(float*, size_t, int, int, const float*, hipStream_t) {}
 #endif
 inline const float* cot_inv(const float* cs) { return cs ? cs + 1 : nullptr; }
 
-// UNet forward on instance k: z fp32 NCHW -> eps2 fp32 NHWC [2B*HW, ld] inside the slab
+// UNet forward on instance k: z fp32 NCHW -> eps2 fp32 NHWC [halves*B*HW, ld] inside the slab (a CFG-free engine: the conditional output alone)
 void unet_fwd(dd_engine* E, int k, const float* z, int step_index, hipStream_t s, bool stash = true) {
   const dd_config& c = E->cfg;
   Ctx ctx = make_ctx(E, dd_engine::UNET, k, s);
@@ -137,6 +137,7 @@ StepParams step_params(dd_engine* E, int k, int step_index, const Schedule::Rows
   p.coef = rows.coef + (size_t)step_index * 8; p.lin = rows.lin + (size_t)step_index * 4;
   p.prediction_type = E->sp.prediction_type; p.phi = E->sp.guidance_rescale;
   p.stats = E->inst[k].rs_stats; p.part = E->rs_part;
+  p.halves = E->halves;
   return p;
 }
 // the noise of a stochastic step (eta > 0 or sde_eta > 0): the caller's tensor [B,C,L,L], or generated inside the step kernel from (seed, unit id of
@@ -412,7 +413,7 @@ int dd_finalize_weights(dd_engine* E) {
     }
     E->scratch_tmp = (char*)E->dmalloc(E->tmp_cap);
     const int maxG = std::max(c.unet_groups, c.vae_groups);
-    E->gn_scratch = (float*)E->dmalloc(groupnorm_scratch_bytes(2 * B, maxG), false);
+    E->gn_scratch = (float*)E->dmalloc(groupnorm_scratch_bytes(E->halves * B, maxG), false);
     E->rowpart = (float*)E->dmalloc(std::max(E->unet.scratch_rowpart, (size_t)256), false);
     for (auto& f : E->f32_tmp) f = (float*)E->dmalloc(zbytes);
     E->img_tmp = (float*)E->dmalloc((size_t)B * 3 * 64 * L * L * 4);
@@ -421,10 +422,10 @@ int dd_finalize_weights(dd_engine* E) {
     E->image_scores = (float*)E->dmalloc((size_t)B * 4);
     E->rng_eb = (float*)E->dmalloc((size_t)B * 8 * 4);
     // cross-attention K/V buffers
-    E->ctx_bf16 = (bf16_t*)E->dmalloc((size_t)2 * B * c.text_len * rup(c.unet_cross_dim, 8) * 2);
+    E->ctx_bf16 = (bf16_t*)E->dmalloc((size_t)E->halves * B * c.text_len * rup(c.unet_cross_dim, 8) * 2);
     for (auto& sl : E->cross_slots) {
-      bf16_t* k = (bf16_t*)E->dmalloc((size_t)2 * B * c.text_len * sl.C * 2);
-      bf16_t* v = (bf16_t*)E->dmalloc((size_t)2 * B * c.text_len * sl.C * 2);
+      bf16_t* k = (bf16_t*)E->dmalloc((size_t)E->halves * B * c.text_len * sl.C * 2);
+      bf16_t* v = (bf16_t*)E->dmalloc((size_t)E->halves * B * c.text_len * sl.C * 2);
       E->cross_kv.push_back({k, v});
     }
     if (!E->plan_only) HIPCHK(hipDeviceSynchronize());
@@ -443,6 +444,15 @@ int dd_finalize_weights(dd_engine* E) {
   } catch (const std::exception& ex) { E->err = ex.what(); return DD_ERR_HIP; }
   return DD_OK;
 }
+
+// the graph is built at finalize: until then the number of CFG halves is a setting
+int dd_set_cfg_free(dd_engine* E, int on) {
+  if (!E) return DD_ERR_ARG;
+  if (E->finalized) { E->err = "dd_set_cfg_free after dd_finalize_weights: the UNet program is built for the batch it runs on"; return DD_ERR_STATE; }
+  E->halves = on ? 1 : 2;
+  return DD_OK;
+}
+int dd_cfg_free(dd_engine* E) { return E ? (E->halves == 1 ? 1 : 0) : DD_ERR_ARG; }
 
 int dd_set_schedule(dd_engine* E, const int* timesteps, int n, const float* alphas_cumprod, int num_train, float final_alpha,
                     const dd_sampler_params* sp) {
@@ -475,6 +485,8 @@ int dd_set_schedule_sde(dd_engine* E, const int* timesteps, int n, const float* 
     const dd_config& c = E->cfg;
     if (sp->prediction_type < 0 || sp->prediction_type > 2) throw std::runtime_error("prediction_type must be 0 (epsilon), 1 (v_prediction) or 2 (sample)");
     if (!(sp->guidance_rescale >= 0.f && sp->guidance_rescale <= 1.f)) throw std::runtime_error("guidance_rescale must be in [0, 1]");
+    if (E->halves == 1 && sp->guidance_rescale != 0.f)
+      throw std::runtime_error("guidance_rescale != 0 on a CFG-free engine (dd_set_cfg_free): there is no guidance to rescale, the factor is identically 1 at m = c");
     if (solver < 0 || solver > 1) throw std::runtime_error("solver must be 0 (DDIM) or 1 (DPM-Solver++(2M))");
     if (!(eta >= 0.f && eta <= 1.f)) throw std::runtime_error("eta must be in [0, 1]");
     if (eta > 0.f && solver != 0) throw std::runtime_error("eta > 0 is stochastic DDIM (solver 0): the per-step noise of solver 1 is sde_eta (dd_set_schedule_sde)");
@@ -577,7 +589,7 @@ int dd_set_prompt(dd_engine* E, const float* embeds, int B, void* stream) {
     check_batch(E, B);
     const dd_config& c = E->cfg;
     hipStream_t s = (hipStream_t)stream;
-    const int rows = 2 * B * c.text_len, ld = rup(c.unet_cross_dim, 8);
+    const int rows = E->halves * B * c.text_len, ld = rup(c.unet_cross_dim, 8);      // a CFG-free engine: [B, T, D], conditional only
     // [rows, cross_dim] fp32 -> bf16 rows (treated as NCHW with H*W = 1 per row)
     HIPCHK(launch_nchw_f32_to_nhwc_bf16(embeds, E->ctx_bf16, rows, c.unet_cross_dim, 1, 1, ld, ld, 0, 1.f, s));
     for (size_t i = 0; i < E->cross_slots.size(); ++i) {
@@ -651,7 +663,7 @@ int dd_unet_forward(dd_engine* E, const float* z, int step_index, float* eps2_ou
     hipStream_t s = (hipStream_t)stream;
     unet_fwd(E, 0, z, step_index, s);
     const Tn& out = E->unet.t[E->unet_out];
-    HIPCHK(launch_nhwc_to_nchw_f32(E->inst[0].act[dd_engine::UNET] + out.off, 1, eps2_out, 2 * B, c.unet_out_channels, c.latent_size, c.latent_size, out.ld,
+    HIPCHK(launch_nhwc_to_nchw_f32(E->inst[0].act[dd_engine::UNET] + out.off, 1, eps2_out, E->halves * B, c.unet_out_channels, c.latent_size, c.latent_size, out.ld,
                                    1.f, 0.f, 0, 0.f, 0.f, s));
   });
 }
@@ -1002,8 +1014,8 @@ int dd_unet_vjp(dd_engine* E, const float* z, int step_index, const float* g_eps
     Ctx uc = make_ctx(E, dd_engine::UNET, 0, s);
     uc.step_index = step_index;
     const Tn& out = E->unet.t[E->unet_out];
-    const float* cs = cot_normalise(E, g_eps2, (size_t)2 * B * c.unet_out_channels, HW, HW, s);
-    HIPCHK(launch_nchw_f32_to_nhwc_bf16(g_eps2, grad_ptr(uc, out), 2 * B, c.unet_out_channels, c.latent_size, c.latent_size, out.ld, out.ld, 0,
+    const float* cs = cot_normalise(E, g_eps2, (size_t)E->halves * B * c.unet_out_channels, HW, HW, s);
+    HIPCHK(launch_nchw_f32_to_nhwc_bf16(g_eps2, grad_ptr(uc, out), E->halves * B, c.unet_out_channels, c.latent_size, c.latent_size, out.ld, out.ld, 0,
                                         1.f, s, cs));
     run_bwd(E->unet, uc);
     const Tn& in = E->unet.t[E->unet_in];

@@ -491,9 +491,12 @@ void build_unet(dd_engine* E) {
   // classifier-free guidance runs the UNet on cat[z, z] (generate_data.py:110-112): until the first cross-attention the two halves are
   // bit-for-bit the same computation, so the program starts on B images and duplicates at that point (build_transformer).  Not with
   // SDXL's text_time conditioning, whose time embedding already differs per half.
-  const bool share = c.unet_add_time_dim == 0 && !E->sw.no_cfg_share;
+  // A CFG-free engine (dd_set_cfg_free) has one half: nothing to share and nothing to duplicate, every tensor is on B images.
+  if (E->halves == 1 && c.unet_add_time_dim > 0)
+    throw std::runtime_error("cfg_free: a UNet with text_time conditioning (unet_add_time_dim > 0, SDXL) is not built single-pass: its per-image bias tables hold 2B rows");
+  const bool share = E->halves == 2 && c.unet_add_time_dim == 0 && !E->sw.no_cfg_share;
   b.full_batch = share ? B2 : 0;
-  E->unet_in = P.tensor(share ? c.max_batch : B2, L, L, c.unet_in_channels);
+  E->unet_in = P.tensor(share ? c.max_batch : E->halves * c.max_batch, L, L, c.unet_in_channels);
   int h = b.conv(E->unet_in, make_conv(E, m, "conv_in", 1));
   std::vector<int> skips{h};
   for (int i = 0; i < nl; ++i) {
@@ -522,7 +525,7 @@ void build_unet(dd_engine* E) {
       h = b.conv(h, make_conv(E, m, name("up_blocks.%d.upsamplers.0.conv", i), 1), {.up = 1});
     }
   }
-  if (P.t[h].B != B2) throw std::runtime_error("UNet without any cross-attention: the CFG halves never part");
+  if (E->halves == 2 && P.t[h].B != B2) throw std::runtime_error("UNet without any cross-attention: the CFG halves never part");
   h = b.gn(h, make_norm(E, m, "conv_norm_out"), G, eps, 1);
   E->unet_out = b.conv(h, make_conv(E, m, "conv_out", 1), {.out_f32 = 1});
   finish_program(P);

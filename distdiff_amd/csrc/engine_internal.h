@@ -270,6 +270,9 @@ struct dd_engine {
   std::string err;
   std::unordered_map<std::string, HostTensor> raw;  // "model/key" -> fp32 host copy until finalize
   bool finalized = false;
+  // 2: the UNet runs on cat[z, z], unconditional and conditional prompt (classifier-free guidance).  1 (dd_set_cfg_free, before finalize):
+  // on the conditional prompt alone -- every batch of the UNet path is halves * max_batch
+  int halves = 2;
 
   std::vector<std::unique_ptr<ConvW>> convs;
   std::vector<std::unique_ptr<NormW>> norms;
@@ -295,8 +298,8 @@ struct dd_engine {
   dd_engine() { for (Program& P : prog) P.sw = &sw; }
   struct CrossSlot { ConvW* wk; ConvW* wv; int C; };
   std::vector<CrossSlot> cross_slots;
-  std::vector<std::pair<bf16_t*, bf16_t*>> cross_kv;  // device K,V [2B*text_len, C] per slot
-  bf16_t* ctx_bf16 = nullptr;                         // [2B*text_len, cross_dim]
+  std::vector<std::pair<bf16_t*, bf16_t*>> cross_kv;  // device K,V [halves*B*text_len, C] per slot
+  bf16_t* ctx_bf16 = nullptr;                         // [halves*B*text_len, cross_dim]
   std::vector<ConvW*> temb_convs;                     // resnet conv1's with time_emb_proj
   float* temb_w1 = nullptr; float* temb_b1 = nullptr; float* temb_w2 = nullptr; float* temb_b2 = nullptr;
   // SDXL text_time conditioning

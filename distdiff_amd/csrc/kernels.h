@@ -216,7 +216,11 @@ hipError_t launch_nhwc_to_nchw_f32(const void* src, int src_f32, float* dst, int
 //                                z' = (the history step on those rows) + sigma n.  The generated form keeps its
 //                                row ranges; every launch reads and writes its own rows only, so x0 may still alias x0_prev.
 //                                With sigma == 0 or no source: the step above, nothing of this block is read.
-// ld: a multiple of 8; C <= 8; B <= 65535; anything else is hipErrorInvalidValue in front of any launch.  No atomics: bitwise deterministic.
+//   halves == 1                  the CFG-free step of an engine that runs the UNet on the conditional prompt alone (dd_set_cfg_free): m2 is
+//                                [B*HW, ld] and m = c -- no mix, coef[0] is not read; every mode above but the rescale, whose factor is
+//                                identically 1 at m = c: phi != 0 is refused.  The backward writes g_m once, to rows [B*HW, ld] of g_m2.
+// ld: a multiple of 8; C <= 8; B <= 65535; halves 1 or 2; anything else is hipErrorInvalidValue in front of any launch.  No atomics: bitwise
+// deterministic.
 #define DD_RNG_UNITS 16
 struct RngUnits { unsigned lo[DD_RNG_UNITS], hi[DD_RNG_UNITS]; };
 struct StepParams {
@@ -232,6 +236,7 @@ struct StepParams {
   const float* noise; float sigma;     // eta > 0 / SDE: explicit step noise NCHW fp32 [B, C, HW] (or null: generated) and sigma of this step
   uint64_t rng_seed; int rng_stream;   // the generated form: Philox key and stream (16 + step index)
   RngUnits rng_ids; int rng_count, rng_row0;
+  int halves = 2;                      // 2: the CFG pair above.  1 (CFG-free): m2 is [B*HW, ld], the conditional output alone -- see below
 };
 // The host numbers of step i of an n-step schedule under one rule, from alphas_cumprod at step i - 1, at step i and at its previous
 // timestep; formed in double, each float rounded once.  One function states them for every mode:
@@ -269,7 +274,7 @@ hipError_t launch_sampler_step(const StepParams& p, hipStream_t s);
 // rng_count and rng_row0 are filled here).  With sigma == 0 this is launch_sampler_step(p).
 hipError_t launch_sampler_step_units(const StepParams& p, const uint64_t* unit_ids, hipStream_t s);
 // VJP of step p in (x0, z'): g_x0, g_zprev NCHW fp32 (either may be null) -> g_z NCHW fp32 (the direct path) and g_m2, bf16 NHWC rows
-// [2B*HW, ld] with every column written (padding = 0).  p.z, p.x0_prev, p.z_prev and p.x0 are not used.  See DESIGN.md / SURVEY appendix A
+// [halves*B*HW, ld] with every column written (padding = 0).  p.z, p.x0_prev, p.z_prev and p.x0 are not used.  See DESIGN.md / SURVEY appendix A
 hipError_t launch_sampler_step_bwd(const StepParams& p, const float* g_x0, const float* g_zprev, bf16_t* g_m2, float* g_z, hipStream_t s);
 // backward of cat[z, z] + NCHW->NHWC: g_z[b,c,pix] (+)= gin[b*HW+pix, c] + gin[(B+b)*HW+pix, c]   (halves = 2), or of the plain
 // layout change when the UNet input itself is not duplicated (halves = 1: the two CFG halves share their prefix, engine.cpp)

@@ -163,6 +163,22 @@ int dd_op_sampler_step_2m_n(const float* m2, int ld, const float* z, const float
   if (noise || unit_ids) { p.noise = noise; p.sigma = sigma; p.rng_seed = seed; p.rng_stream = rng_stream; }
   return (int)launch_sampler_step_units(p, unit_ids, S(st));
 }
+// the CFG-free step (StepParams::halves = 1): m1 is the conditional output alone, every optional input of dd_op_sampler_step_2m_n, no rescale
+int dd_op_sampler_step1(const float* m1, int ld, const float* z, const float* x0_prev, float c2m, const float* noise, float sigma,
+                        uint64_t seed, int rng_stream, const uint64_t* unit_ids, float* z_prev, float* x0, int B, int C, int HW,
+                        const float* coef, const float* lin, int prediction_type, void* st) {
+  StepParams p = step_params(m1, ld, B, C, HW, coef, lin, prediction_type, 0.f, nullptr, nullptr);
+  p.halves = 1;
+  p.z = z; p.x0_prev = x0_prev; p.c2m = c2m; p.z_prev = z_prev; p.x0 = x0;
+  if (noise || unit_ids) { p.noise = noise; p.sigma = sigma; p.rng_seed = seed; p.rng_stream = rng_stream; }
+  return (int)launch_sampler_step_units(p, unit_ids, S(st));
+}
+int dd_op_sampler_step1_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_m1, int ld, float* g_z, int B, int C, int HW,
+                            const float* coef, const float* lin, int prediction_type, void* st) {
+  StepParams p = step_params(nullptr, ld, B, C, HW, coef, lin, prediction_type, 0.f, nullptr, nullptr);
+  p.halves = 1;
+  return (int)launch_sampler_step_bwd(p, g_x0, g_zprev, g_m1, g_z, S(st));
+}
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int acc, void* st) {
   return (int)launch_sumpool2x2(src, src_ld, dst, dst_ld, B, H, W, C, acc, S(st));
 }

@@ -42,25 +42,28 @@ __device__ __forceinline__ void load_row8(const float* p, int C, float* v) {
 // compute it again: 4x the Philox work of rng.hip, microseconds against the UNet) and the Box-Muller of the one word pair it needs.
 // HIST with NOISE keeps the row ranges of the generated form (DD_RNG_UNITS ids per launch): a launch reads and writes the elements of
 // its own rows only -- z, x0_prev, x0, z_prev alike -- so x0 == x0_prev stays legal across the launches of one batch.
-template <bool EPS, bool HIST, bool NOISE>
+// HALVES == 1 (StepParams::halves, the CFG-free engine): m2 holds the conditional rows alone and m = c -- the unconditional row and
+// coef[0] are not read, the mix is not evaluated; everything after `mix` is the same text.  fmaf(s, c - c, c) == c for finite c, so this
+// is the two-half kernel on m2 = [c; c] bit for bit (tests/test_cfg_free_gpu.py).
+template <bool EPS, bool HIST, bool NOISE, int HALVES>
 __global__ __launch_bounds__(STEP_THREADS) void sampler_step_kernel(const StepParams p) {
 #pragma clang fp contract(off)
   const int b = NOISE ? p.rng_row0 + blockIdx.y : blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
   if (pix >= p.HW) return;
-  const float s = p.coef[0];
+  const float s = HALVES == 2 ? p.coef[0] : 1.f;
   // EPS: {sqrt a, sqrt(1-a)} and {sqrt a', sqrt(1-a')}, the latter on (x0, m); linear: {A_z, A_m} and {B_z, B_m}, on (z, m^)
   const float a0 = EPS ? p.coef[1] : p.lin[0], a1 = EPS ? p.coef[2] : p.lin[1];
   const float b0 = EPS ? p.coef[3] : p.lin[2], b1 = EPS ? p.coef[4] : p.lin[3];
-  const float k = !EPS && p.phi != 0.f ? p.stats[b * 8] : 1.f;
+  const float k = HALVES == 2 && !EPS && p.phi != 0.f ? p.stats[b * 8] : 1.f;
   float u[8], c[8];
-  load_row8(p.m2 + ((size_t)b * p.HW + pix) * p.ld, p.C, u);
-  load_row8(p.m2 + ((size_t)(p.B + b) * p.HW + pix) * p.ld, p.C, c);
+  if (HALVES == 2) load_row8(p.m2 + ((size_t)b * p.HW + pix) * p.ld, p.C, u);
+  load_row8(p.m2 + ((size_t)(HALVES == 2 ? p.B + b : b) * p.HW + pix) * p.ld, p.C, c);
 #pragma unroll
   for (int ch = 0; ch < 8; ++ch) {
     if (ch < p.C) {
       const size_t zi = ((size_t)b * p.C + ch) * p.HW + pix;
       const float zz = p.z[zi], xp = HIST ? p.x0_prev[zi] : 0.f;
-      const float mix = __builtin_fmaf(s, c[ch] - u[ch], u[ch]);
+      const float mix = HALVES == 2 ? __builtin_fmaf(s, c[ch] - u[ch], u[ch]) : c[ch];
       const float m = EPS ? mix : k * mix;
       // x0.  EPS: an fma and a correctly rounded division (bits of the former cfg_ddim_kernel); linear: both products rounded, then
       // added (bits of the former linear-form sampler_step_kernel) -- with and without a history
@@ -183,12 +186,14 @@ __global__ __launch_bounds__(STEP_THREADS) void sampler_step_bwd_dot_kernel(cons
 //   linear:   g_z = A_z g_x0 + B_z g_z',  g^ = A_m g_x0 + B_m g_z'; with rescale (p.m2 = the model output of that step, p.part from
 //             the kernel above, S its sum over the image):
 //             g_m = k g^ - phi sigma_c / sigma_m^2 . S (m - mean_m) / ((N - 1) sigma_m),  g_c += phi / sigma_m . S (c - mean_c) / ((N - 1) sigma_c)
-template <bool EPS>
+// HALVES == 1: g_m itself goes to rows [B*HW, ld] of g_m2 -- no (1 - s, s) split, coef[0] is not read, no rescale (refused by the launcher).
+// It is the conditional row of the two-half kernel at s = 1 bit for bit: 1 * g_m and fmaf(1, g_m, 0) are g_m.
+template <bool EPS, int HALVES>
 __global__ __launch_bounds__(STEP_THREADS) void sampler_step_bwd_kernel(const StepParams p, const float* g_x0, const float* g_zprev,
                                                                         bf16_t* g_m2, float* g_z) {
 #pragma clang fp contract(off)
   __shared__ float S_sh;
-  const bool rescale = !EPS && p.phi != 0.f;
+  const bool rescale = HALVES == 2 && !EPS && p.phi != 0.f;
   const int b = blockIdx.y, pix = blockIdx.x * STEP_THREADS + threadIdx.x;
   float k = 1.f, tm = 0.f, tc = 0.f, mean_c = 0.f, mean_m = 0.f;
   if (rescale) {
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(STEP_THREADS) void sampler_step_bwd_kernel(const St
     tc = phi / sig_m * S_sh / (N1 * sig_c);
   }
   if (pix >= p.HW) return;
-  const float s = p.coef[0];
+  const float s = HALVES == 2 ? p.coef[0] : 1.f;
   // EPS: {sqrt a, sqrt(1-a)} and {sqrt a', sqrt(1-a')}; linear: {A_z, A_m} and {B_z, B_m}
   const float a0 = EPS ? p.coef[1] : p.lin[0], a1 = EPS ? p.coef[2] : p.lin[1];
   const float b0 = EPS ? p.coef[3] : p.lin[2], b1 = EPS ? p.coef[4] : p.lin[3];
@@ -226,7 +231,7 @@ __global__ __launch_bounds__(STEP_THREADS) void sampler_step_bwd_kernel(const St
         const float h = __builtin_fmaf(b0, gp, gx);
         g_z[zi] = h / a0;
         gm = -a1 / a0 * h + b1 * gp;
-        gc[ch] = s * gm;
+        gc[ch] = HALVES == 2 ? s * gm : gm;
       } else {     // bits of the former linear-form backward: g_z the sum of two rounded products, g^ and s g_m + extra fused
         g_z[zi] = a0 * gx + b0 * gp;
         gm = __builtin_fmaf(a1, gx, b1 * gp);
@@ -236,22 +241,39 @@ __global__ __launch_bounds__(STEP_THREADS) void sampler_step_bwd_kernel(const St
           gm = k * gm - tm * (m - mean_m);
           extra = tc * (c[ch] - mean_c);
         }
-        gc[ch] = __builtin_fmaf(s, gm, extra);
+        gc[ch] = HALVES == 2 ? __builtin_fmaf(s, gm, extra) : gm;
       }
       gu[ch] = (1.f - s) * gm;
     }
   }
+  const uint4 zero = make_uint4(0, 0, 0, 0);
+  if (HALVES == 1) {
+    bf16_t* rc = g_m2 + ((size_t)b * p.HW + pix) * p.ld;
+    *(uint4*)rc = pack8(gc);
+    for (int c0 = 8; c0 < p.ld; c0 += 8) *(uint4*)(rc + c0) = zero;
+    return;
+  }
   bf16_t* ru = g_m2 + ((size_t)b * p.HW + pix) * p.ld;
   bf16_t* rc = g_m2 + ((size_t)(p.B + b) * p.HW + pix) * p.ld;
   *(uint4*)ru = pack8(gu); *(uint4*)rc = pack8(gc);
-  const uint4 zero = make_uint4(0, 0, 0, 0);
   for (int c0 = 8; c0 < p.ld; c0 += 8) { *(uint4*)(ru + c0) = zero; *(uint4*)(rc + c0) = zero; }
 }
 
 // what both launchers refuse in front of any launch.  The 16-byte row accesses need ld % 8 == 0, the thread map C <= 8, the grid B <= 65535
+// One half (CFG-free) has no rescale: its factor is identically 1 at m = c and the statistics pass is not built for one half
 bool step_args_ok(const StepParams& p, bool eps) {
   const bool shape_ok = p.B >= 1 && p.B <= 65535 && p.C >= 1 && p.C <= 8 && p.HW >= 1 && p.ld >= 8 && !(p.ld & 7);
-  return shape_ok && p.prediction_type >= 0 && p.prediction_type <= 2 && (eps || p.lin) && (p.phi == 0.f || (p.stats && p.part));
+  const bool halves_ok = p.halves == 2 || (p.halves == 1 && p.phi == 0.f);
+  return shape_ok && halves_ok && p.prediction_type >= 0 && p.prediction_type <= 2 && (eps || p.lin) && (p.phi == 0.f || (p.stats && p.part));
+}
+// the forward instantiation of one launch
+template <int HALVES>
+auto step_kernel(bool eps, bool hist, bool noise) -> void (*)(StepParams) {
+  if (noise)
+    return eps ? (hist ? sampler_step_kernel<true, true, true, HALVES> : sampler_step_kernel<true, false, true, HALVES>)
+               : (hist ? sampler_step_kernel<false, true, true, HALVES> : sampler_step_kernel<false, false, true, HALVES>);
+  return eps ? (hist ? sampler_step_kernel<true, true, false, HALVES> : sampler_step_kernel<true, false, false, HALVES>)
+             : (hist ? sampler_step_kernel<false, true, false, HALVES> : sampler_step_kernel<false, false, false, HALVES>);
 }
 
 }  // namespace
@@ -349,13 +371,11 @@ hipError_t launch_sampler_step(const StepParams& p, hipStream_t s) {
     StepParams q = p;
     if (!generated) q.rng_row0 = 0;
     const dim3 rows(grid.x, generated ? p.rng_count : p.B);
-    const auto noisy = eps ? (hist ? sampler_step_kernel<true, true, true> : sampler_step_kernel<true, false, true>)
-                           : (hist ? sampler_step_kernel<false, true, true> : sampler_step_kernel<false, false, true>);
+    const auto noisy = p.halves == 1 ? step_kernel<1>(eps, hist, true) : step_kernel<2>(eps, hist, true);
     hipLaunchKernelGGL(noisy, rows, dim3(STEP_THREADS), 0, s, q);
     return hipGetLastError();
   }
-  const auto kernel = eps ? (hist ? sampler_step_kernel<true, true, false> : sampler_step_kernel<true, false, false>)
-                          : (hist ? sampler_step_kernel<false, true, false> : sampler_step_kernel<false, false, false>);
+  const auto kernel = p.halves == 1 ? step_kernel<1>(eps, hist, false) : step_kernel<2>(eps, hist, false);
   hipLaunchKernelGGL(kernel, grid, dim3(STEP_THREADS), 0, s, p);
   return hipGetLastError();
 }
@@ -376,7 +396,8 @@ hipError_t launch_sampler_step_bwd(const StepParams& p, const float* g_x0, const
   const dim3 grid((p.HW + STEP_THREADS - 1) / STEP_THREADS, p.B);
   if (p.phi != 0.f)
     hipLaunchKernelGGL(sampler_step_bwd_dot_kernel, grid, dim3(STEP_THREADS), 0, s, g_x0, g_zprev, p.m2, p.ld, p.B, p.C, p.HW, p.coef, p.lin, p.part);
-  hipLaunchKernelGGL(eps ? sampler_step_bwd_kernel<true> : sampler_step_bwd_kernel<false>, grid, dim3(STEP_THREADS), 0, s, p, g_x0, g_zprev,
-                     g_m2, g_z);
+  const auto kernel = p.halves == 1 ? (eps ? sampler_step_bwd_kernel<true, 1> : sampler_step_bwd_kernel<false, 1>)
+                                    : (eps ? sampler_step_bwd_kernel<true, 2> : sampler_step_bwd_kernel<false, 2>);
+  hipLaunchKernelGGL(kernel, grid, dim3(STEP_THREADS), 0, s, p, g_x0, g_zprev, g_m2, g_z);
   return hipGetLastError();
 }

@@ -116,6 +116,10 @@ def _declare(l):
     l.dd_workspace_bytes.restype = C.c_size_t
     l.dd_flops_last.argtypes = [vp]
     l.dd_flops_last.restype = C.c_double
+    if hasattr(l, "dd_set_cfg_free"):       # _lib.CFG_FREE_SYMBOLS: absent from a library built before the mode
+        l.dd_set_cfg_free.argtypes = [vp, i]
+    if hasattr(l, "dd_cfg_free"):
+        l.dd_cfg_free.argtypes = [vp]
 
 
 DD_ABI_VERSION = _lib.ABI_VERSION      # include/distdiff_hip.h
@@ -210,8 +214,11 @@ class Engine:
     """One engine per device. Mirrors the objects the reference builds at generate_data.py:863-922, 1100-1125."""
 
     def __init__(self, cfg: EngineConfig, weights, enable_grad=True, max_guidance_period=2, device="cuda:0", layout=None, attn_fp8=False,
-                 act_dtype="bf16"):
-        """attn_fp8: BASELINE configs[4]'s fp8 MFMA attention (P.V of the UNet's d = 64 heads in e4m3; dd_config.unet_attn_fp8).
+                 act_dtype="bf16", cfg_free=False):
+        """cfg_free: the engine runs the UNet once per step, on the conditional prompt alone (dd_set_cfg_free; what diffusers does for
+        guidance_scale <= 1 and how guidance-distilled / few-step checkpoints are sampled): `set_prompt` takes [B, T, D], `unet_forward`
+        returns and `unet_vjp` takes B images, guidance_scale is not read, guidance_rescale must be 0; SDXL (text_time) is refused.
+        attn_fp8: BASELINE configs[4]'s fp8 MFMA attention (P.V of the UNet's d = 64 heads in e4m3; dd_config.unet_attn_fp8).
         act_dtype: 'bf16' | 'fp16', the 16-bit storage format of every activation, weight and gradient of the UNet / VAE / text / ViT
         programs.  It is the library the engine is created in (_lib.lib(act_dtype): libdistdiff_hip.so or libdistdiff_hip_f16.so) and
         every call of this engine goes through that library; engines of both kinds can live in one process.  The boundary is fp32
@@ -230,7 +237,13 @@ class Engine:
         self.L = _lib.lib(self.act_dtype)
         self._h = vp()
         cc = _to_c_config(cfg, enable_grad, max_guidance_period, attn_fp8)
+        self.cfg_free = bool(cfg_free)
+        self.halves = 1 if self.cfg_free else 2          # batches of the UNet path are halves * B
+        if self.cfg_free:
+            _lib.require_cfg_free(self.L)
         self._chk(self.L.dd_create(C.byref(cc), C.byref(self._h)), "dd_create")
+        if self.cfg_free:
+            self._chk(self.L.dd_set_cfg_free(self._h, 1), "dd_set_cfg_free")
         if weights is not None:
             self.layout = []
             for model in ("unet", "vae", "guide", "text", "text2"):
@@ -321,9 +334,10 @@ class Engine:
         self._chk(self.L.dd_set_prototypes(self._h, _p(pc), _p(pg), Cn, K, D), "dd_set_prototypes")
 
     def set_prompt(self, embeds_2b):
-        """embeds_2b: device fp32 [2B, text_len, cross_dim], negative (uncond) half first (generate_data.py:1184)."""
+        """embeds_2b: device fp32 [2B, text_len, cross_dim], negative (uncond) half first (generate_data.py:1184); on a cfg_free engine
+        [B, text_len, cross_dim], the conditional embeddings alone."""
         e = embeds_2b.to(self.device, torch.float32).contiguous()
-        assert e.shape[0] == 2 * self.B
+        assert e.shape[0] == self.halves * self.B, "set_prompt: %d rows for %d (cfg_free=%s)" % (e.shape[0], self.halves * self.B, self.cfg_free)
         self._chk(self.L.dd_set_prompt(self._h, _p(e), self.B, _stream()), "dd_set_prompt")
         self._keep = [e]
 
@@ -400,7 +414,7 @@ class Engine:
 
     def unet_forward(self, z, step_index):
         z = self._f(z)
-        out = torch.empty((2 * z.shape[0],) + tuple(z.shape[1:]), device=self.device, dtype=torch.float32)
+        out = torch.empty((self.halves * z.shape[0],) + tuple(z.shape[1:]), device=self.device, dtype=torch.float32)
         self._chk(self.L.dd_unet_forward(self._h, _p(z), step_index, _p(out), z.shape[0], _stream()), "dd_unet_forward")
         return out
 
@@ -523,6 +537,7 @@ class Engine:
     # ---- per-module VJP diagnostics -------------------------------------------------------------
     def unet_vjp(self, z, step_index, g_eps2):
         z, g = self._f(z), self._f(g_eps2)
+        assert g.shape[0] == self.halves * z.shape[0], "unet_vjp: g_eps2 has %d images, the UNet output %d" % (g.shape[0], self.halves * z.shape[0])
         out = torch.empty_like(z)
         self._chk(self.L.dd_unet_vjp(self._h, _p(z), step_index, _p(g), _p(out), z.shape[0], _stream()), "dd_unet_vjp")
         return out

@@ -157,6 +157,12 @@ def parse_args(argv=None):
                    help="16-bit storage format of the UNet / VAE / text / ViT activations, weights and gradients: bf16 (default, libdistdiff_hip.so) "
                    "or fp16 (IEEE half, what the reference runs in: libdistdiff_hip_f16.so, the same kernels compiled with -DDD_ACT_F16; "
                    "DESIGN.md section 14).  The ranks of --gpus get it with the rest of the command line.  Not with --attn_fp8")
+    p.add_argument("--cfg_free", action="store_true", default=False,
+                   help="one UNet pass per step, on the class prompt alone (Engine(cfg_free=True)): what diffusers does for guidance_scale <= 1 and "
+                   "how guidance-distilled / few-step checkpoints (LCM, Turbo, Lightning, Hyper-SD) and scale-1 fine-tunes are sampled.  The "
+                   "negative prompt is not uploaded and --guidance_scale is not used.  Not with --guidance_rescale > 0, not with SDXL.  Base "
+                   "checkpoints trained for classifier-free guidance give poor images without it.  The ranks of --gpus get it with the rest "
+                   "of the command line.  Off by default: --guidance_scale 1.0 without this flag still runs both passes")
     p.add_argument("--data_root", type=str, default="data")
     p.add_argument("--gpus", type=int, default=1, help="spawn this many ranks (one per GPU) that shard the images like --total_split; "
                    "weights are loaded once on rank 0 and broadcast over RCCL")
@@ -183,6 +189,10 @@ def parse_args(argv=None):
         raise SystemExit("--sde_eta > 0 needs --eta 0: --eta is the noise of stochastic DDIM")
     if args.act_dtype == "fp16" and args.attn_fp8:
         raise SystemExit("--act_dtype fp16 does not go with --attn_fp8: the fp16 library has no fp8 P.V attention")
+    if args.cfg_free and args.guidance_rescale > 0.0:
+        raise SystemExit("--cfg_free does not go with --guidance_rescale > 0: there is no guidance to rescale")
+    if args.cfg_free and args.synthetic_arch == "sdxl":
+        raise SystemExit("--cfg_free does not go with --synthetic_arch sdxl: the single-pass UNet is not built for text_time conditioning")
     if not args.do_classifier_free_guidance:
         raise SystemExit("the engine always runs classifier-free guidance (the reference's type=bool flag cannot be switched off either)")
     return args
@@ -475,7 +485,10 @@ def run_expansion(args, engine, sched, ds, writer=save_png, rng_device="cpu"):
                 noise = noise + torch.stack([u[7] for u in chunk_p])
         e = torch.stack([u[4] for u in chunk_p])
         b = torch.stack([u[5] for u in chunk_p])
-        emb = torch.cat([ds.uncond.expand(EB, -1, -1), torch.stack([u[6] for u in chunk_p])])   # cat[negative, prompt], :1184
+        if getattr(engine, "cfg_free", False):
+            emb = torch.stack([u[6] for u in chunk_p])                                          # --cfg_free: the prompt alone
+        else:
+            emb = torch.cat([ds.uncond.expand(EB, -1, -1), torch.stack([u[6] for u in chunk_p])])   # cat[negative, prompt], :1184
         engine.set_prompt(emb.to(dev))
         if ds.class_pooled is not None:
             # SDXL added_cond_kwargs (StableDiffusionXLPipeline.__call__): pooled text embeddings cat[negative, prompt] and
@@ -611,9 +624,21 @@ def build_engine(args, device=None, distributed=False):
     # transform_guidance differentiates through P chained steps (P activation stashes); direct_guidance one step at a time
     stash = max(1, args.guidance_period) if args.guidance_type == "transform_guidance" else 1
 
+    cfg_free = bool(getattr(args, "cfg_free", False))
+
     def make_engine(cfg, weights, layout):
+        if cfg_free and cfg.unet.add_time_dim > 0:      # a model directory is recognised as SDXL by its config files
+            raise SystemExit("--cfg_free does not go with SDXL models: the single-pass UNet is not built for text_time conditioning")
         return Engine(cfg, weights, enable_grad=guided, max_guidance_period=stash, device=dev, layout=layout, attn_fp8=args.attn_fp8,
-                      **({"act_dtype": args.act_dtype} if getattr(args, "act_dtype", "bf16") != "bf16" else {}))
+                      **({"act_dtype": args.act_dtype} if getattr(args, "act_dtype", "bf16") != "bf16" else {}),
+                      **({"cfg_free": True} if cfg_free else {}))
+
+    if cfg_free:
+        # every rank sees the same directory: refused here, in front of the rank-0-only load
+        if not args.synthetic and os.path.isdir(os.path.join(args.pretrained_model_name_or_path, "text_encoder_2")):
+            raise SystemExit("--cfg_free does not go with SDXL models: the single-pass UNet is not built for text_time conditioning")
+        log.info("--cfg_free: one UNet pass per step on the class prompt alone; --guidance_scale %g is unused and the negative prompt is "
+                 "not uploaded", args.guidance_scale)
 
     if distributed:
         # rank 0 loads + packs once; the packed device buffers go to the other ranks in one RCCL broadcast (launcher.py)

@@ -173,6 +173,17 @@ const char* dd_last_error(dd_engine* e);
 /* model: "unet" | "vae" | "guide" | "text"; key: Hugging Face / timm state-dict key; data: HOST fp32 */
 int dd_load_tensor(dd_engine* e, const char* model, const char* key, const float* data, int ndim, const int64_t* shape);
 int dd_finalize_weights(dd_engine* e);
+/* The CFG-free mode (still version 11: two entry points added, no struct and no existing argument list changed).  dd_set_cfg_free(e, 1)
+ * between dd_create and dd_finalize_weights (DD_ERR_STATE after it) builds an engine that runs the UNet ONCE per step, on the
+ * conditional prompt alone -- what diffusers pipelines do for guidance_scale <= 1, and how guidance-distilled and few-step checkpoints
+ * are sampled: the model output is m = c, dd_sampler_params.guidance_scale is not read.  Every "2B" below is then B: dd_set_prompt
+ * takes embeds [B, text_len, cross_dim] (conditional only), dd_unet_forward writes B images and dd_unet_vjp takes g_eps [B, ...];
+ * dd_denoise_step*, dd_transform_guidance, dd_direct_guidance* and dd_expand are called as before, under every solver, eta and sde_eta.
+ * Refused with a message: dd_set_schedule* with guidance_rescale != 0 (the rescale factor is identically 1 at m = c), and at
+ * dd_finalize_weights a UNet with unet_add_time_dim > 0 (SDXL text_time: its per-image bias tables are built for 2B rows).
+ * dd_cfg_free reports the setting (0 | 1; DD_ERR_ARG for a null engine).  0, the default, is the engine of every earlier version. */
+int dd_set_cfg_free(dd_engine* e, int on);
+int dd_cfg_free(dd_engine* e);
 /* Multi-GPU start-up (replaces every process of scripts/exps/expand_diff.sh:19-24 loading its own copy from disk): rank 0 loads and
  * finalizes as above; every other rank DECLARES the same tensors (shapes only, no data), finalizes -- the op graph and every packed
  * weight buffer are built from the shapes alone, in the same order -- and then receives the packed buffers (bf16 MFMA layouts, fp32

@@ -166,6 +166,22 @@ int dd_op_sampler_step_2m_n(const float* m2, int ld, const float* z, const float
                             uint64_t seed, int rng_stream, const uint64_t* unit_ids, float* z_prev, float* x0, int B, int C, int HW,
                             const float* coef_dev, const float* lin_dev, int prediction_type, float guidance_rescale, float* stats,
                             float* part, void* stream);
+/* The CFG-free step (dd_set_cfg_free: the UNet runs on the conditional prompt alone), m = c:
+ *   dd_op_sampler_step1: m1 fp32 rows [B*HW, ld], the conditional output -- there is no unconditional half and no mix, coef_dev[0] is
+ *       not read (coef_dev may be NULL outside the division form, lin_dev inside it).  Every optional input of dd_op_sampler_step_2m_n
+ *       with the same meaning and the same "modes chosen from the arguments alone": (prediction_type 0) the division form on
+ *       coef_dev[1..4], every other type the linear form on lin_dev; x0_prev != NULL and c != 0 the second-order term; sigma != 0 with
+ *       `noise` or unit_ids the stochastic step; both SDE-DPM-Solver++(2M).  No guidance_rescale / stats / part: the rescale factor is
+ *       identically 1 at m = c.  z' and x0 are those of dd_op_sampler_step_2m_n on m2 = [c; c] at any finite s, bit for bit
+ *       (fma(s, c - c, c) == c).
+ *   dd_op_sampler_step1_bwd: g_m1 bf16 rows [B*HW, ld], g_m written once (every column written, padding 0) -- no (1 - s, s) split;
+ *       g_z as dd_op_sampler_step_bwd.  g_m1 equals the conditional rows of dd_op_sampler_step_bwd at s = 1, bit for bit.
+ * Shapes and refusals as above. */
+int dd_op_sampler_step1(const float* m1, int ld, const float* z, const float* x0_prev, float c, const float* noise, float sigma,
+                        uint64_t seed, int rng_stream, const uint64_t* unit_ids, float* z_prev, float* x0, int B, int C, int HW,
+                        const float* coef_dev, const float* lin_dev, int prediction_type, void* stream);
+int dd_op_sampler_step1_bwd(const float* g_x0, const float* g_zprev, uint16_t* g_m1, int ld, float* g_z, int B, int C, int HW,
+                            const float* coef_dev, const float* lin_dev, int prediction_type, void* stream);
 int dd_op_sumpool2x2(const uint16_t* src, int src_ld, uint16_t* dst, int dst_ld, int B, int H, int W, int C, int accumulate,
                      void* stream);
 int dd_op_geglu_bwd(const uint16_t* raw, int ld_raw, const uint16_t* dout, int ld_dout, uint16_t* draw, int ld_draw, int M,
