@@ -120,7 +120,7 @@ CF_LNFOLD, CF_ROWSTATS = 1024, 2048
 
 # every symbol declared in include/distdiff_hip_ops.h and include/distdiff_hip.h (checked by tests/test_abi.py)
 OPS_SYMBOLS = [
-    "dd_op_conv_gemm", "dd_op_conv_gemm_kind", "dd_op_conv_gemm_plan", "dd_op_conv_gemm_check", "dd_op_groupnorm_fwd", "dd_op_groupnorm_bwd", "dd_op_groupnorm_scratch_bytes",
+    "dd_op_conv_gemm", "dd_op_conv_gemm_kind", "dd_op_conv_gemm_plan", "dd_op_conv_halo_plan", "dd_op_conv_gemm_check", "dd_op_groupnorm_fwd", "dd_op_groupnorm_bwd", "dd_op_groupnorm_scratch_bytes",
     "dd_op_layernorm_fwd", "dd_op_layernorm_bwd", "dd_op_attention_fwd", "dd_op_attention_bwd",
     "dd_op_attention_gemm_workspace", "dd_op_attention_gemm_fwd", "dd_op_attention_gemm_bwd",
     "dd_op_attention", "dd_op_attention_plan", "dd_op_attention_scratch_bytes",
@@ -165,6 +165,8 @@ def _declare(l):
     l.dd_op_conv_gemm.argtypes = [C.POINTER(ConvGemmParams), sz, vp]
     l.dd_op_conv_gemm_kind.argtypes = [C.POINTER(ConvGemmParams), sz]
     l.dd_op_conv_gemm_plan.argtypes = [C.POINTER(ConvGemmParams), sz, vp]
+    if hasattr(l, "dd_op_conv_halo_plan"):      # (added without a version bump, as the CFG-free symbols below)
+        l.dd_op_conv_halo_plan.argtypes = [C.POINTER(ConvGemmParams), sz, vp]
     l.dd_op_conv_gemm_check.argtypes = [C.POINTER(ConvGemmParams), vp]
     l.dd_op_groupnorm_fwd.argtypes = [C.POINTER(GroupNormParams), vp]
     l.dd_op_groupnorm_bwd.argtypes = [C.POINTER(GroupNormParams), vp]

@@ -308,7 +308,7 @@ static int nonempty_split(int split, int ksteps) {
 
 int conv_gemm_pick_split(int M, int N, int K) {
   int s = small_split(M, N, K);
-  // the chunk split of the halo-resident kernel at the 8 x 8 level (conv_halo_split: it needs geometry this query does not have,
+  // the chunk split of the halo-resident kernel at the 8 x 8 level (conv_halo.hip, halo_chunk_split: it needs geometry this query does not have,
   // so every small-M 3x3-shaped problem with N % 320 == 0 reserves its scratch)
   if (M <= 16384 && (M & 255) == 0 && N % 320 == 0 && K % 576 == 0 && K >= 1152) {
     int hs = 1;
@@ -356,7 +356,7 @@ static bool rowstats_shape_ok(const ConvGemmParams& p) {
 // The launcher's decision, in one place and in this order: refusal, path, form inside the path, split, and whether CF_STATS / CF_ROWSTATS
 // are honoured (with how many row spans).  launch_conv_gemm acts on it, conv_gemm_plan_query reports it, conv_gemm_can_emit_* ask it with
 // the flag set.  Only the buffers of the two statistics flags are not looked at here (conv_gemm_plan).  On return p is the problem as the
-// chosen kernel gets it (ksplit set; partial dropped when the 8 x 8 chunk split does not fit the scratch).
+// chosen kernel gets it (ksplit set).
 static hipError_t plan_problem(ConvGemmParams& p, size_t partial_cap_bytes, ConvPlan* pl) {
   *pl = ConvPlan{KIND_GENERAL, 0, 1, 0, false, false, 0};
   const bool stats = (p.flags & CF_STATS) != 0, rowstats = (p.flags & CF_ROWSTATS) != 0;
@@ -379,17 +379,11 @@ static hipError_t plan_problem(ConvGemmParams& p, size_t partial_cap_bytes, Conv
     pl->form = cfg;
     return hipSuccess;
   }
-  {
-    // deep 3x3 / stride 1: halo-resident input tile; at the 8 x 8 level with a chunk split into the split-K scratch + the reduce kernel
-    ConvGemmParams q = p;
-    const int hs = conv_halo_split(q);
-    if (hs > 1 && (size_t)hs * p.M * p.N * sizeof(float) > partial_cap_bytes) q.partial = nullptr;     // scratch too small: no split form
-    if (const int form = conv_halo_config(q)) {
-      if (conv_halo_split(q) > 1) { q.ksplit = hs; pl->split = hs; }
-      p = q;
-      pl->kind = conv_halo_kernel_kind(p, form); pl->form = form; pl->stats = stats;
-      return pl->kind ? hipSuccess : hipErrorInvalidValue;
-    }
+  // deep 3x3 / stride 1: halo-resident input tile; at the 8 x 8 level with a chunk split into the split-K scratch + the reduce kernel
+  if (conv_halo_plan(p, partial_cap_bytes, &pl->halo)) {
+    if (pl->halo.split > 1) p.ksplit = pl->halo.split;
+    pl->kind = pl->halo.kind; pl->form = pl->halo.form; pl->split = pl->halo.split; pl->stats = stats;
+    return hipSuccess;
   }
   // K = 320 pointwise layers: weight-stationary GEMM.  It has no residual and no GroupNorm-partials epilogue (gemm_ws_config refuses
   // CF_RES and CF_STATS), so the SAME problem with CF_STATS set is not refused but moves on to the ping-pong GEMM below, which has both.
@@ -447,6 +441,16 @@ int conv_gemm_plan_query(ConvGemmParams p, size_t partial_cap_bytes, int* out4) 
   return pl.kind;
 }
 
+int conv_halo_plan_query(ConvGemmParams p, size_t partial_cap_bytes, int* out12) {
+  ConvPlan pl;
+  if (conv_gemm_plan(p, partial_cap_bytes, &pl) != hipSuccess || pl.empty || (pl.kind != KIND_HALO && pl.kind != KIND_HALO_PERSIST)) return 0;
+  const HaloPlan& h = pl.halo;
+  const int out[12] = {h.kind, h.form, 1 << h.geo.ltw, h.geo.th, h.geo.tiles_x, h.geo.tiles_y, h.geo.ipt, h.geo.tab, h.lds, h.grid_x, h.grid_y,
+                       h.kind == KIND_HALO_PERSIST};
+  for (int i = 0; i < 12; ++i) out12[i] = out[i];
+  return 1;
+}
+
 int conv_gemm_kind(ConvGemmParams p, size_t partial_cap_bytes) { return conv_gemm_plan_query(p, partial_cap_bytes, nullptr); }
 
 // adds the split's fp32 partial sums and applies the epilogue
@@ -465,7 +469,7 @@ hipError_t launch_conv_gemm(ConvGemmParams p, size_t partial_cap_bytes, hipStrea
   if (e != hipSuccess || pl.empty) return e;
   if (pl.kind == KIND_WS) return launch_gemm_ws(p, pl.form, stream);
   if (pl.kind == KIND_PPS) return launch_gemm_pp(p, pl.form, stream);
-  if (pl.kind == KIND_HALO || pl.kind == KIND_HALO_PERSIST) e = launch_conv_halo(p, pl.form, pl.kind, stream);
+  if (pl.kind == KIND_HALO || pl.kind == KIND_HALO_PERSIST) e = launch_conv_halo(p, pl.halo, stream);
   else if (pl.form) e = launch_conv_gemm_big(p, pl.form, stream);
   else {
     static bool attr_done = false;

@@ -18,7 +18,11 @@
 // Where the loop lives: pp_kloop.h holds the K-step (pp_kstep, also gemm_pps_kernel's), the chunk x tap loop around it with the halo refill
 // (pp_halo_kloop, called by both kernels of this file) and the weight-row map (pp_weight_row); pp_epilogue.h the epilogue; common.h the XCD
 // tile range.  This file keeps what differs between its two kernels: tile selection and the persistent walk, the two halo address schemes,
-// the prologues, the narrow and chunk-split stores.
+// the prologues, the narrow and chunk-split stores.  Stating the rest of the device side once for both kernels (LDS layout, thread
+// decomposition, tile context, halo pixel split, one refill stager) kept registers, scratch and bits but measured 1-3 % slower in every
+// instantiation, so the kernels keep their own text (profiles/halo_unified.json).
+// Host side, at the end of the file: halo_geometry, conv_halo_plan (the ONE decision: form, kernel, chunk split, address table, LDS bytes,
+// grid) and launch_conv_halo, which acts on that plan and recomputes nothing.
 #include "common.h"
 #include "conv_dispatch.h"
 #include "conv_epilogue.h"
@@ -27,12 +31,7 @@
 
 namespace {
 
-// Tile geometry (host: halo_geometry): a tile is th x tw OUTPUT pixels of one image (th * tw = 256 or 512, tw a power of two >= 16 that
-// divides Wo: Wo itself, or 64 / 128 of a wider power-of-two row, or the largest power-of-two factor of a width such as 48 / 96 / 192 / 768),
-// tiles_x = Wo / tw of them side by side; its halo is (th + 2) x (tw + 2) LOGICAL input
-// pixels (the fused nearest-2x upsample of the decoder's / UNet's upsamplers reads stored pixel (iy >> shift, ix >> shift)).
-struct HaloGeo { int ltw, th, halo_px, tiles_x, tiles_y, ipt, tab; };   // tab: the one-tile kernel uses the LDS halo address table   // ipt: images per tile (4 at 8 x 8: a tile is 4 whole images, each with its own 10 x 10 halo block)
-
+// (Tile geometry: HaloGeo, conv_dispatch.h; host: halo_geometry.)
 // CF_STATS block slot of the 64 tile pixels r .. r + 63 (r % 64 == 0) of the tile at (y0, x0) of the image whose first output row is mimg.
 // tw >= 64: they are 64 consecutive output rows m inside one image row, slot m >> 6 as in every other kernel.  tw = 16 / 32: they are
 // 64 / tw image rows x tw pixels, which with several tiles per image row are NOT consecutive in m; the consumer (norm.hip,
@@ -351,6 +350,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo_persist_kernel(ConvGemmParam
   }
 }
 
+// ---- the host side: geometry, the one plan, the one launch --------------------------------------------------------------------------------
 bool halo_geometry(const ConvGemmParams& p, int bm, HaloGeo* g) {
   const int Wo = p.Wo, Ho = p.Ho;
   g->ipt = 1;
@@ -382,128 +382,106 @@ bool halo_geometry(const ConvGemmParams& p, int bm, HaloGeo* g) {
 }
 
 constexpr int LDS_MAX = 163840;
-// Dynamic LDS of form f on geometry g: two weight stages, the halo, the bias row(s) and the halo address table.  The persistent kernel has two
-// bias slots (tile parity) and always the table; the one-tile kernel has the table iff g.tab.
-int halo_lds_bytes(const HaloForm& f, const HaloGeo& g, bool persist) {
-  const int table = (persist || g.tab) ? ((g.halo_px + 7) >> 3) * 256 : 0;
-  return 2 * f.bn() * 128 + ((g.halo_px + 7) & ~7) * 128 + (persist ? 2 : 1) * f.bn() * 4 + table + 64;
+// Dynamic LDS of a form with bn columns on a halo of halo_px pixels, as the kernels carve it: two weight stages, the halo (whole 8-pixel
+// pieces), the bias row (persistent kernel: two slots, tile parity), the halo address table (persistent kernel: always; one-tile: table)
+struct HaloLds {
+  int plain, table_bytes;
+  constexpr int total(bool with_table) const { return plain + (with_table ? table_bytes : 0); }
+};
+constexpr HaloLds halo_lds(int bn, int halo_px, bool persist) {
+  return {2 * bn * 128 + ((halo_px + 7) & ~7) * 128 + (persist ? 2 : 1) * bn * 4 + 64, ((halo_px + 7) >> 3) * 256};
 }
-
-template <int ID, bool MI = false>
-hipError_t run_halo(const ConvGemmParams& p, const HaloGeo& g, hipStream_t stream) {
-  constexpr HaloForm f = halo_form(ID);
-  HaloGeo gg = g;
-  gg.tab = 1;                                            // halo address table behind the bias block when it fits
-  if (!conv_env().halo_tab || halo_lds_bytes(f, gg, false) > LDS_MAX) gg.tab = 0;
-  const int lds = halo_lds_bytes(f, gg, false);
-  static int attr = 0;
-  if (attr < lds) { hipFuncSetAttribute((const void*)conv_halo_kernel<f.tn, f.wn, MI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = lds; }
-  const int tiles = (p.M / f.bm()) * ((p.N + f.bn() - 1) / f.bn());
-  hipLaunchKernelGGL((conv_halo_kernel<f.tn, f.wn, MI>), dim3(tiles, MI ? p.ksplit : 1), dim3(512), lds, stream, p, gg);
-  return hipGetLastError();
-}
-
-template <int ID>
-hipError_t run_halo_persist(const ConvGemmParams& p, const HaloGeo& g, hipStream_t stream) {
-  constexpr HaloForm f = halo_form(ID);
-  const int lds = halo_lds_bytes(f, g, true);
-  static int attr = 0;
-  if (attr < lds) { hipFuncSetAttribute((const void*)conv_halo_persist_kernel<f.tn, f.wn>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = lds; }
-  const int cus = persistent_cus();
-  const int tiles = (p.M / f.bm()) * (p.N / f.bn());
-  const int grid = tiles >= cus ? cus : (tiles + 7) & ~7;
-  hipLaunchKernelGGL((conv_halo_persist_kernel<f.tn, f.wn>), dim3(grid), dim3(512), lds, stream, p, g);
-  return hipGetLastError();
-}
-
-// true iff form f of this problem runs on conv_halo_persist_kernel: 512 x 128 tiles with a short K loop (the decoder's levels, any width
-// halo_geometry accepts: 128 ... 1024 as 192 / 384 / 768), next tile's first stage requested under the epilogue
-bool halo_persist_ok(const ConvGemmParams& p, const HaloGeo& g, const HaloForm& f) {
-  const int persist = conv_env().halo_persist;
-  // (address table: halo row < 31, column < 256, byte offsets inside the halo's stored rows below 8 MB)
-  return f.persist && persist && g.ipt == 1 && p.N % f.bn() == 0 && (p.cin >> 6) <= persist * 8 &&
-         g.th + 2 < 31 && (1 << g.ltw) + 2 < 256 && (size_t)(g.th + 3) * p.W * p.x_ld * 2 < (8u << 20) &&
-         halo_lds_bytes(f, g, true) <= LDS_MAX;
-}
-
-}  // namespace
 
 // chunk split of the 8 x 8 level (M = 64 pixels x images: 64 tiles of 256 x 320 at 64 images -- a quarter of the chip): the smallest
 // power of two that gives >= 192 workgroups -- halved until it DIVIDES the chunk count (the kernel hands ceil(chunks / split) chunks to
 // every blockIdx.y: with a remainder the last workgroups would start behind the last chunk; Cin = 2560 at 16 images: 16 -> 8) -- with
-// every workgroup >= 2 chunks; 1 = this is not that case.  Needs the split-K scratch.
-int conv_halo_split(const ConvGemmParams& p) {
+// every workgroup >= 2 chunks; 1 = this is not that case.  Needs the split-K scratch, large enough for the split's fp32 partial sums.
+int halo_chunk_split(const ConvGemmParams& p, size_t partial_cap_bytes) {
   if (!conv_env().halo_8x8 || p.Wo != 8 || p.Ho != 8 || p.H != 8 || p.W != 8 || p.shift || p.stride != 1 || (p.B & 3) || p.N % 320 || !p.partial) return 1;
   if (p.flags & ~(CF_BIAS | CF_RES | CF_RELU)) return 1;
   const int tiles = (p.M / 256) * (p.N / 320), chunks = p.cin >> 6;
   int s = 1;
   while (tiles * s < 192 && s < 16) s *= 2;
   while (s > 1 && (chunks % s || chunks / s < 2)) s >>= 1;
-  return s;
+  return (size_t)s * p.M * p.N * sizeof(float) > partial_cap_bytes ? 1 : s;      // scratch too small: no split form
 }
 
-// 0 = not eligible, else the tile form (HALO_FORMS id).  Epilogues: bias, residual, ReLU, CF_STATS (the narrow form: bias, fp32 output).  The host
-// reads the tap table once per weight tensor elsewhere: here the caller guarantees a 3x3 / pad 1 table (ntaps == 9 with offsets in
-// {-1, 0, 1}^2), which every packer emits for KH = KW = 3, pad = 1.
-int conv_halo_config(const ConvGemmParams& p) {
+// Form f on this problem, or false: geometry, kernel, address table, LDS bytes and grid -- each decided here and nowhere else.  split > 1:
+// the chunk-split form of the 8 x 8 level, the only one whose tiles are four whole images and that need not fill the chip by tiles alone.
+bool halo_plan_form(const ConvGemmParams& p, const HaloForm& f, int split, HaloPlan* hp) {
   const ConvEnv& env = conv_env();
-  if (!env.conv_halo || p.force_small) return 0;
+  HaloGeo g;
+  if (!halo_geometry(p, f.bm(), &g) || (g.ipt > 1) != (f.multi_image && split > 1)) return false;
+  const int tiles = (p.M / f.bm()) * ((p.N + f.bn() - 1) / f.bn());       // (N < bn: the narrow form, one n-tile)
+  if (split == 1 && tiles < 192) return false;            // needs (most of) the chip: small grids keep the split-K forms
+  const HaloLds one = halo_lds(f.bn(), g.halo_px, false), per = halo_lds(f.bn(), g.halo_px, true);
+  if (one.total(false) > LDS_MAX) return false;
+  // conv_halo_persist_kernel: 512 x 128 tiles with a short K loop (the decoder's levels, any width halo_geometry accepts: 128 ... 1024
+  // as 192 / 384 / 768), next tile's first stage requested under the epilogue.  Its address table: p.shift <= 1 ((hy + 1) >> 1), halo
+  // row < 31, column < 256, byte offsets inside the halo's stored rows below 8 MB.
+  const bool persist = f.persist && env.halo_persist && p.shift <= 1 && g.ipt == 1 && p.N % f.bn() == 0 && (p.cin >> 6) <= env.halo_persist * 8 &&
+                       g.th + 2 < 31 && (1 << g.ltw) + 2 < 256 && (size_t)(g.th + 3) * p.W * p.x_ld * 2 < (8u << 20) && per.total(true) <= LDS_MAX;
+  g.tab = persist || (env.halo_tab && one.total(true) <= LDS_MAX);        // the one-tile kernel: behind the bias block when it fits
+  const int cus = persistent_cus();
+  *hp = HaloPlan{f.id, persist ? KIND_HALO_PERSIST : KIND_HALO, split, g, persist ? per.total(true) : one.total(g.tab != 0),
+                 persist ? (tiles >= cus ? cus : (tiles + 7) & ~7) : tiles, split};
+  return true;
+}
+
+// the instantiation that runs a plan, by the names of HALO_FORMS.  attr: the dynamic LDS bytes fn has been raised to
+struct HaloEntry { int form, kind; bool multi_image; void (*fn)(ConvGemmParams, HaloGeo); int attr; };
+template <int ID, bool MI = false>
+constexpr HaloEntry one_tile() { constexpr HaloForm f = halo_form(ID); return {ID, KIND_HALO, MI, conv_halo_kernel<f.tn, f.wn, MI>, 0}; }
+template <int ID>
+constexpr HaloEntry persistent() { constexpr HaloForm f = halo_form(ID); return {ID, KIND_HALO_PERSIST, false, conv_halo_persist_kernel<f.tn, f.wn>, 0}; }
+
+}  // namespace
+
+// The plan of a halo launch, or false (not eligible: shape, flags, alignment, 32-bit offsets, no form fits).  Epilogues: bias, residual,
+// ReLU, CF_STATS (the narrow form: bias, fp32 output).  The host reads the tap table once per weight tensor elsewhere: here the caller
+// guarantees a 3x3 / pad 1 table (ntaps == 9 with offsets in {-1, 0, 1}^2), which every packer emits for KH = KW = 3, pad = 1.
+bool conv_halo_plan(const ConvGemmParams& p, size_t partial_cap_bytes, HaloPlan* hp) {
+  const ConvEnv& env = conv_env();
+  if (!env.conv_halo || p.force_small) return false;
   if (p.ntaps != 9 || p.stride != 1 || p.shift > 1 || p.parity || (p.H << p.shift) != p.Ho || (p.W << p.shift) != p.Wo || (p.cin & 63) ||
-      p.K != 9 * p.cin) return 0;
+      p.K != 9 * p.cin) return false;
   // narrow outputs (conv_out of the decoder / the UNet, N <= 4): a 512 x 32 form whose weight stage is 4 KB -- the input tile is read once
   // from HBM (halo) instead of being gathered tap by tap through the 128-wide tiles of the general kernels (60 of 64 columns wasted)
   const bool narrow = env.halo_narrow && p.N <= 4 && !(p.flags & ~(CF_BIAS | CF_OUT_F32)) && !p.bias_sel && !p.shift && p.ksplit <= 1;
-  if (!narrow && ((p.flags & ~(CF_BIAS | CF_RES | CF_RELU | CF_STATS)) || p.bias_sel)) return 0;
-  if ((!narrow && (p.y_ld & 7)) || ((p.flags & CF_RES) && (p.res_ld & 7)) || (p.x_ld & 7) || p.alpha != 1.f) return 0;
-  if ((size_t)p.H * p.W * (size_t)p.x_ld * 2 >= 0xF0000000ull) return 0;         // byte offsets are per image
-  if (p.M != p.B * p.Ho * p.Wo) return 0;
-  HaloGeo g;
+  if (!narrow && ((p.flags & ~(CF_BIAS | CF_RES | CF_RELU | CF_STATS)) || p.bias_sel)) return false;
+  if ((!narrow && (p.y_ld & 7)) || ((p.flags & CF_RES) && (p.res_ld & 7)) || (p.x_ld & 7) || p.alpha != 1.f) return false;
+  if ((size_t)p.H * p.W * (size_t)p.x_ld * 2 >= 0xF0000000ull) return false;     // byte offsets are per image
+  if (p.M != p.B * p.Ho * p.Wo) return false;
   if (narrow) {
-    constexpr HaloForm f = halo_form(HALO_NARROW);
-    if (p.N == 4 && (p.flags & CF_OUT_F32) && (p.y_ld & 3)) return 0;             // float4 stores
-    if (!halo_geometry(p, f.bm(), &g) || p.M / f.bm() < 192) return 0;
-    return halo_lds_bytes(f, g, false) > LDS_MAX ? 0 : f.id;
+    if (p.N == 4 && (p.flags & CF_OUT_F32) && (p.y_ld & 3)) return false;         // float4 stores
+    return halo_plan_form(p, halo_form(HALO_NARROW), 1, hp);
   }
-  if (conv_halo_split(p) > 1) return 5;                  // 8 x 8 level: 256 x 320 multi-image tiles + chunk split (fp32 partials)
-  if (p.ksplit > 1) return 0;
+  // 8 x 8 level: 256 x 320 multi-image tiles + chunk split (fp32 partials into the split-K scratch, then the reduce kernel)
+  const int split = halo_chunk_split(p, partial_cap_bytes);
+  if (split > 1) return halo_plan_form(p, halo_form(HALO_256x320), split, hp);
+  if (p.ksplit > 1) return false;
   // tile forms by preference: 512 x 160 / 512 x 128 (20 / 16 KB of weights + ~10 KB of halo per K-step instead of 40 / 32 + 5.6) where the
   // image geometry allows 512-pixel tiles, else 256 x 320 / 256 x 256
   for (const HaloForm& f : HALO_FORMS) {
     if (f.id == HALO_NARROW || p.N % f.bn()) continue;
     if (f.bm() == 512 && !env.halo_tall && p.N != 128) continue;
     if (f.bn() == 128 && p.N % 320 == 0) continue;      // 320-multiples: 160-wide tiles
-    if (!halo_geometry(p, f.bm(), &g) || g.ipt > 1) continue;   // multi-image tiles (8 x 8) exist in the chunk-split form only (above)
-    if ((p.M / f.bm()) * (p.N / f.bn()) < 192) continue;        // needs (most of) the chip: small grids keep the split-K forms
-    if (halo_lds_bytes(f, g, false) > LDS_MAX) continue;
-    return f.id;
+    if (halo_plan_form(p, f, 1, hp)) return true;
   }
-  return 0;
+  return false;
 }
 
-// which kernel runs form `form` of this problem: KIND_HALO conv_halo_kernel, KIND_HALO_PERSIST conv_halo_persist_kernel, 0 neither
-int conv_halo_kernel_kind(const ConvGemmParams& p, int form) {
-  const HaloForm f = halo_form(form);
-  HaloGeo g;
-  if (!f.id || !halo_geometry(p, f.bm(), &g)) return 0;
-  if (halo_persist_ok(p, g, f)) return KIND_HALO_PERSIST;
-  // four whole 8 x 8 images per tile: the chunk-split form only, with a split that divides the chunks
-  if (g.ipt > 1 && !(f.multi_image && p.ksplit > 1 && (p.cin >> 6) % p.ksplit == 0)) return 0;
-  return KIND_HALO;
-}
-
-// kind: what conv_halo_kernel_kind(p, form) returned
-hipError_t launch_conv_halo(const ConvGemmParams& p, int form, int kind, hipStream_t stream) {
-  HaloGeo g;
-  if (!kind || !halo_geometry(p, halo_form(form).bm(), &g)) return hipErrorInvalidValue;
-  if (kind == KIND_HALO_PERSIST) return run_halo_persist<2>(p, g, stream);
-  switch (form) {
-    case 1: return run_halo<1>(p, g, stream);
-    case 2: return run_halo<2>(p, g, stream);
-    case 4: return run_halo<4>(p, g, stream);
-    case 5: return g.ipt > 1 ? run_halo<5, true>(p, g, stream) : run_halo<5>(p, g, stream);
-    case 6: return run_halo<6>(p, g, stream);
-    default: return hipErrorInvalidValue;
+// Raises the kernel's dynamic LDS limit where needed and launches the plan, for both kernels.  p.ksplit = hp.split (the planner sets it).
+hipError_t launch_conv_halo(const ConvGemmParams& p, const HaloPlan& hp, hipStream_t stream) {
+  static HaloEntry entries[] = {persistent<HALO_512x128>(), one_tile<HALO_NARROW>(), one_tile<HALO_512x128>(), one_tile<HALO_256x256>(),
+                                one_tile<HALO_256x320>(), one_tile<HALO_256x320, true>(), one_tile<HALO_512x160>()};
+  for (HaloEntry& e : entries) {
+    if (e.form != hp.form || e.kind != hp.kind || e.multi_image != (hp.geo.ipt > 1)) continue;
+    if (e.attr < hp.lds) { (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, hp.lds); e.attr = hp.lds; }
+    hipLaunchKernelGGL(e.fn, dim3(hp.grid_x, hp.grid_y), dim3(512), hp.lds, stream, p, hp.geo);
+    return hipGetLastError();
   }
+  return hipErrorInvalidValue;
 }
 
 #ifdef DD_TRACE

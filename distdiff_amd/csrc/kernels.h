@@ -76,6 +76,10 @@ int conv_gemm_kind(ConvGemmParams p, size_t partial_cap_bytes);
 // small conv_gemm_kernel; 1 128 x 256, 2 256 x 160, 3 256 x 128 on 8 waves; 4 128 x 160, 5 128 x 128 as two 4-wave workgroups per CU),
 // the split-K (8 x 8 halo level: chunk split) the launch uses, 1 when the small kernel runs 256 x 64 tiles instead of 128 x 128}
 int conv_gemm_plan_query(ConvGemmParams p, size_t partial_cap_bytes, int* out4);
+// What the launch does beyond the bits when a halo kernel runs the problem: 0 when none would, else 1 and out12 = {kind, HALO_FORMS id,
+// tile width, tile height, tiles per image row, tile rows per image, images per tile, halo address table 0 / 1, dynamic LDS bytes, grid x,
+// grid y (the chunk split), persistent 0 / 1}
+int conv_halo_plan_query(ConvGemmParams p, size_t partial_cap_bytes, int* out12);
 // Preferred split for a shape (used by the engine to size the workspace).
 int conv_gemm_pick_split(int M, int N, int K);
 // true iff launch_conv_gemm(p, partial_cap_bytes) will honour CF_STATS for this problem (persistent big-tile kernel, no split-K,

@@ -19,6 +19,10 @@ int dd_op_conv_gemm_plan(const ConvGemmParams* p, size_t cap, int* out4) {
   if (!p) return -1;                                    // DD_ERR_ARG
   return conv_gemm_plan_query(*p, cap, out4);
 }
+int dd_op_conv_halo_plan(const ConvGemmParams* p, size_t cap, int* out12) {
+  if (!p || !out12) return -1;                          // DD_ERR_ARG
+  return conv_halo_plan_query(*p, cap, out12);
+}
 int dd_op_conv_gemm_check(const ConvGemmParams* p, void* st) {
   // The synchronous companion for ABI users who want the contract checked against the DEVICE table: waits for the stream, reads the
   // tap table back and validates it (entries in range; a one-tap stride-1 same-size launch carries the centre tap).  0 = fine.

@@ -49,6 +49,12 @@ int dd_op_conv_gemm_kind(const struct ConvGemmParams* p, size_t partial_cap_byte
  * the small conv_gemm_kernel; 1 128 x 256, 2 256 x 160, 3 256 x 128 tiles on 8 waves; 4 128 x 160, 5 128 x 128 as two 4-wave workgroups
  * per CU), split-K (chunk split at the 8 x 8 halo level) the launch uses, 1 when the small kernel runs 256 x 64 instead of 128 x 128 tiles} */
 int dd_op_conv_gemm_plan(const struct ConvGemmParams* p, size_t partial_cap_bytes, int* out4);
+/* What the launch does beyond the output's bits when one of the halo 3x3 kernels runs the problem (the same dry decision: no device
+ * access).  Returns 0 when the launcher would not run a halo kernel (a refused problem included), DD_ERR_ARG for a null argument, else 1
+ * with out12 = {kind (1 | 2), tile form (1: 512 x 32 narrow, 2: 512 x 128, 4: 256 x 256, 5: 256 x 320, 6: 512 x 160), tile width and
+ * height in output pixels, tiles per image row, tile rows per image, images per tile (4 at 8 x 8 images), halo address table in LDS
+ * 0 / 1, dynamic LDS bytes, grid x, grid y (the chunk split), persistent kernel 0 / 1}.  Added without a version bump. */
+int dd_op_conv_halo_plan(const struct ConvGemmParams* p, size_t partial_cap_bytes, int* out12);
 /* Synchronous check of that contract against the DEVICE table (waits for the stream, copies the table back): 0 when every entry is in
  * range and a pointwise launch carries the centre tap.  For ABI users without a host copy of their tables; never called by the engine. */
 int dd_op_conv_gemm_check(const struct ConvGemmParams* p, void* stream);

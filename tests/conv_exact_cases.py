@@ -85,6 +85,9 @@ CASES = [
     conv("halo_w80", 8, 128, 320, 80, 80, (HALO, None, 1)),
     conv("halo_w96", 6, 320, 320, 96, 96, (HALO, None, 1)),
     conv("halo_w96_dgrad", 6, 320, 320, 96, 96, (HALO, None, 1), dgrad=True, fl=""),
+    # 4 image rows of 128 pixels: 256 x 320 tiles at tw = 128, th = 2, whose halo address table does not fit the LDS (166 464 B): the
+    # per-piece address arithmetic of the one-tile kernel, reached without DD_HALO_TAB=0 (tests/golden/halo_plan_table.npz: table = 0)
+    conv("halo_4x128_table_does_not_fit", 48, 64, 640, 4, 128, (HALO, None, 1), f16=True),
     conv("halo_8x8_cin2560_split8", 32, 2560, 1280, 8, 8, (HALO, None, 8)),
     conv("halo_8x8_cin2560_split8_dgrad_split4", 32, 2560, 1280, 8, 8, (HALO, None, 4), dgrad=True, fl=""),
     conv("halo_8x8_cin2560_b16", 16, 2560, 1280, 8, 8, (HALO, None, 8)),
@@ -156,6 +159,7 @@ STAT_CASES = [
     sconv("s_halo_w48_block_map", 24, 64, 320, 48, 48, (HALO, None, 1), "bs", f16=True, slots="halo"),
     sconv("s_halo_w80_block_map", 8, 128, 320, 80, 80, (HALO, None, 1), "bs", slots="halo"),
     sconv("s_halo_w96_block_map_res", 6, 320, 320, 96, 96, (HALO, None, 1), "brs", slots="halo"),
+    sconv("s_halo_4x128_table_does_not_fit_res", 48, 64, 640, 4, 128, (HALO, None, 1), "brs"),
     sconv("s_persist_256_64x64_res", 12, 64, 256, 64, 64, (PERSIST, None, 1), "brs", f16=True, slots="halo"),
     sconv("s_persist_w256_res", 1, 64, 256, 256, 256, (PERSIST, None, 1), "brs", slots="halo"),
     sconv("s_persist_n128_256x512_res", 1, 128, 128, 256, 512, (PERSIST, None, 1), "brs", slots="halo"),

@@ -15,7 +15,7 @@ and c1 multiples of 1/64 in [-1/2, 1/2), rstd multiples of 1/64 in [1/2, 3/2) --
 per output buffer, the SHA-256 of its raw bytes.  Every output buffer (y, the CF_STATS partials, the CF_ROWSTATS partials, the GEGLU raw
 stash, the fp32 split-K partial sums of the 8 x 8 form) is pre-filled with NaN and hashed whole, so an element that is not written, or
 one written outside the N columns, shows.  Each case first asserts (ops.conv_gemm_kind) that the launcher sends it to the intended kernel;
-the tile form named in a case is what conv_halo_config / launch_conv_halo give for its N.
+the tile form named in a case is what conv_halo_plan / launch_conv_halo give for its N.
 
 Shapes: the smallest that still reach each instantiation (>= 192 tiles wherever the planner asks for most of the chip) and each path of
 the shared loop: more tiles than workgroups (persistent walks of two tiles), an odd number of K-steps per tile (the weight-stage parity
